@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- phonon-histories/s of the HIP engine, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default workload: the reference's headline configuration (BASELINE.json configs[1]: NSCP
@@ -37,7 +37,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-# /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters
+# MI355X chip-level parameters
 HBM_PEAK_GBS = 8000.0
 # What the chip delivers in RANDOM 64-byte sectors from a table of GBs (tools/microbench/hbm_gather.hip, recorded in
 # profiles/r05/hbm_gather.log: 51.2 G sectors/s at 12, 16 or 32 waves per CU, 1 to 8 fetches in flight per lane): the
@@ -283,7 +283,42 @@ def parse_args(argv=None):
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, form the process group (gloo, no GPU), print its size and exit: "
                          "the CPU check of the launcher path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path left its caller -- the result block "
+                         "after the last step (and the chain's flush), summed over ranks -- as DIR/<name>.npy "
+                         "(float64; config 5's event grid as a fixed, seeded sample), so that two builds can be "
+                         "compared output for output")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_VOLUME_SAMPLES = 1 << 21   # counters of the event grid written by --dump-outputs (+ their indices: 32 MB)
+
+
+def dump_outputs(path, res, volume):
+    """--dump-outputs: the timed region's result (rank 0's, after the reduction over ranks) as float64 .npy files.
+    The event grid (10 GB) is sampled: DUMP_VOLUME_SAMPLES flat indices drawn with a fixed seed from the frames this
+    rank holds job totals for, written with the counters there.  Returns {name: shape} for the JSON line."""
+    import numpy as np
+    import torch
+    arrays = {"energy": res.energy, "counts": res.counts.astype(np.float64),
+              "scalars": res.scalars().astype(np.float64)}
+    if volume is not None:
+        runs = volume._valid_runs()                    # [(begin, end)) of the flat grid holding job totals
+        sizes = np.array([e - b for b, e in runs], dtype=np.int64)
+        starts = np.cumsum(sizes) - sizes              # where each run begins among the held counters
+        pos = np.unique(np.random.default_rng(0x5EED).integers(0, sizes.sum(), DUMP_VOLUME_SAMPLES))
+        run = np.searchsorted(starts, pos, side="right") - 1
+        index = np.array([b for b, _ in runs], dtype=np.int64)[run] + pos - starts[run]
+        picked = volume.counters[torch.from_numpy(index).to(volume.counters.device)]
+        arrays["volume_sample_index"] = index.astype(np.float64)   # flat index into count[type][frame][z][y][x]
+        arrays["volume_sample"] = (picked.to(torch.int64) & 0xFFFFFFFF).cpu().numpy().astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def rendezvous_only(args, rank, world):
@@ -507,6 +542,10 @@ def main():
     # stragglers, then the reduction of the bins (and of config 5's grid) -- timed from the first launch
     # to the reduced result, tables resident.  Strong scaling: the job's size does not grow with N.
     res_timed = result.to_result() if rank == 0 else None   # (the timed region's totals: the job leg reuses the block)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, res_timed, volume)
+        note(f"outputs of the timed region written to {args.dump_outputs}")
     job = None
     if not args.timed_only and not args.no_job:
         n_job = JOB_HISTORIES[args.config]
@@ -665,6 +704,8 @@ def main():
         }
         if job is not None:
             line["job"] = job
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if volume is not None:
             line["volume"] = volume_line
 

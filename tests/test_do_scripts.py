@@ -1,57 +1,37 @@
-"""The reference's own run scripts against this repository's command line and run configurations
-(build container only: skipped where /root/reference is absent; nothing of the reference is copied
-into the repository and nothing of it travels to the GPU box).
+"""The reference's own run scripts against this repository's command line and run configurations.
 
-north_star: "the existing do-*.sh drivers ... work unchanged".  Each do-script is run AS IT LIES in
-the reference tree, from a scratch directory that holds symbolic links to the scripts, `scripts/`
-and `vis/`, a Makefile for which `make -q` succeeds (scripts/do-fundamentals.sh:145-152) and a
-stand-in `./main` that writes its argument list to a file.  The captured tokens -- what
-RunSimulation assembles, scripts/do-fundamentals.sh:387-427 -- must be (a) exactly the run
+north_star: "the existing do-*.sh drivers ... work unchanged".  Each do-script of an unmodified
+checkout was run as it lies, from a scratch directory that held symbolic links to the scripts,
+`scripts/` and `vis/`, a Makefile for which `make -q` succeeds (scripts/do-fundamentals.sh:145-152)
+and a stand-in `./main` that wrote its argument list to a file; those argument lists -- what
+RunSimulation assembles, scripts/do-fundamentals.sh:387-427 -- are recorded in
+tests/golden/reference_do_scripts.json (written by tests/golden/make_reference_fixtures.py; nothing of
+the reference's sources is copied into the repository).  They must be (a) exactly the run
 configuration radiative3d_amd/configs.py transcribes and bench.py runs, at the script's TOA degree,
 and (b) accepted by host/cmdline.cpp: the model builds from them."""
+import json
 import os
-import shutil
 import subprocess
 
 import pytest
 
 from radiative3d_amd import Model, configs
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "scripts")), reason="reference tree not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_do_scripts.json")
 
 # what a script adds for its own bookkeeping and every run shares (do-fundamentals.sh:396-419)
 BOOKKEEPING = ("--reports=", "--output-dir=", "--report-file=", "--mparams-outfile=", "--num-phonons=", "--dump-grid")
 
 
-def run_do_script(tmp_path, script, edit=None):
-    """Run reference do-script `script` in a scratch directory; returns the tokens ./main was given."""
-    work = tmp_path / script.replace(".sh", "")
-    work.mkdir()
-    for entry in os.listdir(REF):
-        if entry.startswith("do-") and entry.endswith(".sh"):
-            os.symlink(os.path.join(REF, entry), work / entry)
-    os.symlink(os.path.join(REF, "scripts"), work / "scripts")
-    os.symlink(os.path.join(REF, "vis"), work / "vis")
-    if edit:   # a user's one-line choice inside the script (the scripts say "copy and edit this file")
-        text = open(os.path.join(REF, script)).read()
-        assert edit[0] in text
-        os.unlink(work / script)
-        (work / script).write_text(text.replace(edit[0], edit[1], 1))
-    argv_file = work / "argv.txt"
-    main = work / "main"
-    main.write_text('#!/bin/bash\nprintf \'%s\\n\' "$@" > "$R3D_ARGV_OUT"\n'
-                    'echo "#  R3D_GRID:"; echo "#  END R3D_GRID"\n')
-    main.chmod(0o755)
-    (work / "Makefile").write_text("main:\n")
-    assert subprocess.run(["make", "-q"], cwd=work).returncode == 0
-    env = dict(os.environ, R3D_ARGV_OUT=str(argv_file))
-    # (figure generation follows the run and needs octave: absent here, its errors are not the test's)
-    subprocess.run(["bash", "./" + script, "noseis"], cwd=work, env=env, capture_output=True, text=True, timeout=120)
-    assert argv_file.exists(), "the script never reached ./main"
-    tokens = argv_file.read_text().split("\n")[:-1]
-    shutil.rmtree(work / "data", ignore_errors=True)
-    return tokens
+def case_id(script, edit):
+    return script + ("+expl" if edit else "")
+
+
+def do_script_tokens(script, edit=None):
+    """The tokens do-script `script` (with the one-line `edit` a user makes, if any) gave ./main."""
+    rec = json.load(open(GOLDEN))["scripts"][case_id(script, edit)]
+    assert (rec["script"], rec["edit"]) == (script, list(edit) if edit else None)
+    return rec["argv"]
 
 
 def split(tokens):
@@ -75,9 +55,9 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("script,edit,config", CASES, ids=[c[0] + ("+expl" if c[1] else "") for c in CASES])
-def test_do_script_tokens_are_the_run_configuration(tmp_path, script, edit, config):
-    tokens = run_do_script(tmp_path, script, edit)
+@pytest.mark.parametrize("script,edit,config", CASES, ids=[case_id(c[0], c[1]) for c in CASES])
+def test_do_script_tokens_are_the_run_configuration(script, edit, config):
+    tokens = do_script_tokens(script, edit)
     run, book = split(tokens)
     deg = toa_degree(run)
     assert deg == (8 if "vids" in script else 9)                  # PopDefaults: waveform 9, video 8
@@ -102,7 +82,7 @@ def test_the_cli_accepts_a_do_script_command_line_end_to_end(tmp_path):
     exe = os.path.join(repo, "main")
     if not os.path.exists(exe):
         pytest.skip("./main not built")
-    tokens = run_do_script(tmp_path, "do-halfspace.sh")
+    tokens = do_script_tokens("do-halfspace.sh")
     out = tmp_path / "out"
     out.mkdir()
     args = [("--toa-degree=3" if t.startswith("--toa-degree=") else f"--output-dir={out}" if t.startswith("--output-dir=")
