@@ -528,6 +528,50 @@ uint32_t r3d_engine_accumulators(const r3d_engine* e);
 /* Number of scalar counters r3d_run_device expects.                         */
 #define R3D_N_SCALARS (3 + R3D_INV_NUM + R3D_EV_NUM)
 
+/* ---- per-bin standard errors from id-partitioned batches ---------------------
+ * THE ESTIMATOR.  A run of ids [first_id, first_id + n) in B batches, 2 <= B <= 64 (the launches of one engine
+ * that may be in flight): batch j is the ids [first_id + floor(j n / B), first_id + floor((j + 1) n / B)), run as
+ * ONE self-contained r3d_run_device launch with the run's seed into its own zeroed block X_j (energy, counts,
+ * scalars).  Histories are keyed by id, so the batches are a partition of the run and their blocks independent
+ * samples.  For every entry i of the energy and of the counts array
+ *     T_i  = sum_j X_j[i]                                   ADDED into the caller's result, as r3d_run does
+ *     se_i = sqrt( B/(B-1) * sum_j (X_j[i] - T_i/B)^2 )     the standard error of T_i: WRITTEN, not accumulated
+ * (batch means: B times the variance of the batch values estimates the variance of their sum).  Energies: T is
+ * the fp64 sum in the order j = 0 .. B-1.  Counts: T exact in u64, se in fp64 from the exactly converted
+ * values.  Scalars: summed in u64, no se.  The deviations are taken from the mean in a second pass
+ * (radiative3d_amd/stats/r3d_batch_moments.h), never as sum x^2 - (sum x)^2 / B; with u = 2^-53
+ *     |se - se_exact| <= 2 B^1.5 u max_j|X_j| + (B + 4) u se_exact,
+ * and the result has the same bits on every run (no atomics, fixed order).
+ *
+ * r3d_batch_moments: T and se of caller-owned blocks on `device` -- d_batch_energy [B][n_energy], d_batch_counts
+ * [B][n_counts], d_batch_scalars [B][n_scalars] (may be NULL), batch-major --, asynchronous on `stream` (a
+ * hipStream_t; NULL = the default stream); the blocks are only read.  d_energy_se / d_counts_se may be NULL.
+ *
+ * r3d_run_device_batched: the device-resident run -- the B launches go round-robin over four streams of the
+ * library's own (a batch's drain phase is filled by the batches behind it), ordered behind what `stream` holds
+ * when the call is made; the moments follow on `stream`.  Asynchronous.  d_energy, d_counts, d_scalars as for
+ * r3d_run_device (their device is taken to be the engine's).  d_batch_energy [B][r3d_energy_len] /
+ * d_batch_counts [B][r3d_counts_len]: NULL (scratch that lives in stream order until the moments are taken), or
+ * caller-owned to keep the blocks; they are zeroed by the call.  Do not start a second batched run of one engine
+ * before the first has finished: together they would pass the 64 launches in flight.
+ * r3d_run_batched: r3d_run plus the two se arrays (r3d_energy_len / r3d_counts_len doubles, host; may be NULL).
+ *
+ * Both runs REFUSE (non-zero, r3d_last_error, nothing enqueued, no buffer touched): B < 2, B > 64, n < B, a carry
+ * chain that awaits its flush, an attached event log, an attached production-finals buffer.  An attached event
+ * grid is fine: it accumulates atomically as in any run.                                                    */
+int r3d_batch_moments(int device, uint32_t n_batches,
+                      const double* d_batch_energy, uint64_t n_energy,
+                      const uint64_t* d_batch_counts, uint64_t n_counts,
+                      const uint64_t* d_batch_scalars, uint64_t n_scalars,
+                      double* d_energy, uint64_t* d_counts, uint64_t* d_scalars,
+                      double* d_energy_se, double* d_counts_se, void* stream);
+int r3d_run_device_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                           double* d_energy, uint64_t* d_counts, uint64_t* d_scalars,
+                           double* d_energy_se, double* d_counts_se,
+                           double* d_batch_energy, uint64_t* d_batch_counts, void* stream);
+int r3d_run_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                    r3d_result* out, double* energy_se, double* counts_se);
+
 /* Self-test hook: evaluates one of the kernel's own elementary functions
  * (radiative3d_amd/csrc/r3d_math.h -- the traversal uses these instead of the
  * device library's exp / log / atanh / asin / atan2 / sincos) on the device,

@@ -54,6 +54,14 @@ const char* r3dh_params_echo(r3dh_model* m);
 const char* r3dh_write_outputs(r3dh_model* m, const r3d_result* result, const char* outdir,
                                const char* trace_path, const char* mparams_path);
 
+/* The standard errors of a batched run (r3d.h r3d_run_batched: energy_se / counts_se laid out as the result's
+ * energy / counts) as seis_NNN_err.octv beside each seis_NNN.octv in `outdir` ("" = cwd), same Octave text
+ * conventions: matrices TraceXYZ_se, TracePS_se, CountPS_se and the scalars NumBins, NumBatches.  Returns 0 ok.
+ * r3dh_error_batches: what --error-batches=B in the model's arguments asked for (2..64; 0 if absent).        */
+int r3dh_write_errors(r3dh_model* m, const double* energy_se, const double* counts_se, uint32_t n_batches,
+                      const char* outdir);
+uint32_t r3dh_error_batches(const r3dh_model* m);
+
 /* For a model built with --device-tables (scattering tables left to the engine):
  * record what r3d_engine_scatterer_stats() returned, so that the scatterer dump
  * and r3dh_scatterer_info show the engine's numbers.  Returns 0 ok.            */

@@ -170,6 +170,10 @@ def host_lib():
         L.r3dh_grid_nodes.argtypes = [C.c_void_p, C.POINTER(GridNode), C.c_size_t]
         L.r3dh_grid_nodes_raw.restype = C.c_int
         L.r3dh_grid_nodes_raw.argtypes = [C.c_void_p, C.POINTER(GridNodeRaw), C.c_size_t]
+        L.r3dh_write_errors.restype = C.c_int
+        L.r3dh_write_errors.argtypes = [C.c_void_p, _dp, _dp, C.c_uint32, C.c_char_p]
+        L.r3dh_error_batches.restype = C.c_uint32
+        L.r3dh_error_batches.argtypes = [C.c_void_p]
         L.r3dh_seismometer_axes.restype = C.c_int
         L.r3dh_seismometer_axes.argtypes = [C.c_void_p, C.c_int]
         _host = L
@@ -310,6 +314,16 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_volume_read_range.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
         L.r3d_volume_reduce_by_frame.restype = C.c_int
         L.r3d_volume_reduce_by_frame.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        L.r3d_batch_moments.restype = C.c_int
+        L.r3d_batch_moments.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.r3d_run_device_batched.restype = C.c_int
+        L.r3d_run_device_batched.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]
+        L.r3d_run_batched.restype = C.c_int
+        L.r3d_run_batched.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
+                                      _dp, _dp]
         L.r3d_last_error.restype = C.c_char_p
         L.r3d_version.restype = C.c_char_p
         _hip[key] = L

@@ -111,6 +111,21 @@ const char* r3dh_write_outputs(r3dh_model* m, const r3d_result* result, const ch
   return nullptr;
 }
 
+int r3dh_write_errors(r3dh_model* m, const double* energy_se, const double* counts_se, uint32_t n_batches,
+                      const char* outdir) {
+  if (!m || !energy_se || !counts_se) return g_error = "r3dh_write_errors: null argument", 1;
+  if (n_batches < 2) return g_error = "r3dh_write_errors: a standard error needs at least 2 batches", 1;
+  try {
+    OutputSeismometerErrors(*m->model, energy_se, counts_se, n_batches, outdir ? outdir : "");
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
+uint32_t r3dh_error_batches(const r3dh_model* m) { return m ? m->mission.ErrorBatches : 0; }
+
 int r3dh_model_set_scatterer_stats(r3dh_model* m, int s, const double mfp[2], const double dipole[2]) {
   if (!m || !mfp || !dipole || s < 0 || s >= (int)m->model->Scatterers().size()) return 1;
   m->model->SetScattererStats(s, mfp, dipole);

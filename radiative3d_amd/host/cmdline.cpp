@@ -15,7 +15,7 @@ enum OptID {
   OPT_REPORTS, OPT_REPORT_FILE, OPT_OUTDIR, OPT_OCSRAW, OPT_SEISBINS, OPT_SEISBINSIZE,
   OPT_SEISARRAY, OPT_SEIS_P2P, OPT_SEIS_P2PW, OPTM_HELP, OPTM_DUMPGRID, OPTM_PARAMOUTFN,
   OPTM_RTTEST, OPTM_EVENTTEST, OPTM_RUNSIM, OPTX_SEED, OPTX_GPUS, OPTX_DEVTABLES, OPTX_HOSTTABLES,
-  OPTX_DEVICES, OPTX_SCATGRID, OPTX_SCATGRID_FILE
+  OPTX_DEVICES, OPTX_SCATGRID, OPTX_SCATGRID_FILE, OPTX_ERRBATCHES
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -46,7 +46,8 @@ const std::map<std::string, OptID>& option_table() {
       {"--run-simulation", OPTM_RUNSIM}, {"--run-sim", OPTM_RUNSIM},
       {"--seed", OPTX_SEED}, {"--gpus", OPTX_GPUS}, {"--device-tables", OPTX_DEVTABLES},
       {"--host-tables", OPTX_HOSTTABLES}, {"--devices", OPTX_DEVICES},
-      {"--scatter-grid", OPTX_SCATGRID}, {"--scatter-grid-file", OPTX_SCATGRID_FILE}};
+      {"--scatter-grid", OPTX_SCATGRID}, {"--scatter-grid-file", OPTX_SCATGRID_FILE},
+      {"--error-batches", OPTX_ERRBATCHES}};
   return t;
 }
 
@@ -282,6 +283,13 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
         break;
       }
       case OPTX_SCATGRID_FILE: mission.ScatterGridFile = o.text(); break;
+      case OPTX_ERRBATCHES: {
+        const long b = o.integer();
+        if (b < 2 || b > 64)
+          throw Runtime("--error-batches=B: the number of batches must be 2 .. 64 (got " + std::to_string(b) + ").");
+        mission.ErrorBatches = (unsigned)b;
+        break;
+      }
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }

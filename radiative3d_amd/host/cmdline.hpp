@@ -34,6 +34,9 @@ struct MissionParams {
   bool bScatterGrid = false;
   unsigned GridDims[3] = {0, 0, 0}, GridFrames = 0;
   double GridLo[3] = {0, 0, 0}, GridHi[3] = {0, 0, 0};
+  // --error-batches=B (2..64): run the histories as B id-partitioned batches and write each bin's standard error
+  // (seis_NNN_err.octv beside seis_NNN.octv; include/r3d.h r3d_run_batched); 0 = not asked for
+  unsigned ErrorBatches = 0;
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

@@ -34,6 +34,14 @@ void OutputSeismometerOctave(const Model& model, const r3d_result& res, int s, s
 void OutputPostSimSummary(const Model& model, const r3d_result& res, const std::string& outdir,
                           std::ostream& console, std::ostream& trace);
 
+// The standard errors of a batched run (include/r3d.h r3d_run_batched) for seismometer `s`, in the conventions of
+// OutputSeismometerOctave: matrices TraceXYZ_se, TracePS_se, CountPS_se (the rows of TraceXYZ, TracePS, CountPS)
+// and the scalar NumBatches.  OutputSeismometerErrors writes one seis_NNN_err.octv per seismometer into `outdir`.
+void OutputSeismometerErrorsOctave(const Model& model, const double* energy_se, const double* counts_se,
+                                   unsigned n_batches, int s, std::ostream& out);
+void OutputSeismometerErrors(const Model& model, const double* energy_se, const double* counts_se, unsigned n_batches,
+                             const std::string& outdir);
+
 // --reports keywords (reference main.cpp:223-258) -> R3D_RPT_* mask.  `csv` is the keyword
 // list as given ("ALL_ON", "GEN,SCT,REF", "SCATTERS", ...); empty = none.
 uint32_t ReportMaskFromKeywords(const std::string& csv);

@@ -5,8 +5,8 @@
 // files.  The N-phonon loop itself (Model::RunSimulation, model.cpp:602-633)
 // is one call into the engine's C-ABI.
 //
-// Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...` and `--scatter-grid=...` are accepted (the
-// reference seeds from the clock, is single-process and has no event histogram); the `--reports` stream is written
+// Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...` and `--error-batches=B`
+// are accepted (the reference seeds from the clock, is single-process, has no event histogram and no error bars); the `--reports` stream is written
 // after the run, grouped by history, where the reference writes its lines as they happen (the engine appends binary
 // records in HBM: include/r3d.h r3d_event); tables are built in HBM unless `--host-tables` is given.
 #include <cstdio>
@@ -145,7 +145,8 @@ struct StdoutToStderr {
 // frames) and each engine's frames written to the raw file.
 void run_simulation(const Model& model, uint64_t n, uint64_t seed, r3d_node* node, r3d_result& total,
                     std::vector<double>& energy, std::vector<uint64_t>& counts, uint32_t report_mask,
-                    std::vector<r3d_event>& events, uint64_t& events_dropped, const GridJob& grid) {
+                    std::vector<r3d_event>& events, uint64_t& events_dropped, const GridJob& grid,
+                    unsigned error_batches, std::vector<double>& energy_se, std::vector<double>& counts_se) {
   const r3d_model_desc& d = model.Desc();
   const int gpus = r3d_node_size(node);
   const size_t ne = (size_t)d.n_seismometers * d.params.n_bins * R3D_N_ENERGY;
@@ -164,7 +165,16 @@ void run_simulation(const Model& model, uint64_t n, uint64_t seed, r3d_node* nod
     if (report_mask && r3d_engine_set_event_log(e, report_mask, caps[g])) throw Runtime(r3d_last_error());
     if (grid.on && r3d_engine_set_volume(e, &grid.desc)) throw Runtime(r3d_last_error());
   }
-  if (r3d_node_run(node, n, 0, seed, &total)) throw Runtime(r3d_last_error());
+  if (error_batches) {
+    // --error-batches: the one shard's ids as B batches, every bin's standard error from their spread
+    // (include/r3d.h r3d_run_batched); the totals are those of the plain run up to summation order
+    energy_se.assign(ne, 0.0), counts_se.assign(nc, 0.0);
+    if (r3d_run_batched(engines[0], n, 0, seed, error_batches, &total, energy_se.data(), counts_se.data()))
+      throw Runtime(r3d_last_error());
+    std::cout << "|  Batches: " << error_batches << " (standard errors from batch means)\n";
+  } else if (r3d_node_run(node, n, 0, seed, &total)) {
+    throw Runtime(r3d_last_error());
+  }
   std::cout << "|  Shards: " << gpus << " (summed by " << r3d_node_reduction(node)
             << (*r3d_node_reduction_note(node) ? std::string(": ") + r3d_node_reduction_note(node) : std::string()) << ")\n";
   if (report_mask)
@@ -239,7 +249,9 @@ int main(int argc, char* argv[]) {
               << "additional: --seed=<n>  --gpus=<n>  --devices=<a,b,...>  --host-tables (a simulation run builds the\n"
               << "take-off set, source and scattering tables in HBM unless told otherwise)  --device-tables\n"
               << "--scatter-grid=NX,NY,NZ,FRAMES,X0,Y0,Z0,X1,Y1,Z1 [--scatter-grid-file=<name>]: SCT / REF events per wave\n"
-              << "type, frame and model-space cell, written as <name>.octv + <name>.u32 under --output-dir\n\n";
+              << "type, frame and model-space cell, written as <name>.octv + <name>.u32 under --output-dir\n"
+              << "--error-batches=B (2..64, one device): the histories run as B id-partitioned batches and every bin's\n"
+              << "standard error is written to seis_NNN_err.octv beside seis_NNN.octv\n\n";
     return 0;
   }
   // A simulation run makes its tables where it uses them (seconds of host work and GBs of upload
@@ -274,6 +286,11 @@ int main(int argc, char* argv[]) {
       std::vector<int> devices = mission.Devices;
       if (devices.empty())
         for (int g = 0; g < std::max(1, mission.Gpus); g++) devices.push_back(g);
+      if (mission.bRunSim && mission.ErrorBatches && devices.size() > 1)
+        throw Runtime("--error-batches runs on one device: --gpus / --devices name " + std::to_string(devices.size()) +
+                      " shards (standard errors over several devices are not built: DESIGN.md section 5).");
+      if (mission.bRunSim && mission.ErrorBatches && report_mask)
+        throw Runtime("--error-batches cannot be combined with --reports (the event log's launches run one at a time).");
       GridJob grid;
       if (mission.bRunSim && mission.bScatterGrid) {
         grid.on = true;
@@ -315,9 +332,10 @@ int main(int argc, char* argv[]) {
         std::vector<double> energy;
         std::vector<uint64_t> counts;
         std::vector<r3d_event> events;
+        std::vector<double> energy_se, counts_se;
         uint64_t dropped = 0;
         run_simulation(model, (uint64_t)std::max(0L, par.NumPhonons), mission.Seed, held.node, res, energy, counts,
-                       report_mask, events, dropped, grid);
+                       report_mask, events, dropped, grid, mission.ErrorBatches, energy_se, counts_se);
         if (report_mask) {   // the reference writes them as they happen: stdout, or --report-file
           if (mission.ReportFile.empty()) {
             OutputReports(events.data(), events.size(), std::cout);
@@ -334,6 +352,8 @@ int main(int argc, char* argv[]) {
         // seis_traces_asc.dat is opened in the CWD whatever --output-dir says (dataout.hpp:332)
         std::ofstream trace("seis_traces_asc.dat");
         OutputPostSimSummary(model, res, mission.OutputDir, std::cout, trace);
+        if (mission.ErrorBatches)
+          OutputSeismometerErrors(model, energy_se.data(), counts_se.data(), mission.ErrorBatches, mission.OutputDir);
       }
     }
   } catch (std::exception& e) {

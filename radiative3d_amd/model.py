@@ -206,8 +206,64 @@ class Model:
             raise RuntimeError("write_reports failed: " + self._lib.r3dh_last_error().decode())
         return txt.decode()
 
+    def write_errors(self, energy_se, counts_se, n_batches, outdir):
+        """Write seis_NNN_err.octv beside each seis_NNN.octv: the standard errors of a batched run
+        (Engine.run_batched) as matrices TraceXYZ_se, TracePS_se, CountPS_se and the scalar NumBatches."""
+        shape = (self.n_seismometers, self.n_bins)
+        e = np.ascontiguousarray(energy_se, dtype=np.float64).reshape(shape + (_ffi.R3D_N_ENERGY,))
+        c = np.ascontiguousarray(counts_se, dtype=np.float64).reshape(shape + (_ffi.R3D_N_COUNT,))
+        if self._lib.r3dh_write_errors(self._h, e.ctypes.data_as(_ffi._dp), c.ctypes.data_as(_ffi._dp), int(n_batches),
+                                       (outdir or "").encode()):
+            raise RuntimeError("write_errors failed: " + self._lib.r3dh_last_error().decode())
+
+    @property
+    def error_batches(self):
+        """What --error-batches=B in the model's arguments asked for (0: absent)."""
+        return int(self._lib.r3dh_error_batches(self._h))
+
     def new_result(self):
         return Result(self.n_seismometers, self.n_bins)
+
+
+def batch_moments(batch_energy, batch_counts, batch_scalars=None, energy=None, counts=None, scalars=None, stream=None):
+    """r3d_batch_moments on torch tensors of one device: batch_energy [B, ...] float64 and batch_counts [B, ...] of
+    a 64-bit integer type are B batch blocks (batch_scalars [B, k] likewise, optional).  Returns
+    (energy, counts, scalars, energy_se, counts_se): the blocks' sums ADDED into `energy` / `counts` / `scalars`
+    (made and zeroed here when None; scalars is None without batch_scalars) and the standard errors of those sums
+    (include/r3d.h has the estimator).  Asynchronous on `stream` (a raw hipStream_t; None: torch's current one)."""
+    import torch
+    lib = _ffi.hip_lib()
+    B = int(batch_energy.shape[0])
+    for t, what in ((batch_energy, torch.float64), (batch_counts, None), (batch_scalars, None)):
+        if t is None:
+            continue
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != 8 or t.shape[0] != B or t.device != batch_energy.device:
+            raise ValueError("batch blocks must be contiguous 8-byte tensors [B, ...] on one GPU")
+        if (what is not None and t.dtype != what) or (what is None and t.dtype.is_floating_point):
+            raise ValueError("batch_energy must be float64, batch_counts / batch_scalars 64-bit integers")
+    dev = batch_energy.device
+    if energy is None:
+        energy = torch.zeros(batch_energy.shape[1:], dtype=torch.float64, device=dev)
+    if counts is None:
+        counts = torch.zeros(batch_counts.shape[1:], dtype=batch_counts.dtype, device=dev)
+    if scalars is None and batch_scalars is not None:
+        scalars = torch.zeros(batch_scalars.shape[1:], dtype=batch_scalars.dtype, device=dev)
+    ne, nc = batch_energy[0].numel(), batch_counts[0].numel()
+    for t, n in ((energy, ne), (counts, nc)):
+        if t.device != dev or not t.is_contiguous() or t.numel() != n or t.element_size() != 8:
+            raise ValueError("totals must be contiguous 8-byte tensors of a block's size on the blocks' GPU")
+    energy_se = torch.empty(batch_energy.shape[1:], dtype=torch.float64, device=dev)
+    counts_se = torch.empty(batch_counts.shape[1:], dtype=torch.float64, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.r3d_batch_moments(dev.index or 0, B, batch_energy.data_ptr(), ne, batch_counts.data_ptr(), nc,
+                               batch_scalars.data_ptr() if batch_scalars is not None else None,
+                               batch_scalars[0].numel() if batch_scalars is not None else 0,
+                               energy.data_ptr(), counts.data_ptr(), scalars.data_ptr() if scalars is not None else None,
+                               energy_se.data_ptr(), counts_se.data_ptr(), stream)
+    if rc:
+        raise RuntimeError("r3d_batch_moments failed: " + lib.r3d_last_error().decode())
+    return energy, counts, scalars, energy_se, counts_se
 
 
 def run_model(model, n, first_id=0, seed=0x5EED, n_gpus=1, devices=None):
@@ -307,6 +363,7 @@ class Engine:
         four None the engine is made by plain r3d_engine_create."""
         self._lib = _ffi.hip_lib(reproducible, lib)
         self.model = model
+        self.device = int(device)
         self._volume_keepalive = None
         if residency is None and pool_slots is None and accumulator_bits is None and lds_reserve is None:
             self._e = self._lib.r3d_engine_create(model.desc_p, device)
@@ -359,6 +416,45 @@ class Engine:
             raise RuntimeError("r3d_run failed: " + self._lib.r3d_last_error().decode())
         res._from_c(c)
         return (res, finals) if trace else res
+
+    def run_batched(self, n, n_batches, first_id=0, seed=0x5EED, keep_batches=False):
+        """Histories [first_id, first_id+n) as n_batches id-partitioned batches (2..64), each a self-contained launch
+        into its own block, overlapped on the library's streams: (Result, energy_se, counts_se) -- the run's totals
+        as Engine.run gives them (to summation order) and the standard error of every energy and count entry from
+        the spread of the batches (include/r3d.h r3d_run_batched; numpy arrays shaped like Result.energy / .counts).
+        keep_batches: the run goes through r3d_run_device_batched on torch tensors and the blocks themselves follow
+        as numpy arrays, (..., batch_energy[B, seis, bin, 5], batch_counts[B, seis, bin, 2])."""
+        m = self.model
+        res = m.new_result()
+        shape = (m.n_seismometers, m.n_bins)
+        if not keep_batches:
+            ese = np.zeros(shape + (_ffi.R3D_N_ENERGY,))
+            cse = np.zeros(shape + (_ffi.R3D_N_COUNT,))
+            c = res._as_c()
+            if self._lib.r3d_run_batched(self._e, n, first_id, seed, n_batches, C.byref(c), ese.ctypes.data_as(_ffi._dp),
+                                         cse.ctypes.data_as(_ffi._dp)):
+                raise RuntimeError("r3d_run_batched failed: " + self._lib.r3d_last_error().decode())
+            res._from_c(c)
+            return res, ese, cse
+        import torch
+        dev = torch.device("cuda", self.device)
+        B = max(int(n_batches), 0)
+        energy = torch.zeros(shape + (_ffi.R3D_N_ENERGY,), dtype=torch.float64, device=dev)
+        counts = torch.zeros(shape + (_ffi.R3D_N_COUNT,), dtype=torch.int64, device=dev)
+        scalars = torch.zeros(_ffi.R3D_N_SCALARS, dtype=torch.int64, device=dev)
+        ese, cse = torch.zeros_like(energy), torch.zeros(counts.shape, dtype=torch.float64, device=dev)
+        be = torch.zeros((B,) + tuple(energy.shape), dtype=torch.float64, device=dev)
+        bc = torch.zeros((B,) + tuple(counts.shape), dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        if self._lib.r3d_run_device_batched(self._e, n, first_id, seed, n_batches, energy.data_ptr(), counts.data_ptr(),
+                                            scalars.data_ptr(), ese.data_ptr(), cse.data_ptr(), be.data_ptr(),
+                                            bc.data_ptr(), stream.cuda_stream):
+            raise RuntimeError("r3d_run_device_batched failed: " + self._lib.r3d_last_error().decode())
+        stream.synchronize()
+        res.energy[:] = energy.cpu().numpy()
+        res.counts[:] = counts.cpu().numpy().view(np.uint64)
+        res.set_scalars(scalars.cpu().numpy().view(np.uint64))
+        return res, ese.cpu().numpy(), cse.cpu().numpy(), be.cpu().numpy(), bc.cpu().numpy().view(np.uint64)
 
     def run_device(self, n, first_id, seed, d_energy, d_counts, d_scalars, stream=None, carry=None):
         """Asynchronous, device-resident accumulate (pointers are raw device

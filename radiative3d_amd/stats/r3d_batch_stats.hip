@@ -1,0 +1,314 @@
+// r3d_batch_stats.hip -- per-bin standard errors from id-partitioned batches (include/r3d.h r3d_batch_moments,
+// r3d_run_device_batched, r3d_run_batched).
+//
+// A run of ids [first_id, first_id + n) is cut into B contiguous batches; each is one self-contained
+// r3d_run_device launch into its own zeroed block.  Histories are keyed by id, so the blocks are independent
+// samples of one distribution and the spread of a bin over them gives the standard error of the bin's total
+// (batch means; the per-entry arithmetic is r3d_batch_moments.h).  The moments are taken where the blocks live:
+// one streaming kernel over [B][len] in HBM instead of B copies to the host.
+//
+// This file stands ON TOP of the engine: it calls only what include/r3d.h declares and owns the streams and
+// events it overlaps the batches with; nothing in csrc/ knows about it.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/r3d.h"
+#include "r3d_batch_moments.h"
+
+namespace r3d {
+extern thread_local std::string g_error;   // (csrc/r3d_engine.hip: what r3d_last_error returns)
+
+namespace {
+
+constexpr int kMomentsBlock = 256;
+constexpr uint32_t kMaxBatches = 64;   // launches of one engine in flight (include/r3d.h r3d_run_device)
+constexpr int kStreams = 4;            // hardware queues a process gets by default
+
+// One work-item per entry, grid-stride.  The blocks are batch-major, so for every j the lanes of a wave read 64
+// consecutive 8-byte entries of block j: coalesced 512-byte requests; the second pass over the B values finds them
+// in L2 / Infinity Cache.  Fixed order j = 0 .. B-1 and no atomics: the output is the same bits every run.
+// total_out += the batches' sum (the caller's result accumulates, as r3d_run's does); se_out = (may be NULL).
+__global__ __launch_bounds__(kMomentsBlock) void batch_moments_f64_kernel(const double* __restrict__ x, uint64_t len,
+                                                                          uint32_t n_batches, double* __restrict__ total_out,
+                                                                          double* __restrict__ se_out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += stride) {
+    double total, se;
+    batch_moments_f64(x + i, len, n_batches, &total, &se);
+    total_out[i] += total;
+    if (se_out) se_out[i] = se;
+  }
+}
+
+__global__ __launch_bounds__(kMomentsBlock) void batch_moments_u64_kernel(const uint64_t* __restrict__ x, uint64_t len,
+                                                                          uint32_t n_batches, uint64_t* __restrict__ total_out,
+                                                                          double* __restrict__ se_out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += stride) {
+    uint64_t total;
+    double se;
+    batch_moments_u64(x + i, len, n_batches, &total, &se);
+    total_out[i] += total;
+    if (se_out) se_out[i] = se;
+  }
+}
+
+unsigned moments_grid(uint64_t len) {
+  // (enough workgroups to keep every CU's memory pipeline busy -- 256 CUs x 8 x 256 work-items --, grid-stride beyond)
+  const uint64_t blocks = (len + kMomentsBlock - 1) / kMomentsBlock;
+  return (unsigned)(blocks < 2048 ? blocks : 2048);
+}
+
+// The caller's current device kept across an entry point (as the engine's own entry points do).
+struct OnDevice {
+  int prev = -1;
+  hipError_t status;
+  explicit OnDevice(int device) {
+    status = hipGetDevice(&prev);
+    if (status != hipSuccess) {
+      prev = -1;
+      return;
+    }
+    if (prev == device) prev = -1;
+    else status = hipSetDevice(device);
+  }
+  ~OnDevice() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+  OnDevice(const OnDevice&) = delete;
+  OnDevice& operator=(const OnDevice&) = delete;
+};
+
+int fail(const char* where, hipError_t err) {
+  g_error = std::string(where) + ": " + hipGetErrorString(err);
+  return 1;
+}
+
+// The streams the batches overlap on and the events that tie them to the caller's stream: made once per device,
+// kept for the life of the process (an enqueue holds the lock: the events are re-recorded by every call).
+struct Lanes {
+  hipStream_t stream[kStreams] = {};
+  hipEvent_t begin = nullptr, done[kStreams] = {};
+  bool ready = false;
+};
+std::mutex g_lanes_lock;
+std::vector<Lanes> g_lanes;
+
+hipError_t lanes_for(int device, Lanes** out) {
+  if (device < 0) return hipErrorInvalidDevice;
+  if (g_lanes.size() <= (size_t)device) g_lanes.resize((size_t)device + 1);
+  Lanes& l = g_lanes[(size_t)device];
+  if (!l.ready) {
+    Lanes made;
+    hipError_t err = hipEventCreateWithFlags(&made.begin, hipEventDisableTiming);
+    for (int k = 0; k < kStreams && err == hipSuccess; k++) {
+      err = hipStreamCreateWithFlags(&made.stream[k], hipStreamNonBlocking);
+      if (err == hipSuccess) err = hipEventCreateWithFlags(&made.done[k], hipEventDisableTiming);
+    }
+    if (err != hipSuccess) {
+      if (made.begin) (void)hipEventDestroy(made.begin);
+      for (int k = 0; k < kStreams; k++) {
+        if (made.stream[k]) (void)hipStreamDestroy(made.stream[k]);
+        if (made.done[k]) (void)hipEventDestroy(made.done[k]);
+      }
+      return err;
+    }
+    made.ready = true;
+    l = made;
+  }
+  *out = &l;
+  return hipSuccess;
+}
+
+// The device a pointer of the caller's lives on (-1: not device memory).
+int device_of(const void* p) {
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  if (attr.type != hipMemoryTypeDevice) return -1;
+  return attr.device;
+}
+
+int enqueue_moments(uint32_t n_batches, const double* d_batch_energy, uint64_t n_energy, const uint64_t* d_batch_counts,
+                    uint64_t n_counts, const uint64_t* d_batch_scalars, uint64_t n_scalars, double* d_energy,
+                    uint64_t* d_counts, uint64_t* d_scalars, double* d_energy_se, double* d_counts_se, hipStream_t s) {
+  if (n_energy)
+    batch_moments_f64_kernel<<<dim3(moments_grid(n_energy)), dim3(kMomentsBlock), 0, s>>>(d_batch_energy, n_energy, n_batches,
+                                                                                       d_energy, d_energy_se);
+  if (n_counts)
+    batch_moments_u64_kernel<<<dim3(moments_grid(n_counts)), dim3(kMomentsBlock), 0, s>>>(d_batch_counts, n_counts, n_batches,
+                                                                                       d_counts, d_counts_se);
+  if (d_batch_scalars && n_scalars)
+    batch_moments_u64_kernel<<<dim3(moments_grid(n_scalars)), dim3(kMomentsBlock), 0, s>>>(d_batch_scalars, n_scalars, n_batches,
+                                                                                        d_scalars, nullptr);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : fail("r3d_batch_moments", err);
+}
+
+// What a batched run cannot be combined with, asked of the engine through its public calls.
+int refuse_engine_state(r3d_engine* e, const char* who) {
+  if (r3d_engine_carry_pending(e))
+    return g_error = std::string(who) + ": histories carried over by r3d_run_device_carry await their flush; a batch must be a "
+                     "self-contained launch", 1;
+  if (r3d_event_log_read(e, nullptr, 0, 0) != ~uint64_t(0))
+    return g_error = std::string(who) + ": an event log is attached (its launches run the diagnostic kernel, one at a time); "
+                     "detach it first", 1;
+  if (r3d_production_finals_read(e, nullptr, 0, 0) == 0)
+    return g_error = std::string(who) + ": a production-finals buffer is attached; detach it first", 1;
+  return 0;
+}
+
+int check_batches(const char* who, uint64_t n, uint32_t n_batches) {
+  if (n_batches < 2)
+    return g_error = std::string(who) + ": at least 2 batches are needed for a variance (got " + std::to_string(n_batches) + ")", 1;
+  if (n_batches > kMaxBatches)
+    return g_error = std::string(who) + ": at most 64 batches (the engine's launches in flight), got " + std::to_string(n_batches), 1;
+  if (n < n_batches)
+    return g_error = std::string(who) + ": fewer histories (" + std::to_string(n) + ") than batches (" + std::to_string(n_batches) + ")", 1;
+  return 0;
+}
+
+}  // namespace
+}  // namespace r3d
+
+using namespace r3d;
+
+extern "C" {
+
+int r3d_batch_moments(int device, uint32_t n_batches, const double* d_batch_energy, uint64_t n_energy,
+                      const uint64_t* d_batch_counts, uint64_t n_counts, const uint64_t* d_batch_scalars, uint64_t n_scalars,
+                      double* d_energy, uint64_t* d_counts, uint64_t* d_scalars, double* d_energy_se, double* d_counts_se,
+                      void* stream) {
+  if (n_batches < 2 || n_batches > kMaxBatches)
+    return g_error = "r3d_batch_moments: the number of batches must be 2 .. 64, got " + std::to_string(n_batches), 1;
+  if ((n_energy && (!d_batch_energy || !d_energy)) || (n_counts && (!d_batch_counts || !d_counts)) ||
+      (d_batch_scalars && n_scalars && !d_scalars))
+    return g_error = "r3d_batch_moments: null argument", 1;
+  OnDevice on(device);
+  if (on.status != hipSuccess) return g_error = "r3d_batch_moments: no HIP device (or a bad device index)", 1;
+  return enqueue_moments(n_batches, d_batch_energy, n_energy, d_batch_counts, n_counts, d_batch_scalars, n_scalars, d_energy,
+                         d_counts, d_scalars, d_energy_se, d_counts_se, reinterpret_cast<hipStream_t>(stream));
+}
+
+int r3d_run_device_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches, double* d_energy,
+                           uint64_t* d_counts, uint64_t* d_scalars, double* d_energy_se, double* d_counts_se,
+                           double* d_batch_energy, uint64_t* d_batch_counts, void* stream) {
+  const char* const who = "r3d_run_device_batched";
+  if (!e) return g_error = "null engine", 1;
+  if (!d_energy || !d_counts || !d_scalars) return g_error = "null result buffer", 1;
+  if (check_batches(who, n, n_batches)) return 1;
+  if (refuse_engine_state(e, who)) return 1;
+  const int device = device_of(d_energy);
+  if (device < 0) return g_error = std::string(who) + ": d_energy is not device memory", 1;
+  OnDevice on(device);
+  if (on.status != hipSuccess) return fail(who, on.status);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const uint64_t ne = r3d_energy_len(e), nc = r3d_counts_len(e), ns = R3D_N_SCALARS, B = n_batches;
+
+  std::lock_guard<std::mutex> lock(g_lanes_lock);
+  Lanes* lanes = nullptr;
+  if (hipError_t err = lanes_for(device, &lanes); err != hipSuccess) return fail(who, err);
+
+  // the batches' blocks: the caller's, or scratch that lives in stream order from here to behind the moments kernel
+  // (the scalars' blocks are always scratch); every block starts from zero
+  const uint64_t own_e = d_batch_energy ? 0 : B * ne, own_c = d_batch_counts ? 0 : B * nc;
+  void* scratch = nullptr;
+  if (hipError_t err = hipMallocAsync(&scratch, (own_e + own_c + B * ns) * 8, s); err != hipSuccess) return fail(who, err);
+  uint64_t* const bs = reinterpret_cast<uint64_t*>(scratch);
+  double* const be = d_batch_energy ? d_batch_energy : reinterpret_cast<double*>(bs + B * ns);
+  uint64_t* const bc = d_batch_counts ? d_batch_counts : bs + B * ns + own_e;
+  hipError_t err = hipMemsetAsync(scratch, 0, (own_e + own_c + B * ns) * 8, s);
+  if (err == hipSuccess && d_batch_energy && ne) err = hipMemsetAsync(be, 0, B * ne * 8, s);
+  if (err == hipSuccess && d_batch_counts && nc) err = hipMemsetAsync(bc, 0, B * nc * 8, s);
+  if (err == hipSuccess) err = hipEventRecord(lanes->begin, s);
+  for (int k = 0; k < kStreams && err == hipSuccess; k++) err = hipStreamWaitEvent(lanes->stream[k], lanes->begin, 0);
+  int rc = err == hipSuccess ? 0 : fail(who, err);
+  // batch j: ids [first_id + floor(j n / B), first_id + floor((j + 1) n / B)), round-robin over the streams so that a
+  // batch's drain phase overlaps the batches behind it
+  for (uint64_t j = 0; j < B && rc == 0; j++) {
+    const uint64_t lo = j * (n / B) + j * (n % B) / B, hi = (j + 1) * (n / B) + (j + 1) * (n % B) / B;
+    rc = r3d_run_device(e, hi - lo, first_id + lo, seed, be + j * ne, bc + j * nc, bs + j * ns, nullptr,
+                        lanes->stream[j % kStreams]);   // (its message stands)
+  }
+  // join: whatever was enqueued is waited for by the caller's stream, also when a launch was refused
+  for (int k = 0; k < kStreams; k++) {
+    hipError_t j = hipEventRecord(lanes->done[k], lanes->stream[k]);
+    if (j == hipSuccess) j = hipStreamWaitEvent(s, lanes->done[k], 0);
+    if (j != hipSuccess && rc == 0) rc = fail(who, j);
+  }
+  if (rc == 0)
+    rc = enqueue_moments(n_batches, be, ne, bc, nc, bs, ns, d_energy, d_counts, d_scalars, d_energy_se, d_counts_se, s);
+  if (hipError_t f = hipFreeAsync(scratch, s); f != hipSuccess && rc == 0) rc = fail(who, f);
+  return rc;
+}
+
+int r3d_run_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches, r3d_result* out,
+                    double* energy_se, double* counts_se) {
+  const char* const who = "r3d_run_batched";
+  if (!e) return g_error = "null engine", 1;
+  if (!out || !out->energy || !out->counts) return g_error = "null result", 1;
+  if (check_batches(who, n, n_batches)) return 1;
+  if (refuse_engine_state(e, who)) return 1;
+  // The engine's device, learned from an address it owns: the only one the interface hands out is its event grid's,
+  // so an engine without a grid gets one of a single cell for the length of the question.
+  int device = -1;
+  if (r3d_volume_len(e)) {
+    device = device_of(r3d_volume_device_ptr(e));
+  } else {
+    r3d_volume_desc one{};
+    one.cell_size[0] = one.cell_size[1] = one.cell_size[2] = 1.0, one.dims[0] = one.dims[1] = one.dims[2] = 1;
+    one.n_frames = 1, one.frame_dt = 1.0;
+    if (r3d_engine_set_volume(e, &one)) return 1;
+    device = device_of(r3d_volume_device_ptr(e));
+    if (r3d_engine_set_volume(e, nullptr)) return 1;
+  }
+  if (device < 0) return g_error = std::string(who) + ": the engine's device could not be determined", 1;
+  OnDevice on(device);
+  if (on.status != hipSuccess) return fail(who, on.status);
+  const size_t ne = r3d_energy_len(e), nc = r3d_counts_len(e), ns = R3D_N_SCALARS;
+  // one block: totals (energy, counts, scalars), then the two se arrays
+  void* block = nullptr;
+  const size_t words = 2 * ne + 2 * nc + ns;
+  if (hipError_t err = hipMalloc(&block, words * 8); err != hipSuccess) return fail(who, err);
+  double* const d_e = reinterpret_cast<double*>(block);
+  uint64_t* const d_c = reinterpret_cast<uint64_t*>(d_e + ne);
+  uint64_t* const d_s = d_c + nc;
+  double* const d_ese = reinterpret_cast<double*>(d_s + ns);
+  double* const d_cse = d_ese + ne;
+  std::vector<uint64_t> host(words);
+  hipStream_t s = nullptr;
+  hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  if (err == hipSuccess) err = hipMemsetAsync(block, 0, words * 8, s);
+  int rc = err == hipSuccess ? 0 : fail(who, err);
+  if (rc == 0) rc = r3d_run_device_batched(e, n, first_id, seed, n_batches, d_e, d_c, d_s, d_ese, d_cse, nullptr, nullptr, s);
+  if (s) {   // (also after a refusal: what was enqueued reads the block)
+    err = hipStreamSynchronize(s);
+    if (err == hipSuccess && rc == 0) err = hipMemcpy(host.data(), block, words * 8, hipMemcpyDeviceToHost);
+    if (err != hipSuccess && rc == 0) rc = fail(who, err);
+    (void)hipStreamDestroy(s);
+  }
+  (void)hipFree(block);
+  if (rc) return rc;
+  const double* const he = reinterpret_cast<const double*>(host.data());
+  const uint64_t* const hc = host.data() + ne;
+  const uint64_t* const hs = hc + nc;
+  const double* const hese = reinterpret_cast<const double*>(hs + ns);
+  for (size_t i = 0; i < ne; i++) out->energy[i] += he[i];
+  for (size_t i = 0; i < nc; i++) out->counts[i] += hc[i];
+  out->n_lost += hs[0], out->n_timeout += hs[1], out->n_invalid += hs[2];
+  for (int r = 0; r < R3D_INV_NUM; r++) out->invalid_reasons[r] += hs[3 + r];
+  for (int k = 0; k < R3D_EV_NUM; k++) out->events[k] += hs[3 + R3D_INV_NUM + k];
+  if (energy_se)
+    for (size_t i = 0; i < ne; i++) energy_se[i] = hese[i];
+  if (counts_se)
+    for (size_t i = 0; i < nc; i++) counts_se[i] = hese[ne + i];
+  return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,210 @@
+"""Per-bin standard errors from id-partitioned batches, the parts that need no GPU: the per-entry arithmetic the
+moments kernel runs (radiative3d_amd/stats/r3d_batch_moments.h, compiled here by the host compiler) against an
+exact reference, the --error-batches option, the seis_NNN_err.octv writer and the C-ABI's new names."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from batch_cases import BATCHES, check_se, count_families, families, sum_in_order
+from radiative3d_amd import Model, _ffi
+from tests.configs import halfspace
+
+REPO = _ffi.REPO
+
+WRAPPER = r'''
+#include "r3d_batch_moments.h"
+extern "C" void moments_f64(const double* x, uint64_t len, uint32_t b, double* total, double* se) {
+  for (uint64_t i = 0; i < len; i++) r3d::batch_moments_f64(x + i, len, b, total + i, se + i);
+}
+extern "C" void moments_u64(const uint64_t* x, uint64_t len, uint32_t b, uint64_t* total, double* se) {
+  for (uint64_t i = 0; i < len; i++) r3d::batch_moments_u64(x + i, len, b, total + i, se + i);
+}
+'''
+
+
+@pytest.fixture(scope="module")
+def host_moments(tmp_path_factory):
+    d = tmp_path_factory.mktemp("moments")
+    src, so = d / "wrap.cpp", d / "libmoments.so"
+    src.write_text(WRAPPER)
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Werror", "-I",
+                           os.path.join(REPO, "radiative3d_amd", "stats"), "-o", str(so), str(src)])
+    L = C.CDLL(str(so))
+    L.moments_f64.argtypes = L.moments_u64.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.moments_f64.restype = L.moments_u64.restype = None
+    return L
+
+
+@pytest.mark.parametrize("B", BATCHES)
+def test_energy_moments_meet_the_derived_bound(host_moments, B):
+    rng = np.random.default_rng(1000 + B)
+    for name, x in families(B, 160, rng).items():
+        x = np.ascontiguousarray(x)
+        total, se = np.empty(x.shape[1]), np.empty(x.shape[1])
+        host_moments.moments_f64(x.ctypes.data, x.shape[1], B, total.ctypes.data, se.ctypes.data)
+        assert (total == sum_in_order(x)).all(), name          # the fp64 sum in order j, to the bit
+        worst = check_se(x, se, f"{name}, B = {B}")
+        print(f"B = {B:2d} {name:12s} worst error / bound = {worst:.3f}")
+        if name in ("all_equal", "all_zero"):
+            assert (se == 0.0).all(), name
+
+
+@pytest.mark.parametrize("B", BATCHES)
+def test_count_moments_are_exact_in_the_total_and_meet_the_bound(host_moments, B):
+    rng = np.random.default_rng(2000 + B)
+    for name, x in count_families(B, 160, rng).items():
+        x = np.ascontiguousarray(x)
+        total, se = np.empty(x.shape[1], dtype=np.uint64), np.empty(x.shape[1])
+        host_moments.moments_u64(x.ctypes.data, x.shape[1], B, total.ctypes.data, se.ctypes.data)
+        assert (total == x.sum(axis=0, dtype=np.uint64)).all(), name
+        check_se(x, se, f"counts {name}, B = {B}")
+        if name in ("all_equal", "all_zero"):
+            assert (se == 0.0).all(), name
+
+
+def test_a_single_entry_and_the_textbook_value(host_moments):
+    """len == 1, and a value known in closed form: batches 1, 2, 3, 4 -> T = 10, se = sqrt(4/3 * 5) = sqrt(20/3)."""
+    x = np.array([[1.0], [2.0], [3.0], [4.0]])
+    total, se = np.empty(1), np.empty(1)
+    host_moments.moments_f64(x.ctypes.data, 1, 4, total.ctypes.data, se.ctypes.data)
+    assert total[0] == 10.0 and se[0] == pytest.approx((20.0 / 3.0) ** 0.5, rel=1e-15)
+
+
+def test_the_one_pass_form_would_miss_the_bound():
+    """Why the header insists on two passes: sum x^2 - (sum x)^2 / B on 1e9 + N(0,1) batches is off by orders of
+    magnitude more than the bound allows (so the bound does tell the two apart)."""
+    from batch_cases import bound, exact_se
+    rng = np.random.default_rng(7)
+    x = 1e9 + rng.standard_normal((16, 64))
+    naive = np.sqrt(np.maximum((x * x).sum(0) - x.sum(0) ** 2 / 16, 0.0) * 16 / 15)
+    over = max(abs(naive[i] - exact_se(x[:, i])) / bound(16, x[:, i], exact_se(x[:, i])) for i in range(64))
+    assert over > 1e3, over
+
+
+# ---- --error-batches ------------------------------------------------------------------------------------------------
+def test_error_batches_option_parses_and_is_off_by_default():
+    assert Model(halfspace(3)).error_batches == 0
+    assert Model(halfspace(3) + ["--error-batches=16"]).error_batches == 16
+    assert Model(halfspace(3) + ["--error-batches=2"]).error_batches == 2
+    assert Model(halfspace(3) + ["--error-batches=64"]).error_batches == 64
+
+
+@pytest.mark.parametrize("value,message", [("0", "2 .. 64"), ("1", "2 .. 64"), ("65", "2 .. 64"), ("-3", "2 .. 64"),
+                                           ("many", "cannot interpret 'many'"), ("", "Required value not provided")])
+def test_error_batches_option_refuses_bad_values(value, message):
+    with pytest.raises(RuntimeError, match=re.escape(message)):
+        Model(halfspace(3) + ["--error-batches=" + value])
+
+
+def main_exe():
+    exe = os.path.join(REPO, "main")
+    assert os.path.exists(exe), "./main was not built"
+    return exe
+
+
+def test_cli_refuses_bad_error_batches_and_more_than_one_shard(tmp_path):
+    r = subprocess.run([main_exe()] + halfspace(3) + ["--error-batches=65"], cwd=tmp_path, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 1 and "Error processing command-line options" in r.stdout and "2 .. 64" in r.stdout
+    for shards in (["--gpus=2"], ["--devices=0,0"]):
+        r = subprocess.run([main_exe()] + halfspace(3) + ["--num-phonons=1K", "--error-batches=4", f"--output-dir={tmp_path}"]
+                           + shards, cwd=tmp_path, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 1 and "--error-batches runs on one device" in r.stdout, r.stdout[-2000:]
+    assert not list(tmp_path.glob("seis_*_err.octv"))
+    assert "--error-batches" in subprocess.run([main_exe(), "--help"], capture_output=True, text=True, timeout=60).stdout
+
+
+# ---- seis_NNN_err.octv ----------------------------------------------------------------------------------------------
+def parse_octave_matrices(text):
+    """name -> 2-D array (matrices) or float (scalars) of an Octave text file as dataout.cpp writes them."""
+    out, lines, i = {}, text.splitlines(), 0
+    while i < len(lines):
+        m = re.match(r"# name: (\w+)", lines[i])
+        if not m:
+            i += 1
+            continue
+        name, kind = m.group(1), lines[i + 1].split(":")[1].strip()
+        if kind == "scalar":
+            out[name] = float(lines[i + 2])
+            i += 3
+        elif kind == "matrix":
+            rows, cols = int(lines[i + 2].split(":")[1]), int(lines[i + 3].split(":")[1])
+            out[name] = np.array([[float(v) for v in lines[i + 4 + r].split()] for r in range(rows)]).reshape(rows, cols)
+            i += 4 + rows
+        else:
+            i += 2
+    return out
+
+
+def test_write_errors_writes_err_files_beside_untouched_seis_files(tmp_path):
+    m = Model(halfspace(3))
+    rng = np.random.default_rng(5)
+    res = m.new_result()
+    res.energy[:] = rng.lognormal(0, 2, res.energy.shape)
+    res.counts[:] = rng.poisson(40, res.counts.shape)
+    ese = rng.lognormal(0, 2, res.energy.shape)
+    cse = np.sqrt(rng.poisson(40, res.counts.shape).astype(np.float64))
+    plain, both = tmp_path / "plain", tmp_path / "both"
+    plain.mkdir(), both.mkdir()
+    m.write_outputs(res, str(plain))
+    m.write_outputs(res, str(both))
+    before = {p.name: p.read_bytes() for p in both.glob("seis_*.octv")}
+    assert len(before) == m.n_seismometers
+    m.write_errors(ese, cse, 16, str(both))
+    for s in range(m.n_seismometers):
+        name = f"seis_{s:03d}.octv"
+        assert (both / name).read_bytes() == before[name] == (plain / name).read_bytes()
+        got = parse_octave_matrices((both / f"seis_{s:03d}_err.octv").read_text())
+        assert got["NumBatches"] == 16 and got["NumBins"] == m.n_bins
+        # (the files print 6 significant digits, like seis_NNN.octv)
+        assert np.allclose(got["TraceXYZ_se"], ese[s][:, 0:3], rtol=1e-5, atol=0)
+        assert np.allclose(got["TracePS_se"], ese[s][:, 3:5], rtol=1e-5, atol=0)
+        assert np.allclose(got["CountPS_se"], cse[s], rtol=1e-5, atol=0)
+    assert not list(plain.glob("*_err.octv"))
+    with pytest.raises(RuntimeError, match="at least 2 batches"):
+        m.write_errors(ese, cse, 1, str(both))
+
+
+# ---- the C-ABI ------------------------------------------------------------------------------------------------------
+def test_new_entry_points_are_declared_exported_and_bound():
+    header = open(os.path.join(REPO, "include", "r3d.h")).read()
+    L, H = _ffi.hip_lib(), _ffi.host_lib()
+    for name in ("r3d_batch_moments", "r3d_run_device_batched", "r3d_run_batched"):
+        assert re.search(r"\bint\s+" + name + r"\s*\(", header), name
+        f = getattr(L, name)
+        assert f.argtypes and f.restype is C.c_int, name
+        assert getattr(_ffi.hip_lib(reproducible=True), name)
+    assert len(L.r3d_batch_moments.argtypes) == 14 and len(L.r3d_run_device_batched.argtypes) == 13
+    assert len(L.r3d_run_batched.argtypes) == 8
+    host_header = open(os.path.join(REPO, "include", "r3d_host.h")).read()
+    for name in ("r3dh_write_errors", "r3dh_error_batches"):
+        assert name in host_header and getattr(H, name).argtypes
+    import radiative3d_amd
+    assert callable(radiative3d_amd.batch_moments) and callable(radiative3d_amd.Engine.run_batched)
+
+
+def test_the_new_hip_lives_outside_the_hashed_kernel_sources():
+    """The moments kernel is a file of its own under radiative3d_amd/stats/: the traversal kernels' sources, whose
+    hash the committed counter files carry, do not know about it."""
+    csrc = os.path.join(REPO, "radiative3d_amd", "csrc")
+    for f in os.listdir(csrc):
+        assert "batch_moments" not in open(os.path.join(csrc, f), errors="ignore").read(), f
+    text = open(os.path.join(REPO, "radiative3d_amd", "stats", "r3d_batch_stats.hip")).read()
+    assert "__global__" in text and "atomic" not in re.sub(r"//[^\n]*", "", text)
+
+
+def test_batch_calls_fail_loudly_without_a_gpu():
+    import torch
+    if torch.cuda.is_available():
+        return   # (tests/test_batch_stats_gpu.py runs them)
+    L = _ffi.hip_lib()
+    buf = (C.c_double * 8)()
+    p = C.addressof(buf)
+    assert L.r3d_batch_moments(0, 2, p, 1, p, 1, None, 0, p, p, None, p, p, None) != 0
+    assert "no HIP device" in L.r3d_last_error().decode()
+    assert L.r3d_batch_moments(0, 1, p, 1, p, 1, None, 0, p, p, None, p, p, None) != 0
+    assert "2 .. 64" in L.r3d_last_error().decode()
