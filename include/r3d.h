@@ -467,6 +467,63 @@ int r3d_volume_scatter_add(int device, uint32_t* d_counters, uint64_t len, const
  * are undefined.                                                                                         */
 int r3d_volume_reduce_by_frame(r3d_engine* const* engines, int n, uint32_t* frames, uint64_t* saturated);
 
+/* ---- the grid as the two video views ---------------------------------------------
+ * What the reference makes of a video run's events is two movies: per frame floor(t / dt) the events of each
+ * wave type seen from ABOVE, at (x, y) (vis/scattervid/scattervid_above.m:111, 179-197), and in ELEVATION, at
+ * (rho, z), rho the horizontal distance from the source's epicentre (scattervid_p2p.m:135-148, 220-243; its
+ * header means it to filter by azimuth, :20-22, `azifilt` :83).  Both are per-frame 2-D histograms of the grid.
+ *
+ * THE VIEWS.  Grid as in r3d_volume_desc: origin o, cell size c, dims nx, ny, nz.  A call projects the grid frames
+ * [frame_begin, frame_end), frame_group >= 1 of them per output frame: F = (f - frame_begin) / frame_group,
+ * n_out = ceil((frame_end - frame_begin) / frame_group); the last group may be short.
+ *     above[t][F][iy][ix] += sum over f in F, over iz, of count[t][f][iz][iy][ix]
+ *     elev[t][F][iz][ir]  += sum over f in F, over the columns (iy, ix) with range_bin[iy][ix] == ir, of count[t][f][iz][iy][ix]
+ *     outside[t]          += the same sum over the columns with range_bin >= n_range (not in the elevation view)
+ * uint64, ADDED into, like every result buffer of this ABI.  64-bit sums do not saturate; a grid cell pinned at
+ * 2^32 - 1 counts as that value.  All arithmetic on the device is integer: the result has the same bits on every
+ * run, whatever the launch geometry.  The views are in model coordinates, as the grid is.
+ *
+ * THE COLUMN MAP range_bin[ny][nx] is made on the HOST, once (r3d_volume_range_bins), and uploaded by the caller;
+ * the device only reads it.  In fp64, by exactly these operations in this order, no fused multiply-add:
+ *     dx = (o_x + (ix + 0.5) * c_x) - s_x        dy = (o_y + (iy + 0.5) * c_y) - s_y
+ *     rho = sqrt(dx*dx + dy*dy)                   ir = floor(rho / dr)
+ *     in view  <=>  ir < n_range  and  (half_width >= 180  or  |wrap180(atan2(dy, dx) in degrees - azimuth)| <= half_width)
+ *     range_bin = in view ? ir : 0xFFFFFFFF
+ * with wrap180(d) = d - 360 * floor((d + 180) / 360).  An event is placed at its cell's CENTRE: against the
+ * reference's exact rho that moves it by at most half the cell's horizontal diagonal, 0.5 * sqrt(c_x^2 + c_y^2).
+ *
+ * r3d_volume_project: device level, like r3d_volume_compact -- d_counters is any grid of the shape *v on `device`
+ * (the engine's own through r3d_volume_device_ptr, or the caller's; the caller passes the description it attached),
+ * asynchronous on `stream`, every counter loaded once whether one view is asked for or both.  d_outside is filled
+ * with the elevation view only.  REFUSED (non-zero, r3d_last_error, nothing enqueued): a null grid, description or
+ * views, a size mismatch, frame_begin > frame_end, frame_end > n_frames, frame_group == 0, both views NULL, an
+ * elevation view without a map or with n_range == 0, d_outside without an elevation view.  An empty frame range is
+ * success and touches nothing.  r3d_volume_range_bins (host only, no device needed) refuses dr <= 0.            */
+typedef struct r3d_volume_views {
+  uint32_t size;                    /* sizeof(r3d_volume_views): a mismatch is refused         */
+  uint32_t frame_begin, frame_end, frame_group;
+  uint32_t n_range;                 /* 0: no elevation view                                    */
+  uint32_t pad_;
+  const uint32_t* d_range_bin;      /* [ny][nx], device                                        */
+  uint64_t* d_above;                /* [2][n_out][ny][nx], device, or NULL                     */
+  uint64_t* d_elev;                 /* [2][n_out][nz][n_range], device, or NULL                */
+  uint64_t* d_outside;              /* [2], device, or NULL                                    */
+} r3d_volume_views;
+int r3d_volume_project(int device, const uint32_t* d_counters, const r3d_volume_desc* v,
+                       const r3d_volume_views* views, void* stream);
+int r3d_volume_range_bins(const r3d_volume_desc* v, const double epicentre[2], double dr, uint32_t n_range,
+                          double azimuth_deg, double half_width_deg, uint32_t* out /* host, ny * nx */);
+/* The projection for a host that holds no device memory of its own (./main --scatter-views): frames [frame_begin,
+ * frame_end) of the grid d_counters on `device` are projected into scratch views there, read back, and ADDED into
+ * the host arrays above [2][n_out_total][ny][nx] / elev [2][n_out_total][nz][n_range] at output frame out_frame0
+ * onward, and into outside [2] (any of the three may be NULL; range_bin: the host's map).  An engine that owns a
+ * share of the frames (r3d_volume_reduce_by_frame) is projected piece by piece, cut where the job's groups are cut,
+ * so that a group that straddles two owners is the sum of their parts.  Synchronous.  Returns 0 on success.       */
+int r3d_volume_project_to_host(int device, const uint32_t* d_counters, const r3d_volume_desc* v, uint32_t frame_begin,
+                               uint32_t frame_end, uint32_t frame_group, const uint32_t* range_bin, uint32_t n_range,
+                               uint32_t out_frame0, uint32_t n_out_total, uint64_t* above, uint64_t* elev,
+                               uint64_t* outside);
+
 /* ---- optional per-event report stream --------------------------------------
  * The reference's `--reports[=KEYWORDS]` (main.cpp:223-258) writes one text line
  * per event with the phonon's state at that moment (dataout.cpp:484-520): GEN

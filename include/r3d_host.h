@@ -62,6 +62,25 @@ int r3dh_write_errors(r3dh_model* m, const double* energy_se, const double* coun
                       const char* outdir);
 uint32_t r3dh_error_batches(const r3dh_model* m);
 
+/* --scatter-views[=GROUP] [--scatter-view-azimuth=AZI,HALFWIDTH] [--no-scatter-grid-file] in the model's arguments
+ * (all three refused without --scatter-grid, the last two without --scatter-views): returns 1 and fills *group
+ * (grid frames per frame of the views), azimuth[2] (degrees; half width 180 = no filter) and *no_grid_file when the
+ * views were asked for, 0 otherwise.  Any of the three may be NULL.
+ * r3dh_write_view_header: the GNU/Octave text header of one video view of the scatter-event grid (r3d.h
+ * r3d_volume_project) to `path`: ViewKind ("above" / "elevation"), ViewAxes, ViewDims (the raw file's fastest two
+ * axes: nx, ny or n_range, nz), ViewFrames, ViewFrameGroup, ViewWaveTypes, ViewFrameSeconds (the grid's frame length
+ * x group), ViewBoxLo / Hi, ViewRangeBin, ViewEpicentre, ViewAzimuthFilter, ViewEventsInView, ViewEventsOutside,
+ * ViewFile (little-endian uint64 [2][frames][dims[1]][dims[0]]).  Returns 0 ok.                                  */
+typedef struct r3dh_view_header {
+  int32_t  elevation;            /* 0: from above; 1: range x depth                       */
+  uint32_t dims[2], frames, group;
+  double   frame_seconds, lo[2], hi[2], dr, epicentre[2], azimuth, half_width;
+  const char* raw_file;
+  uint64_t events_in_view, events_outside;
+} r3dh_view_header;
+int r3dh_scatter_views(const r3dh_model* m, uint32_t* group, double azimuth[2], int* no_grid_file);
+int r3dh_write_view_header(const r3dh_view_header* h, const char* path);
+
 /* For a model built with --device-tables (scattering tables left to the engine):
  * record what r3d_engine_scatterer_stats() returned, so that the scatterer dump
  * and r3dh_scatterer_info show the engine's numbers.  Returns 0 ok.            */

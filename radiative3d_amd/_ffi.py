@@ -88,6 +88,22 @@ class VolumeDesc(C.Structure):
                 ("n_frames", C.c_uint32), ("frame_dt", C.c_double)]
 
 
+class VolumeViews(C.Structure):
+    """include/r3d.h r3d_volume_views"""
+    _fields_ = [("size", C.c_uint32), ("frame_begin", C.c_uint32), ("frame_end", C.c_uint32),
+                ("frame_group", C.c_uint32), ("n_range", C.c_uint32), ("pad_", C.c_uint32),
+                ("d_range_bin", C.c_void_p), ("d_above", C.c_void_p), ("d_elev", C.c_void_p),
+                ("d_outside", C.c_void_p)]
+
+
+class ViewHeader(C.Structure):
+    """include/r3d_host.h r3dh_view_header"""
+    _fields_ = [("elevation", C.c_int32), ("dims", C.c_uint32 * 2), ("frames", C.c_uint32), ("group", C.c_uint32),
+                ("frame_seconds", C.c_double), ("lo", C.c_double * 2), ("hi", C.c_double * 2), ("dr", C.c_double),
+                ("epicentre", C.c_double * 2), ("azimuth", C.c_double), ("half_width", C.c_double),
+                ("raw_file", C.c_char_p), ("events_in_view", C.c_uint64), ("events_outside", C.c_uint64)]
+
+
 class Final(C.Structure):
     _fields_ = [("time", C.c_double), ("path", C.c_double), ("amp", C.c_double),
                 ("loc", C.c_double * 3), ("dir", C.c_double * 3), ("moves", C.c_uint32),
@@ -174,6 +190,10 @@ def host_lib():
         L.r3dh_write_errors.argtypes = [C.c_void_p, _dp, _dp, C.c_uint32, C.c_char_p]
         L.r3dh_error_batches.restype = C.c_uint32
         L.r3dh_error_batches.argtypes = [C.c_void_p]
+        L.r3dh_scatter_views.restype = C.c_int
+        L.r3dh_scatter_views.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), _dp, C.POINTER(C.c_int)]
+        L.r3dh_write_view_header.restype = C.c_int
+        L.r3dh_write_view_header.argtypes = [C.POINTER(ViewHeader), C.c_char_p]
         L.r3dh_seismometer_axes.restype = C.c_int
         L.r3dh_seismometer_axes.argtypes = [C.c_void_p, C.c_int]
         _host = L
@@ -314,6 +334,15 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_volume_read_range.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
         L.r3d_volume_reduce_by_frame.restype = C.c_int
         L.r3d_volume_reduce_by_frame.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        L.r3d_volume_project.restype = C.c_int
+        L.r3d_volume_project.argtypes = [C.c_int, C.c_void_p, C.POINTER(VolumeDesc), C.POINTER(VolumeViews), C.c_void_p]
+        L.r3d_volume_range_bins.restype = C.c_int
+        L.r3d_volume_range_bins.argtypes = [C.POINTER(VolumeDesc), _dp, C.c_double, C.c_uint32, C.c_double, C.c_double,
+                                            C.POINTER(C.c_uint32)]
+        L.r3d_volume_project_to_host.restype = C.c_int
+        L.r3d_volume_project_to_host.argtypes = [C.c_int, C.c_void_p, C.POINTER(VolumeDesc), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
         L.r3d_batch_moments.restype = C.c_int
         L.r3d_batch_moments.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

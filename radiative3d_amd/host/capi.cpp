@@ -126,6 +126,29 @@ int r3dh_write_errors(r3dh_model* m, const double* energy_se, const double* coun
 
 uint32_t r3dh_error_batches(const r3dh_model* m) { return m ? m->mission.ErrorBatches : 0; }
 
+int r3dh_scatter_views(const r3dh_model* m, uint32_t* group, double azimuth[2], int* no_grid_file) {
+  if (!m || !m->mission.bScatterViews) return 0;
+  if (group) *group = m->mission.ViewGroup;
+  if (azimuth) azimuth[0] = m->mission.ViewAzimuth, azimuth[1] = m->mission.ViewHalfWidth;
+  if (no_grid_file) *no_grid_file = m->mission.bNoScatterGridFile ? 1 : 0;
+  return 1;
+}
+
+int r3dh_write_view_header(const r3dh_view_header* h, const char* path) {
+  if (!h || !path || !h->raw_file) return g_error = "r3dh_write_view_header: null argument", 1;
+  ScatterViewInfo v;
+  v.elevation = h->elevation != 0;
+  for (int k = 0; k < 2; k++)
+    v.dims[k] = h->dims[k], v.lo[k] = h->lo[k], v.hi[k] = h->hi[k], v.epicentre[k] = h->epicentre[k];
+  v.frames = h->frames, v.group = h->group, v.frame_seconds = h->frame_seconds, v.dr = h->dr;
+  v.azimuth = h->azimuth, v.half_width = h->half_width, v.raw_file = h->raw_file;
+  v.events_in_view = h->events_in_view, v.events_outside = h->events_outside;
+  std::ofstream f(path);
+  OutputScatterViewHeader(v, f);
+  if (!f) return g_error = std::string("r3dh_write_view_header: cannot write ") + path, 1;
+  return 0;
+}
+
 int r3dh_model_set_scatterer_stats(r3dh_model* m, int s, const double mfp[2], const double dipole[2]) {
   if (!m || !mfp || !dipole || s < 0 || s >= (int)m->model->Scatterers().size()) return 1;
   m->model->SetScattererStats(s, mfp, dipole);

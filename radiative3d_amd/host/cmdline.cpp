@@ -15,7 +15,8 @@ enum OptID {
   OPT_REPORTS, OPT_REPORT_FILE, OPT_OUTDIR, OPT_OCSRAW, OPT_SEISBINS, OPT_SEISBINSIZE,
   OPT_SEISARRAY, OPT_SEIS_P2P, OPT_SEIS_P2PW, OPTM_HELP, OPTM_DUMPGRID, OPTM_PARAMOUTFN,
   OPTM_RTTEST, OPTM_EVENTTEST, OPTM_RUNSIM, OPTX_SEED, OPTX_GPUS, OPTX_DEVTABLES, OPTX_HOSTTABLES,
-  OPTX_DEVICES, OPTX_SCATGRID, OPTX_SCATGRID_FILE, OPTX_ERRBATCHES
+  OPTX_DEVICES, OPTX_SCATGRID, OPTX_SCATGRID_FILE, OPTX_ERRBATCHES,
+  OPTX_SCATVIEWS, OPTX_SCATVIEW_AZI, OPTX_NO_SCATGRID_FILE
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -47,7 +48,9 @@ const std::map<std::string, OptID>& option_table() {
       {"--seed", OPTX_SEED}, {"--gpus", OPTX_GPUS}, {"--device-tables", OPTX_DEVTABLES},
       {"--host-tables", OPTX_HOSTTABLES}, {"--devices", OPTX_DEVICES},
       {"--scatter-grid", OPTX_SCATGRID}, {"--scatter-grid-file", OPTX_SCATGRID_FILE},
-      {"--error-batches", OPTX_ERRBATCHES}};
+      {"--error-batches", OPTX_ERRBATCHES},
+      {"--scatter-views", OPTX_SCATVIEWS}, {"--scatter-view-azimuth", OPTX_SCATVIEW_AZI},
+      {"--no-scatter-grid-file", OPTX_NO_SCATGRID_FILE}};
   return t;
 }
 
@@ -290,8 +293,33 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
         mission.ErrorBatches = (unsigned)b;
         break;
       }
+      case OPTX_SCATVIEWS: {
+        const long g = o.has() ? o.integer() : 1;
+        if (g < 1 || g > 0xFFFFFFFFL)
+          throw Runtime("--scatter-views[=GROUP]: GROUP, the grid frames per frame of the views, must be positive (got " +
+                        std::to_string(g) + ").");
+        mission.bScatterViews = true;
+        mission.ViewGroup = (unsigned)g;
+        break;
+      }
+      case OPTX_SCATVIEW_AZI:
+        mission.ViewAzimuth = o.real();
+        mission.ViewHalfWidth = o.real();
+        if (!(mission.ViewHalfWidth >= 0)) throw Runtime("--scatter-view-azimuth=AZI,HALFWIDTH: HALFWIDTH must not be negative.");
+        mission.bViewAzimuth = true;
+        break;
+      case OPTX_NO_SCATGRID_FILE: mission.bNoScatterGridFile = true; break;
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }
   }
+  // the views are made from the grid: none of their options means anything without it
+  if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile))
+    throw Runtime(std::string(mission.bScatterViews ? "--scatter-views" : mission.bViewAzimuth ? "--scatter-view-azimuth"
+                                                                                                : "--no-scatter-grid-file") +
+                  " needs --scatter-grid: the views are projections of that grid.");
+  if (mission.bNoScatterGridFile && !mission.bScatterViews)
+    throw Runtime("--no-scatter-grid-file needs --scatter-views: without the views the run would leave nothing of its grid.");
+  if (mission.bViewAzimuth && !mission.bScatterViews)
+    throw Runtime("--scatter-view-azimuth needs --scatter-views: it filters the elevation view.");
 }

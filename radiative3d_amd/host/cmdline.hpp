@@ -37,6 +37,13 @@ struct MissionParams {
   // --error-batches=B (2..64): run the histories as B id-partitioned batches and write each bin's standard error
   // (seis_NNN_err.octv beside seis_NNN.octv; include/r3d.h r3d_run_batched); 0 = not asked for
   unsigned ErrorBatches = 0;
+  // --scatter-views[=GROUP]: the grid's two video views (include/r3d.h r3d_volume_project), GROUP grid frames per
+  // frame of the views, as scatterview_above.{octv,u64} and scatterview_elev.{octv,u64};
+  // --scatter-view-azimuth=AZI,HALFWIDTH (degrees): the elevation view keeps the columns in that cone about the
+  // epicentre; --no-scatter-grid-file: the raw grid is neither read back nor written
+  bool bScatterViews = false, bViewAzimuth = false, bNoScatterGridFile = false;
+  unsigned ViewGroup = 1;
+  double ViewAzimuth = 0.0, ViewHalfWidth = 180.0;
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

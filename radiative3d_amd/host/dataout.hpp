@@ -57,6 +57,23 @@ void OutputReports(const r3d_event* ev, size_t n, std::ostream& out);
 // the grid's shape, box, frame length and the name of the raw file beside it, which holds
 // count[type P,S][frame][iz][iy][ix] as little-endian uint32 (x fastest) -- in Octave:
 //   c = reshape(fread(fopen(GridFile), Inf, "uint32"), GridDims(1), GridDims(2), GridDims(3), GridFrames, 2);
+// Header of one video view of that grid (--scatter-views; include/r3d.h r3d_volume_project): `elevation` false: the
+// events of each output frame seen from above, sum[type][frame][iy][ix]; true: in elevation, sum[type][frame][iz][ir],
+// ir the range bin of width `dr` about `epicentre`, columns outside azimuth +- half_width (degrees; >= 180: none)
+// left out.  The raw file beside it holds little-endian uint64, the first of ViewDims fastest -- in Octave:
+//   v = reshape(fread(fopen(ViewFile), Inf, "uint64"), ViewDims(1), ViewDims(2), ViewFrames, 2);
+struct ScatterViewInfo {
+  bool elevation;
+  unsigned dims[2];              // above: nx, ny; elevation: n_range, nz
+  unsigned frames, group;        // output frames; grid frames per output frame
+  double frame_seconds;          // grid frame length x group
+  double lo[2], hi[2];           // above: x, y of the box; elevation: range 0 .. n_range dr, z of the box
+  double dr, epicentre[2], azimuth, half_width;
+  std::string raw_file;
+  unsigned long long events_in_view, events_outside;
+};
+void OutputScatterViewHeader(const ScatterViewInfo& v, std::ostream& out);
+
 void OutputScatterGridHeader(const unsigned dims[3], unsigned frames, const double lo[3], const double hi[3],
                              double frame_dt, const std::string& raw_file, unsigned long long events_binned,
                              unsigned long long saturated_cells, std::ostream& out);

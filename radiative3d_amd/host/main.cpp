@@ -105,7 +105,87 @@ struct GridJob {
   bool on = false;
   r3d_volume_desc desc{};
   std::string header_path, raw_path, raw_name;
+  // --scatter-views: the grid's two video views, written beside it (or, with --no-scatter-grid-file, in its place)
+  bool views = false, raw_file = true;
+  unsigned group = 1;
+  double azimuth = 0.0, half_width = 180.0;
+  std::string dir;
 };
+
+// One raw file written under a temporary name and renamed when complete.
+void write_raw(const std::string& path, const void* data, size_t bytes) {
+  const std::string part = path + ".part";
+  {
+    std::ofstream f(part.c_str(), std::ios::binary);
+    f.write(static_cast<const char*>(data), (std::streamsize)bytes);
+    if (!f) {
+      std::remove(part.c_str());
+      throw Runtime("cannot write " + part);
+    }
+  }
+  if (std::rename(part.c_str(), path.c_str())) {
+    std::remove(part.c_str());
+    throw Runtime("cannot rename " + part + " to " + path);
+  }
+}
+
+// --scatter-views: every engine projects the frames it owns (include/r3d.h r3d_volume_project_to_host), piece by
+// piece, cut where the job's groups of frames are cut; the pieces of a group that straddles two owners add up on
+// the host.  Epicentre = the model's source, dr = the smaller horizontal cell size, n_range = enough bins to reach
+// the grid's corner farthest from the epicentre.
+void write_scatter_views(const GridJob& grid, const r3d_model_desc& d, const std::vector<r3d_engine*>& engines,
+                         const std::vector<int>& devices, const std::vector<uint32_t>& frames, uint64_t saturated) {
+  const r3d_volume_desc& v = grid.desc;
+  const double epi[2] = {d.source.loc[0], d.source.loc[1]};
+  const double dr = std::min(v.cell_size[0], v.cell_size[1]);
+  double far = 0;
+  for (int cx = 0; cx < 2; cx++)
+    for (int cy = 0; cy < 2; cy++) {
+      const double dx = v.origin[0] + cx * v.cell_size[0] * v.dims[0] - epi[0];
+      const double dy = v.origin[1] + cy * v.cell_size[1] * v.dims[1] - epi[1];
+      far = std::max(far, std::sqrt(dx * dx + dy * dy));
+    }
+  const uint32_t n_range = (uint32_t)std::floor(far / dr) + 1;
+  const uint32_t nx = v.dims[0], ny = v.dims[1], nz = v.dims[2], nf = v.n_frames;
+  const uint32_t group = std::min<uint32_t>(grid.group, nf);
+  const uint32_t n_out = (nf + group - 1) / group;
+  std::vector<uint32_t> map((size_t)ny * nx);
+  if (r3d_volume_range_bins(&v, epi, dr, n_range, grid.azimuth, grid.half_width, map.data())) throw Runtime(r3d_last_error());
+  std::vector<uint64_t> above((size_t)2 * n_out * ny * nx, 0), elev((size_t)2 * n_out * nz * n_range, 0);
+  uint64_t outside[2] = {0, 0};
+  for (size_t g = 0; g < engines.size(); g++)
+    for (uint32_t begin = frames[g]; begin < frames[g + 1];) {
+      // a head piece up to the next cut of the job's groups, then everything else this engine owns in one call
+      const uint32_t end = begin % group ? std::min<uint32_t>(frames[g + 1], (begin / group + 1) * group) : frames[g + 1];
+      if (r3d_volume_project_to_host(devices[g], static_cast<const uint32_t*>(r3d_volume_device_ptr(engines[g])), &v, begin,
+                                     end, group, map.data(), n_range, begin / group, n_out, above.data(), elev.data(), outside))
+        throw Runtime(r3d_last_error());
+      begin = end;
+    }
+  unsigned long long in_above = 0, in_elev = 0;
+  for (uint64_t c : above) in_above += c;
+  for (uint64_t c : elev) in_elev += c;
+  write_raw(grid.dir + "scatterview_above.u64", above.data(), above.size() * sizeof(uint64_t));
+  write_raw(grid.dir + "scatterview_elev.u64", elev.data(), elev.size() * sizeof(uint64_t));
+  ScatterViewInfo a;
+  a.elevation = false, a.dims[0] = nx, a.dims[1] = ny, a.frames = n_out, a.group = group, a.frame_seconds = v.frame_dt * group;
+  a.lo[0] = v.origin[0], a.lo[1] = v.origin[1];
+  a.hi[0] = v.origin[0] + v.cell_size[0] * nx, a.hi[1] = v.origin[1] + v.cell_size[1] * ny;
+  a.dr = dr, a.epicentre[0] = epi[0], a.epicentre[1] = epi[1], a.azimuth = 0.0, a.half_width = 180.0;   // (no filter from above)
+  a.raw_file = "scatterview_above.u64", a.events_in_view = in_above, a.events_outside = 0;
+  ScatterViewInfo e = a;
+  e.elevation = true, e.dims[0] = n_range, e.dims[1] = nz;
+  e.lo[0] = 0.0, e.lo[1] = v.origin[2], e.hi[0] = dr * n_range, e.hi[1] = v.origin[2] + v.cell_size[2] * nz;
+  e.azimuth = grid.azimuth, e.half_width = grid.half_width;
+  e.raw_file = "scatterview_elev.u64", e.events_in_view = in_elev, e.events_outside = outside[0] + outside[1];
+  std::ofstream ha((grid.dir + "scatterview_above.octv").c_str()), he((grid.dir + "scatterview_elev.octv").c_str());
+  OutputScatterViewHeader(a, ha);
+  OutputScatterViewHeader(e, he);
+  if (!ha || !he) throw Runtime("cannot write the view headers under " + (grid.dir.empty() ? std::string(".") : grid.dir));
+  std::cout << "|  Scatter-event views: " << in_above << " events in " << n_out << " frames of " << group
+            << " grid frames, from above " << nx << " x " << ny << ", in elevation " << n_range << " x " << nz << " ("
+            << outside[0] + outside[1] << " events outside it; " << saturated << " grid cells at the 2^32 - 1 ceiling) -> " << grid.dir << "scatterview_{above,elev}.{octv,u64}\n";
+}
 
 // A scatter grid is checked BEFORE the run (a 1e8-history job must not find out at its end that its grid
 // cannot be reduced or written): the pair exchange of r3d_volume_reduce_by_frame carries 32-bit cell indices,
@@ -116,7 +196,7 @@ void check_grid_job(const GridJob& grid, size_t n_shards) {
   if (n_shards > 1 && cells >= (1ull << 32))
     throw Runtime("--scatter-grid: 2 x NX x NY x NZ x FRAMES = " + std::to_string(cells) + " cells do not fit the 32-bit cell "
                   "indices the shards' grids are added with (r3d_volume_reduce_by_frame); use one device or a coarser grid.");
-  const std::string probe = grid.raw_path + ".part";
+  const std::string probe = (grid.raw_file ? grid.raw_path : grid.dir + "scatterview_above.u64") + ".part";
   std::ofstream f(probe.c_str(), std::ios::binary);
   if (!f) throw Runtime("--scatter-grid: cannot write " + probe);
   f.close();
@@ -146,7 +226,8 @@ struct StdoutToStderr {
 void run_simulation(const Model& model, uint64_t n, uint64_t seed, r3d_node* node, r3d_result& total,
                     std::vector<double>& energy, std::vector<uint64_t>& counts, uint32_t report_mask,
                     std::vector<r3d_event>& events, uint64_t& events_dropped, const GridJob& grid,
-                    unsigned error_batches, std::vector<double>& energy_se, std::vector<double>& counts_se) {
+                    unsigned error_batches, std::vector<double>& energy_se, std::vector<double>& counts_se,
+                    const std::vector<int>& devices) {
   const r3d_model_desc& d = model.Desc();
   const int gpus = r3d_node_size(node);
   const size_t ne = (size_t)d.n_seismometers * d.params.n_bins * R3D_N_ENERGY;
@@ -190,6 +271,8 @@ void run_simulation(const Model& model, uint64_t n, uint64_t seed, r3d_node* nod
     std::vector<uint32_t> frames(gpus + 1);
     uint64_t saturated = 0;
     if (r3d_volume_reduce_by_frame(engines.data(), gpus, frames.data(), &saturated)) throw Runtime(r3d_last_error());
+    if (grid.views) write_scatter_views(grid, d, engines, devices, frames, saturated);
+    if (!grid.raw_file) return;
     const uint64_t fc = (uint64_t)grid.desc.dims[0] * grid.desc.dims[1] * grid.desc.dims[2], nf = grid.desc.n_frames;
     unsigned long long binned = 0;
     // (written under a temporary name and renamed when complete: a failed run leaves no half-written grid behind)
@@ -250,6 +333,10 @@ int main(int argc, char* argv[]) {
               << "take-off set, source and scattering tables in HBM unless told otherwise)  --device-tables\n"
               << "--scatter-grid=NX,NY,NZ,FRAMES,X0,Y0,Z0,X1,Y1,Z1 [--scatter-grid-file=<name>]: SCT / REF events per wave\n"
               << "type, frame and model-space cell, written as <name>.octv + <name>.u32 under --output-dir\n"
+              << "--scatter-views[=GROUP] [--scatter-view-azimuth=AZI,HALFWIDTH] [--no-scatter-grid-file] (with --scatter-grid):\n"
+              << "the grid's two video views made on the GPU, GROUP grid frames per frame -- the events from above (x, y) and in\n"
+              << "elevation (range from the epicentre, z; only the columns within HALFWIDTH degrees of azimuth AZI) -- as\n"
+              << "scatterview_above.{octv,u64} and scatterview_elev.{octv,u64}; the last option leaves the raw grid unwritten\n"
               << "--error-batches=B (2..64, one device): the histories run as B id-partitioned batches and every bin's\n"
               << "standard error is written to seis_NNN_err.octv beside seis_NNN.octv\n\n";
     return 0;
@@ -301,6 +388,9 @@ int main(int argc, char* argv[]) {
         grid.desc.n_frames = mission.GridFrames;
         grid.desc.frame_dt = par.PhononTTL / mission.GridFrames;
         const std::string dir = mission.OutputDir.empty() ? "" : mission.OutputDir + "/";
+        grid.dir = dir;
+        grid.views = mission.bScatterViews, grid.raw_file = !mission.bNoScatterGridFile, grid.group = mission.ViewGroup;
+        grid.azimuth = mission.ViewAzimuth, grid.half_width = mission.ViewHalfWidth;
         grid.raw_name = mission.ScatterGridFile + ".u32";
         grid.raw_path = dir + grid.raw_name, grid.header_path = dir + mission.ScatterGridFile + ".octv";
         check_grid_job(grid, devices.size());
@@ -335,7 +425,7 @@ int main(int argc, char* argv[]) {
         std::vector<double> energy_se, counts_se;
         uint64_t dropped = 0;
         run_simulation(model, (uint64_t)std::max(0L, par.NumPhonons), mission.Seed, held.node, res, energy, counts,
-                       report_mask, events, dropped, grid, mission.ErrorBatches, energy_se, counts_se);
+                       report_mask, events, dropped, grid, mission.ErrorBatches, energy_se, counts_se, devices);
         if (report_mask) {   // the reference writes them as they happen: stdout, or --report-file
           if (mission.ReportFile.empty()) {
             OutputReports(events.data(), events.size(), std::cout);

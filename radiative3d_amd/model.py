@@ -221,6 +221,15 @@ class Model:
         """What --error-batches=B in the model's arguments asked for (0: absent)."""
         return int(self._lib.r3dh_error_batches(self._h))
 
+    @property
+    def scatter_views(self):
+        """What --scatter-views[=GROUP] [--scatter-view-azimuth=AZI,HALFWIDTH] [--no-scatter-grid-file] asked for:
+        None, or dict(group, azimuth, half_width, no_grid_file)."""
+        group, azi, no_file = C.c_uint32(0), (C.c_double * 2)(), C.c_int(0)
+        if not self._lib.r3dh_scatter_views(self._h, C.byref(group), azi, C.byref(no_file)):
+            return None
+        return dict(group=int(group.value), azimuth=azi[0], half_width=azi[1], no_grid_file=bool(no_file.value))
+
     def new_result(self):
         return Result(self.n_seismometers, self.n_bins)
 
@@ -349,6 +358,68 @@ def volume_desc(origin, cell_size, dims, n_frames, frame_dt):
         v.origin[k], v.cell_size[k], v.dims[k] = origin[k], cell_size[k], dims[k]
     v.n_frames, v.frame_dt = n_frames, frame_dt
     return v
+
+
+def range_bins(desc, epicentre, dr, n_range, azimuth_deg=0.0, half_width_deg=180.0):
+    """r3d_volume_range_bins: the column map of the elevation view, numpy uint32 [ny][nx] -- the range bin
+    floor(rho / dr) of every column's centre, rho its horizontal distance from `epicentre` (x, y), or 0xFFFFFFFF
+    for a column beyond n_range bins or outside azimuth_deg +- half_width_deg (half_width_deg >= 180: no filter).
+    `desc`: a volume_desc(...).  Made on the host; needs no GPU.  include/r3d.h has the definition."""
+    lib = _ffi.hip_lib()
+    out = np.empty((int(desc.dims[1]), int(desc.dims[0])), dtype=np.uint32)
+    epi = (C.c_double * 2)(float(epicentre[0]), float(epicentre[1]))
+    if lib.r3d_volume_range_bins(C.byref(desc), epi, float(dr), int(n_range), float(azimuth_deg), float(half_width_deg),
+                                 out.ctypes.data_as(C.POINTER(C.c_uint32))):
+        raise RuntimeError("r3d_volume_range_bins failed: " + lib.r3d_last_error().decode())
+    return out
+
+
+def project_volume(counters, desc, frame_begin, frame_end, frame_group=1, range_bin=None, n_range=0, above=True,
+                   outputs=None, stream=None):
+    """r3d_volume_project on torch tensors: `counters` is a grid of the shape `desc` (a volume_desc) on a GPU, 32-bit.
+    Returns (above, elev, outside): int64 device tensors [2][n_out][ny][nx], [2][n_out][nz][n_range] and [2] holding
+    the uint64 sums (above is None with above=False; elev and outside are None without a `range_bin` map -- a
+    uint32 [ny][nx] numpy array from range_bins(), or a 32-bit tensor already on the device).  `outputs`: the same
+    triple from an earlier call, to be ADDED into.  Asynchronous on `stream` (a raw hipStream_t; None: torch's
+    current one).  include/r3d.h has the definition of the views."""
+    import torch
+    lib = _ffi.hip_lib()
+    if not counters.is_cuda or not counters.is_contiguous() or counters.element_size() != 4:
+        raise ValueError("the grid must be a contiguous tensor of 32-bit counters on a GPU")
+    nx, ny, nz = (int(d) for d in desc.dims)
+    if counters.numel() != 2 * int(desc.n_frames) * nz * ny * nx:
+        raise ValueError("the grid does not have the description's size")
+    dev = counters.device
+    n_out = max(0, -(-(int(frame_end) - int(frame_begin)) // max(1, int(frame_group))))
+    elev_on = range_bin is not None
+    if elev_on and not torch.is_tensor(range_bin):
+        range_bin = torch.from_numpy(np.ascontiguousarray(range_bin, dtype=np.uint32).view(np.int32)).to(dev)
+    if elev_on and (range_bin.device != dev or range_bin.numel() != ny * nx or range_bin.element_size() != 4
+                    or not range_bin.is_contiguous()):
+        raise ValueError("range_bin must be [ny][nx] contiguous 32-bit values on the grid's GPU")
+    a, e, o = outputs if outputs is not None else (None, None, None)
+    if (not above and a is not None) or (not elev_on and (e is not None or o is not None)):
+        raise ValueError("`outputs` holds a view that this call does not ask for")
+    if above and a is None:
+        a = torch.zeros((2, n_out, ny, nx), dtype=torch.int64, device=dev)
+    if elev_on and e is None:
+        e = torch.zeros((2, n_out, nz, int(n_range)), dtype=torch.int64, device=dev)
+    if elev_on and o is None:
+        o = torch.zeros(2, dtype=torch.int64, device=dev)
+    for t, shape in ((a, (2, n_out, ny, nx)), (e, (2, n_out, nz, int(n_range))), (o, (2,))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.int64 or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"a view to add into must be a contiguous int64 tensor {shape} on the grid's GPU")
+    views = _ffi.VolumeViews(size=C.sizeof(_ffi.VolumeViews), frame_begin=int(frame_begin), frame_end=int(frame_end),
+                             frame_group=int(frame_group), n_range=int(n_range) if elev_on else 0,
+                             d_range_bin=range_bin.data_ptr() if elev_on else None,
+                             d_above=a.data_ptr() if a is not None else None,
+                             d_elev=e.data_ptr() if e is not None else None,
+                             d_outside=o.data_ptr() if o is not None else None)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    if lib.r3d_volume_project(dev.index or 0, counters.data_ptr(), C.byref(desc), C.byref(views), stream):
+        raise RuntimeError("r3d_volume_project failed: " + lib.r3d_last_error().decode())
+    return a, e, o
 
 
 class Engine:

@@ -205,6 +205,8 @@ class DeviceVolume:
         self.widened = None
         self.owned = None
         self.timing = {}
+        from .model import volume_desc
+        self.desc = volume_desc(origin, cell_size, dims, n_frames, frame_dt)
         self.engine = engine
         if engine is not None:   # (the engine keeps a reference to the tensor: model.Engine.set_volume_buffer)
             engine.set_volume_buffer(origin, cell_size, dims, n_frames, frame_dt, self.counters)
@@ -468,6 +470,21 @@ class DeviceVolume:
             dist.all_reduce(v, op=dist.ReduceOp.SUM)
             t = int(v.item())
         return t
+
+    def project(self, frame_begin=None, frame_end=None, frame_group=1, range_bin=None, n_range=0, above=True, outputs=None):
+        """The two video views of frames [frame_begin, frame_end) (default: the frames this rank holds job totals
+        for), `frame_group` grid frames per output frame, as device tensors (above, elev, outside) -- model.py
+        project_volume, include/r3d.h r3d_volume_project.  `range_bin`: the column map of model.range_bins(self.desc,
+        ...); without it only the above view is made.  Frames outside `owned` are refused, as every read is."""
+        from .model import project_volume
+        if self.owned == ():
+            self._valid_runs()
+        lo, hi = (0, self.n_frames) if self.owned is None else self.owned
+        frame_begin = lo if frame_begin is None else int(frame_begin)
+        frame_end = hi if frame_end is None else int(frame_end)
+        if frame_begin < frame_end and not (lo <= frame_begin and frame_end <= hi):
+            raise RuntimeError(f"only frames {(lo, hi)} of this rank's grid hold job totals (reduce_scatter_frames_)")
+        return project_volume(self.counters, self.desc, frame_begin, frame_end, frame_group, range_bin, n_range, above, outputs)
 
     def frames_numpy(self):
         """(lo, hi, counts[2][hi - lo][z][y][x]) of the frames this rank holds job totals for."""
