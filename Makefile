@@ -46,12 +46,16 @@ STATS_HDR := $(STATSDIR)/r3d_batch_moments.h include/r3d.h
 VIEWSDIR  := radiative3d_amd/views
 VIEWS_SRC := $(VIEWSDIR)/r3d_volume_project.hip
 VIEWS_HDR := $(VIEWSDIR)/r3d_volume_views.h include/r3d.h
+# the grid reduced along its frame axis: arrival-time, peak and total maps (r3d_volume_time_maps): a device-level call
+MAPSDIR  := radiative3d_amd/maps
+MAPS_SRC := $(MAPSDIR)/r3d_volume_time_maps.hip
+MAPS_HDR := $(MAPSDIR)/r3d_volume_time_maps.h include/r3d.h
 OBJDIR   := build/obj
 
 # (the default goal is the first target of the file: it has to come before the generated object rules)
 .PHONY: default all host engine repro oracle cli clean
 default: all
-# engine_objects(tag, extra flags): the eight objects of one engine build
+# engine_objects(tag, extra flags): the nine objects of one engine build
 define engine_objects
 $(OBJDIR)/$(1)_engine.o: $(CSRC)/r3d_engine.hip $(ENGINE_HDR)
 	@mkdir -p $(OBJDIR)
@@ -77,8 +81,11 @@ $(OBJDIR)/$(1)_stats.o: $(STATS_SRC) $(STATS_HDR)
 $(OBJDIR)/$(1)_views.o: $(VIEWS_SRC) $(VIEWS_HDR)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(VIEWS_SRC)
+$(OBJDIR)/$(1)_maps.o: $(MAPS_SRC) $(MAPS_HDR)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(MAPS_SRC)
 endef
-engine_objs = $(OBJDIR)/$(1)_stats.o $(OBJDIR)/$(1)_views.o $(OBJDIR)/$(1)_engine.o $(OBJDIR)/$(1)_tables.o $(OBJDIR)/$(1)_volume.o $(OBJDIR)/$(1)_cyl.o $(OBJDIR)/$(1)_tet.o $(OBJDIR)/$(1)_sph.o
+engine_objs = $(OBJDIR)/$(1)_stats.o $(OBJDIR)/$(1)_views.o $(OBJDIR)/$(1)_maps.o $(OBJDIR)/$(1)_engine.o $(OBJDIR)/$(1)_tables.o $(OBJDIR)/$(1)_volume.o $(OBJDIR)/$(1)_cyl.o $(OBJDIR)/$(1)_tet.o $(OBJDIR)/$(1)_sph.o
 $(eval $(call engine_objects,main,))
 $(eval $(call engine_objects,repro,-DR3D_REPRODUCIBLE -ffp-contract=off))
 
@@ -139,15 +146,16 @@ VOBJ = $(OBJDIR)/v$(NAME)
 VDEFS = -DR3D_DEV_BUILD $(DEFS)
 variant:
 	@mkdir -p $(OBJDIR)
-	rm -f $(VOBJ)_engine.o $(VOBJ)_tables.o $(VOBJ)_volume.o $(VOBJ)_cyl.o $(VOBJ)_tet.o $(VOBJ)_sph.o $(VOBJ)_stats.o $(VOBJ)_views.o $(LIBDIR)/variant_$(NAME).so
+	rm -f $(VOBJ)_engine.o $(VOBJ)_tables.o $(VOBJ)_volume.o $(VOBJ)_cyl.o $(VOBJ)_tet.o $(VOBJ)_sph.o $(VOBJ)_stats.o $(VOBJ)_views.o $(VOBJ)_maps.o $(LIBDIR)/variant_$(NAME).so
 	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_engine.o $(CSRC)/r3d_engine.hip & p1=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_tables.o $(CSRC)/r3d_tables_build.hip & p2=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_volume.o $(CSRC)/r3d_volume.hip & p6=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_stats.o $(STATS_SRC) & p7=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_views.o $(VIEWS_SRC) & p8=$$!; \
+	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_maps.o $(MAPS_SRC) & p9=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_CYL) $(VDEFS) $(DEFS_CYL) -DR3D_KIND=0 -c -o $(VOBJ)_cyl.o $(CSRC)/r3d_kernels_kind.hip & p3=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_TET) $(VDEFS) $(DEFS_TET) -DR3D_KIND=1 -c -o $(VOBJ)_tet.o $(CSRC)/r3d_kernels_kind.hip & p4=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_SPH) $(VDEFS) $(DEFS_SPH) -DR3D_KIND=2 -c -o $(VOBJ)_sph.o $(CSRC)/r3d_kernels_kind.hip & p5=$$!; \
-	rc=0; for p in $$p1 $$p2 $$p3 $$p4 $$p5 $$p6 $$p7 $$p8; do wait $$p || rc=1; done; exit $$rc
+	rc=0; for p in $$p1 $$p2 $$p3 $$p4 $$p5 $$p6 $$p7 $$p8 $$p9; do wait $$p || rc=1; done; exit $$rc
 	$(HIPCC) --offload-arch=gfx950 -shared -pthread -o $(LIBDIR)/variant_$(NAME).so $(VOBJ)_engine.o \
-	    $(VOBJ)_tables.o $(VOBJ)_volume.o $(VOBJ)_cyl.o $(VOBJ)_tet.o $(VOBJ)_sph.o $(VOBJ)_stats.o $(VOBJ)_views.o $(RCCL_LIBS)
+	    $(VOBJ)_tables.o $(VOBJ)_volume.o $(VOBJ)_cyl.o $(VOBJ)_tet.o $(VOBJ)_sph.o $(VOBJ)_stats.o $(VOBJ)_views.o $(VOBJ)_maps.o $(RCCL_LIBS)

@@ -524,6 +524,57 @@ int r3d_volume_project_to_host(int device, const uint32_t* d_counters, const r3d
                                uint32_t out_frame0, uint32_t n_out_total, uint64_t* above, uint64_t* elev,
                                uint64_t* outside);
 
+/* ---- the grid reduced along TIME: arrival, peak and total maps -------------------
+ * The views reduce the grid along z and along range; the three stills a user takes from a clean-wavefront movie
+ * reduce it along its frame axis: when scattered energy first reaches a place (the travel-time field), when and how
+ * strongly activity peaks there, and how many events the place saw over the run.
+ *
+ * THE MAPS.  Grid as in r3d_volume_desc.  A call covers the grid frames [frame_begin, frame_end) with a threshold
+ * min_count >= 1.  Every wave type t and cell (iz, iy, ix) has four map entries, each map [2][nz][ny][nx]:
+ *     first      (uint32)  the smallest frame f with count >= min_count; 0xFFFFFFFF if there is none
+ *     peak_count (uint32)  the largest count over the frames
+ *     peak_frame (uint32)  the smallest frame at which peak_count is reached; 0xFFFFFFFF while peak_count == 0
+ *     total      (uint64)  the sum of the counts; a cell pinned at 2^32 - 1 counts as that value
+ * Frames are ABSOLUTE grid frame indices, not relative to frame_begin; the time of frame f is (f + 1) * frame_dt, the
+ * reference's own label (vis/scattervid/scattervid_above.m, scattervid_axial.m: (f_idx+1)*dt).  The maps are UPDATED,
+ * the way every other result buffer of this ABI is added into: for each f of the range, c = count[t][f][iz][iy][ix],
+ *     total += c
+ *     if (c >= min_count && f < first)                                    first = f
+ *     if (c > peak_count || (c == peak_count && c > 0 && f < peak_frame)) peak_count = c, peak_frame = f
+ * THE NEUTRAL START is first = peak_frame = 0xFFFFFFFF, peak_count = total = 0: a byte-wise memset of 0xFF or of 0,
+ * which the CALLER does before the first call.  The update is a min, a lexicographic max of (count, earlier frame)
+ * and a sum, so it is associative and commutative: pieces of the frame range, taken in any order and on any engine,
+ * give the maps of one call.  All arithmetic is integer; the result has the same bits on every run.
+ *
+ * r3d_volume_time_maps: device level, like r3d_volume_project -- d_counters is any grid of the shape *v on `device`
+ * (the engine's own through r3d_volume_device_ptr, or the caller's), only read; asynchronous on `stream`; every
+ * counter of the range is loaded once, whichever maps are asked for.  One work-item owns four neighbouring ix of one
+ * (t, iz, iy) and walks the frames, so no cell has two writers and there are no atomics.  The frames are not split
+ * over workgroups: a grid with few cells and many frames is not the workload (config 5 has 2.1e6 such quads).
+ * REFUSED (non-zero, r3d_last_error, nothing enqueued, no buffer touched; all checked before any HIP call): a null
+ * grid, description or maps, a size mismatch, an empty grid, frame_begin > frame_end, frame_end > n_frames,
+ * min_count == 0, all maps NULL, exactly one of d_peak_frame / d_peak_count.  An empty frame range is success and
+ * touches nothing.                                                                                                 */
+typedef struct r3d_volume_maps {
+  uint32_t size;                    /* sizeof(r3d_volume_maps): a mismatch is refused          */
+  uint32_t frame_begin, frame_end, min_count;
+  uint32_t* d_first;                /* [2][nz][ny][nx], device, or NULL                        */
+  uint32_t* d_peak_frame;           /* both or neither                                         */
+  uint32_t* d_peak_count;
+  uint64_t* d_total;                /* or NULL                                                 */
+} r3d_volume_maps;
+int r3d_volume_time_maps(int device, const uint32_t* d_counters, const r3d_volume_desc* v,
+                         const r3d_volume_maps* maps, void* stream);
+/* The maps for a host that holds no device memory of its own (./main --scatter-maps): scratch maps on `device` at the
+ * neutral start are brought up to date with frames [frame_begin, frame_end) of d_counters, read back, and MERGED into
+ * the host arrays (each [2][nz][ny][nx]; first / total may be NULL, peak_frame and peak_count both or neither), which
+ * the caller has put into the neutral state before the first call.  The merge is the update rule applied to two
+ * partial states, so every engine's own frames (r3d_volume_reduce_by_frame) go into ONE set of host arrays, in any
+ * order.  Synchronous.  Returns 0 on success; refuses what r3d_volume_time_maps refuses.                        */
+int r3d_volume_time_maps_to_host(int device, const uint32_t* d_counters, const r3d_volume_desc* v,
+                                 uint32_t frame_begin, uint32_t frame_end, uint32_t min_count,
+                                 uint32_t* first, uint32_t* peak_frame, uint32_t* peak_count, uint64_t* total);
+
 /* ---- optional per-event report stream --------------------------------------
  * The reference's `--reports[=KEYWORDS]` (main.cpp:223-258) writes one text line
  * per event with the phonon's state at that moment (dataout.cpp:484-520): GEN

@@ -81,6 +81,23 @@ typedef struct r3dh_view_header {
 int r3dh_scatter_views(const r3dh_model* m, uint32_t* group, double azimuth[2], int* no_grid_file);
 int r3dh_write_view_header(const r3dh_view_header* h, const char* path);
 
+/* --scatter-maps[=MINCOUNT] in the model's arguments (refused without --scatter-grid; independent of --scatter-views):
+ * returns 1 and fills *min_count (may be NULL; default 1) when the maps along time were asked for, 0 otherwise.
+ * r3dh_write_maps_header: the GNU/Octave text header of those maps (r3d.h r3d_volume_time_maps) to `path`: MapDims
+ * (nx, ny, nz), MapFrames, MapWaveTypes, MapFrameSeconds (the time of frame f is (f + 1) x this), MapMinCount,
+ * MapBoxLo / Hi, MapNever (= 4294967295: the frame index of "never"), the range map of the elevation still --
+ * MapRangeBins, MapRangeBin, MapEpicentre, MapAzimuthFilter -- and MapFiles: <prefix>_first.u32, _peakframe.u32,
+ * _peakcount.u32 (little-endian uint32 [2][nz][ny][nx]), _total.u64 (uint64, the same shape), and the two first-arrival
+ * stills _first_above.u32 [2][ny][nx] (min over iz) and _first_elev.u32 [2][nz][n_range] (min over the columns of a
+ * range bin).  Returns 0 ok.                                                                                       */
+typedef struct r3dh_maps_header {
+  uint32_t dims[3], frames, min_count, n_range;
+  double   frame_seconds, lo[3], hi[3], dr, epicentre[2], azimuth, half_width;
+  const char* prefix;
+} r3dh_maps_header;
+int r3dh_scatter_maps(const r3dh_model* m, uint32_t* min_count);
+int r3dh_write_maps_header(const r3dh_maps_header* h, const char* path);
+
 /* For a model built with --device-tables (scattering tables left to the engine):
  * record what r3d_engine_scatterer_stats() returned, so that the scatterer dump
  * and r3dh_scatterer_info show the engine's numbers.  Returns 0 ok.            */

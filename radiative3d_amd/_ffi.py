@@ -104,6 +104,21 @@ class ViewHeader(C.Structure):
                 ("raw_file", C.c_char_p), ("events_in_view", C.c_uint64), ("events_outside", C.c_uint64)]
 
 
+class VolumeMaps(C.Structure):
+    """include/r3d.h r3d_volume_maps"""
+    _fields_ = [("size", C.c_uint32), ("frame_begin", C.c_uint32), ("frame_end", C.c_uint32), ("min_count", C.c_uint32),
+                ("d_first", C.c_void_p), ("d_peak_frame", C.c_void_p), ("d_peak_count", C.c_void_p),
+                ("d_total", C.c_void_p)]
+
+
+class MapsHeader(C.Structure):
+    """include/r3d_host.h r3dh_maps_header"""
+    _fields_ = [("dims", C.c_uint32 * 3), ("frames", C.c_uint32), ("min_count", C.c_uint32), ("n_range", C.c_uint32),
+                ("frame_seconds", C.c_double), ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("dr", C.c_double),
+                ("epicentre", C.c_double * 2), ("azimuth", C.c_double), ("half_width", C.c_double),
+                ("prefix", C.c_char_p)]
+
+
 class Final(C.Structure):
     _fields_ = [("time", C.c_double), ("path", C.c_double), ("amp", C.c_double),
                 ("loc", C.c_double * 3), ("dir", C.c_double * 3), ("moves", C.c_uint32),
@@ -194,6 +209,10 @@ def host_lib():
         L.r3dh_scatter_views.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), _dp, C.POINTER(C.c_int)]
         L.r3dh_write_view_header.restype = C.c_int
         L.r3dh_write_view_header.argtypes = [C.POINTER(ViewHeader), C.c_char_p]
+        L.r3dh_scatter_maps.restype = C.c_int
+        L.r3dh_scatter_maps.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.r3dh_write_maps_header.restype = C.c_int
+        L.r3dh_write_maps_header.argtypes = [C.POINTER(MapsHeader), C.c_char_p]
         L.r3dh_seismometer_axes.restype = C.c_int
         L.r3dh_seismometer_axes.argtypes = [C.c_void_p, C.c_int]
         _host = L
@@ -343,6 +362,11 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_volume_project_to_host.argtypes = [C.c_int, C.c_void_p, C.POINTER(VolumeDesc), C.c_uint32, C.c_uint32, C.c_uint32,
                                                  C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]
+        L.r3d_volume_time_maps.restype = C.c_int
+        L.r3d_volume_time_maps.argtypes = [C.c_int, C.c_void_p, C.POINTER(VolumeDesc), C.POINTER(VolumeMaps), C.c_void_p]
+        L.r3d_volume_time_maps_to_host.restype = C.c_int
+        L.r3d_volume_time_maps_to_host.argtypes = [C.c_int, C.c_void_p, C.POINTER(VolumeDesc), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.r3d_batch_moments.restype = C.c_int
         L.r3d_batch_moments.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -149,6 +149,25 @@ int r3dh_write_view_header(const r3dh_view_header* h, const char* path) {
   return 0;
 }
 
+int r3dh_scatter_maps(const r3dh_model* m, uint32_t* min_count) {
+  if (!m || !m->mission.bScatterMaps) return 0;
+  if (min_count) *min_count = m->mission.MapMinCount;
+  return 1;
+}
+
+int r3dh_write_maps_header(const r3dh_maps_header* h, const char* path) {
+  if (!h || !path || !h->prefix) return g_error = "r3dh_write_maps_header: null argument", 1;
+  ScatterMapsInfo v;
+  for (int k = 0; k < 3; k++) v.dims[k] = h->dims[k], v.lo[k] = h->lo[k], v.hi[k] = h->hi[k];
+  v.frames = h->frames, v.min_count = h->min_count, v.frame_seconds = h->frame_seconds;
+  v.n_range = h->n_range, v.dr = h->dr, v.epicentre[0] = h->epicentre[0], v.epicentre[1] = h->epicentre[1];
+  v.azimuth = h->azimuth, v.half_width = h->half_width, v.prefix = h->prefix;
+  std::ofstream f(path);
+  OutputScatterMapsHeader(v, f);
+  if (!f) return g_error = std::string("r3dh_write_maps_header: cannot write ") + path, 1;
+  return 0;
+}
+
 int r3dh_model_set_scatterer_stats(r3dh_model* m, int s, const double mfp[2], const double dipole[2]) {
   if (!m || !mfp || !dipole || s < 0 || s >= (int)m->model->Scatterers().size()) return 1;
   m->model->SetScattererStats(s, mfp, dipole);

@@ -16,7 +16,7 @@ enum OptID {
   OPT_SEISARRAY, OPT_SEIS_P2P, OPT_SEIS_P2PW, OPTM_HELP, OPTM_DUMPGRID, OPTM_PARAMOUTFN,
   OPTM_RTTEST, OPTM_EVENTTEST, OPTM_RUNSIM, OPTX_SEED, OPTX_GPUS, OPTX_DEVTABLES, OPTX_HOSTTABLES,
   OPTX_DEVICES, OPTX_SCATGRID, OPTX_SCATGRID_FILE, OPTX_ERRBATCHES,
-  OPTX_SCATVIEWS, OPTX_SCATVIEW_AZI, OPTX_NO_SCATGRID_FILE
+  OPTX_SCATVIEWS, OPTX_SCATVIEW_AZI, OPTX_NO_SCATGRID_FILE, OPTX_SCATMAPS
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -50,7 +50,7 @@ const std::map<std::string, OptID>& option_table() {
       {"--scatter-grid", OPTX_SCATGRID}, {"--scatter-grid-file", OPTX_SCATGRID_FILE},
       {"--error-batches", OPTX_ERRBATCHES},
       {"--scatter-views", OPTX_SCATVIEWS}, {"--scatter-view-azimuth", OPTX_SCATVIEW_AZI},
-      {"--no-scatter-grid-file", OPTX_NO_SCATGRID_FILE}};
+      {"--no-scatter-grid-file", OPTX_NO_SCATGRID_FILE}, {"--scatter-maps", OPTX_SCATMAPS}};
   return t;
 }
 
@@ -309,15 +309,25 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
         mission.bViewAzimuth = true;
         break;
       case OPTX_NO_SCATGRID_FILE: mission.bNoScatterGridFile = true; break;
+      case OPTX_SCATMAPS: {
+        const long c = o.has() ? o.integer() : 1;
+        if (c < 1 || c > 0xFFFFFFFFL)
+          throw Runtime("--scatter-maps[=MINCOUNT]: MINCOUNT, the events a cell needs in a frame to count as reached, must be "
+                        "positive (got " + std::to_string(c) + ").");
+        mission.bScatterMaps = true;
+        mission.MapMinCount = (unsigned)c;
+        break;
+      }
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }
   }
-  // the views are made from the grid: none of their options means anything without it
-  if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile))
+  // the views and the maps are made from the grid: none of their options means anything without it
+  if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile || mission.bScatterMaps))
     throw Runtime(std::string(mission.bScatterViews ? "--scatter-views" : mission.bViewAzimuth ? "--scatter-view-azimuth"
-                                                                                                : "--no-scatter-grid-file") +
-                  " needs --scatter-grid: the views are projections of that grid.");
+                              : mission.bNoScatterGridFile ? "--no-scatter-grid-file" : "--scatter-maps") +
+                  " needs --scatter-grid: the views (--scatter-views, --scatter-view-azimuth, --no-scatter-grid-file) and the "
+                  "maps (--scatter-maps) are made from that grid.");
   if (mission.bNoScatterGridFile && !mission.bScatterViews)
     throw Runtime("--no-scatter-grid-file needs --scatter-views: without the views the run would leave nothing of its grid.");
   if (mission.bViewAzimuth && !mission.bScatterViews)

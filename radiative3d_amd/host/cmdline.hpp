@@ -44,6 +44,10 @@ struct MissionParams {
   bool bScatterViews = false, bViewAzimuth = false, bNoScatterGridFile = false;
   unsigned ViewGroup = 1;
   double ViewAzimuth = 0.0, ViewHalfWidth = 180.0;
+  // --scatter-maps[=MINCOUNT]: the grid reduced along time (include/r3d.h r3d_volume_time_maps) -- per cell the first
+  // frame with MINCOUNT events, the peak's frame and count, the total -- as scattermaps.octv and scattermaps_*.{u32,u64}
+  bool bScatterMaps = false;
+  unsigned MapMinCount = 1;
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

@@ -74,6 +74,23 @@ struct ScatterViewInfo {
 };
 void OutputScatterViewHeader(const ScatterViewInfo& v, std::ostream& out);
 
+// Header of the grid's maps along time (--scatter-maps; include/r3d.h r3d_volume_time_maps): per wave type and cell the
+// first frame with `min_count` events, the peak's frame and count, the total; and two stills of the first arrival, its
+// min over iz (from above) and over the columns of one range bin (in elevation: bins of width `dr` about `epicentre`,
+// columns outside azimuth +- half_width left out).  A frame index of MapNever = 4294967295 means "never"; the time
+// of frame f is (f + 1) * MapFrameSeconds.  The raw files are little-endian, x fastest -- in Octave:
+//   first = reshape(fread(fopen("<prefix>_first.u32"), Inf, "uint32"), MapDims(1), MapDims(2), MapDims(3), 2);
+struct ScatterMapsInfo {
+  unsigned dims[3], frames, min_count;
+  double frame_seconds, lo[3], hi[3];
+  unsigned n_range;
+  double dr, epicentre[2], azimuth, half_width;
+  std::string prefix;            // the raw files are <prefix>_first.u32, ... (kScatterMapFiles)
+};
+// suffixes of the raw files, in the order MapFiles lists them: [2][nz][ny][nx] x 4, then [2][ny][nx] and [2][nz][n_range]
+extern const char* const kScatterMapFiles[6];
+void OutputScatterMapsHeader(const ScatterMapsInfo& m, std::ostream& out);
+
 void OutputScatterGridHeader(const unsigned dims[3], unsigned frames, const double lo[3], const double hi[3],
                              double frame_dt, const std::string& raw_file, unsigned long long events_binned,
                              unsigned long long saturated_cells, std::ostream& out);

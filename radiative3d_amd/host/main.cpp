@@ -109,6 +109,9 @@ struct GridJob {
   bool views = false, raw_file = true;
   unsigned group = 1;
   double azimuth = 0.0, half_width = 180.0;
+  // --scatter-maps: the grid reduced along time (first arrival, peak, total per cell), written beside it
+  bool maps = false;
+  unsigned min_count = 1;
   std::string dir;
 };
 
@@ -129,6 +132,32 @@ void write_raw(const std::string& path, const void* data, size_t bytes) {
   }
 }
 
+// The column map of the elevation view and of the elevation still of the maps (include/r3d.h r3d_volume_range_bins):
+// epicentre = the model's source, dr = the smaller horizontal cell size, n_range = enough bins to reach the grid's
+// corner farthest from the epicentre; the azimuth filter of --scatter-view-azimuth where it was given.
+struct RangeMap {
+  double epi[2], dr;
+  uint32_t n_range;
+  std::vector<uint32_t> bin;   // [ny][nx]
+};
+RangeMap make_range_map(const GridJob& grid, const r3d_model_desc& d) {
+  const r3d_volume_desc& v = grid.desc;
+  RangeMap m;
+  m.epi[0] = d.source.loc[0], m.epi[1] = d.source.loc[1];
+  m.dr = std::min(v.cell_size[0], v.cell_size[1]);
+  double far = 0;
+  for (int cx = 0; cx < 2; cx++)
+    for (int cy = 0; cy < 2; cy++) {
+      const double dx = v.origin[0] + cx * v.cell_size[0] * v.dims[0] - m.epi[0];
+      const double dy = v.origin[1] + cy * v.cell_size[1] * v.dims[1] - m.epi[1];
+      far = std::max(far, std::sqrt(dx * dx + dy * dy));
+    }
+  m.n_range = (uint32_t)std::floor(far / m.dr) + 1;
+  m.bin.resize((size_t)v.dims[1] * v.dims[0]);
+  if (r3d_volume_range_bins(&v, m.epi, m.dr, m.n_range, grid.azimuth, grid.half_width, m.bin.data())) throw Runtime(r3d_last_error());
+  return m;
+}
+
 // --scatter-views: every engine projects the frames it owns (include/r3d.h r3d_volume_project_to_host), piece by
 // piece, cut where the job's groups of frames are cut; the pieces of a group that straddles two owners add up on
 // the host.  Epicentre = the model's source, dr = the smaller horizontal cell size, n_range = enough bins to reach
@@ -136,21 +165,14 @@ void write_raw(const std::string& path, const void* data, size_t bytes) {
 void write_scatter_views(const GridJob& grid, const r3d_model_desc& d, const std::vector<r3d_engine*>& engines,
                          const std::vector<int>& devices, const std::vector<uint32_t>& frames, uint64_t saturated) {
   const r3d_volume_desc& v = grid.desc;
-  const double epi[2] = {d.source.loc[0], d.source.loc[1]};
-  const double dr = std::min(v.cell_size[0], v.cell_size[1]);
-  double far = 0;
-  for (int cx = 0; cx < 2; cx++)
-    for (int cy = 0; cy < 2; cy++) {
-      const double dx = v.origin[0] + cx * v.cell_size[0] * v.dims[0] - epi[0];
-      const double dy = v.origin[1] + cy * v.cell_size[1] * v.dims[1] - epi[1];
-      far = std::max(far, std::sqrt(dx * dx + dy * dy));
-    }
-  const uint32_t n_range = (uint32_t)std::floor(far / dr) + 1;
+  const RangeMap range = make_range_map(grid, d);
+  const double* const epi = range.epi;
+  const double dr = range.dr;
+  const uint32_t n_range = range.n_range;
+  const std::vector<uint32_t>& map = range.bin;
   const uint32_t nx = v.dims[0], ny = v.dims[1], nz = v.dims[2], nf = v.n_frames;
   const uint32_t group = std::min<uint32_t>(grid.group, nf);
   const uint32_t n_out = (nf + group - 1) / group;
-  std::vector<uint32_t> map((size_t)ny * nx);
-  if (r3d_volume_range_bins(&v, epi, dr, n_range, grid.azimuth, grid.half_width, map.data())) throw Runtime(r3d_last_error());
   std::vector<uint64_t> above((size_t)2 * n_out * ny * nx, 0), elev((size_t)2 * n_out * nz * n_range, 0);
   uint64_t outside[2] = {0, 0};
   for (size_t g = 0; g < engines.size(); g++)
@@ -185,6 +207,52 @@ void write_scatter_views(const GridJob& grid, const r3d_model_desc& d, const std
   std::cout << "|  Scatter-event views: " << in_above << " events in " << n_out << " frames of " << group
             << " grid frames, from above " << nx << " x " << ny << ", in elevation " << n_range << " x " << nz << " ("
             << outside[0] + outside[1] << " events outside it; " << saturated << " grid cells at the 2^32 - 1 ceiling) -> " << grid.dir << "scatterview_{above,elev}.{octv,u64}\n";
+}
+
+// --scatter-maps: every engine's own frames go through r3d_volume_time_maps_to_host into ONE set of host maps (the
+// merge makes the owners' cut invisible); the two first-arrival stills are mins of `first` taken here, on the host.
+void write_scatter_maps(const GridJob& grid, const r3d_model_desc& d, const std::vector<r3d_engine*>& engines,
+                        const std::vector<int>& devices, const std::vector<uint32_t>& frames) {
+  const r3d_volume_desc& v = grid.desc;
+  const RangeMap range = make_range_map(grid, d);
+  const uint32_t nx = v.dims[0], ny = v.dims[1], nz = v.dims[2], n_range = range.n_range;
+  const size_t plane = (size_t)ny * nx, cells = (size_t)2 * nz * plane;
+  const uint32_t never = 0xFFFFFFFFu;
+  std::vector<uint32_t> first(cells, never), peak_frame(cells, never), peak_count(cells, 0);   // the neutral start
+  std::vector<uint64_t> total(cells, 0);
+  for (size_t g = 0; g < engines.size(); g++)
+    if (r3d_volume_time_maps_to_host(devices[g], static_cast<const uint32_t*>(r3d_volume_device_ptr(engines[g])), &v, frames[g],
+                                     frames[g + 1], grid.min_count, first.data(), peak_frame.data(), peak_count.data(), total.data()))
+      throw Runtime(r3d_last_error());
+  std::vector<uint32_t> above((size_t)2 * plane, never), elev((size_t)2 * nz * n_range, never);
+  unsigned long long reached = 0, events = 0;
+  for (size_t t = 0; t < 2; t++)
+    for (size_t iz = 0; iz < nz; iz++)
+      for (size_t c = 0; c < plane; c++) {
+        const size_t cell = (t * nz + iz) * plane + c;
+        const uint32_t f = first[cell], ir = range.bin[c];
+        events += total[cell];
+        if (f == never) continue;
+        reached++;
+        above[t * plane + c] = std::min(above[t * plane + c], f);
+        if (ir < n_range) elev[(t * nz + iz) * n_range + ir] = std::min(elev[(t * nz + iz) * n_range + ir], f);
+      }
+  const std::string prefix = "scattermaps";
+  const void* data[6] = {first.data(), peak_frame.data(), peak_count.data(), total.data(), above.data(), elev.data()};
+  const size_t bytes[6] = {cells * 4, cells * 4, cells * 4, cells * 8, above.size() * 4, elev.size() * 4};
+  for (int k = 0; k < 6; k++) write_raw(grid.dir + prefix + kScatterMapFiles[k], data[k], bytes[k]);
+  ScatterMapsInfo h;
+  for (int k = 0; k < 3; k++)
+    h.dims[k] = v.dims[k], h.lo[k] = v.origin[k], h.hi[k] = v.origin[k] + v.cell_size[k] * v.dims[k];
+  h.frames = v.n_frames, h.min_count = grid.min_count, h.frame_seconds = v.frame_dt;
+  h.n_range = n_range, h.dr = range.dr, h.epicentre[0] = range.epi[0], h.epicentre[1] = range.epi[1];
+  h.azimuth = grid.azimuth, h.half_width = grid.half_width, h.prefix = prefix;
+  std::ostringstream text;
+  OutputScatterMapsHeader(h, text);
+  write_raw(grid.dir + prefix + ".octv", text.str().data(), text.str().size());
+  std::cout << "|  Scatter-event maps: " << events << " events; " << reached << " of " << cells << " (wave type, cell) reached "
+            << grid.min_count << " events in a frame -> " << grid.dir << prefix << ".octv, " << prefix
+            << "_{first,peakframe,peakcount,first_above,first_elev}.u32, " << prefix << "_total.u64\n";
 }
 
 // A scatter grid is checked BEFORE the run (a 1e8-history job must not find out at its end that its grid
@@ -272,6 +340,7 @@ void run_simulation(const Model& model, uint64_t n, uint64_t seed, r3d_node* nod
     uint64_t saturated = 0;
     if (r3d_volume_reduce_by_frame(engines.data(), gpus, frames.data(), &saturated)) throw Runtime(r3d_last_error());
     if (grid.views) write_scatter_views(grid, d, engines, devices, frames, saturated);
+    if (grid.maps) write_scatter_maps(grid, d, engines, devices, frames);
     if (!grid.raw_file) return;
     const uint64_t fc = (uint64_t)grid.desc.dims[0] * grid.desc.dims[1] * grid.desc.dims[2], nf = grid.desc.n_frames;
     unsigned long long binned = 0;
@@ -337,6 +406,10 @@ int main(int argc, char* argv[]) {
               << "the grid's two video views made on the GPU, GROUP grid frames per frame -- the events from above (x, y) and in\n"
               << "elevation (range from the epicentre, z; only the columns within HALFWIDTH degrees of azimuth AZI) -- as\n"
               << "scatterview_above.{octv,u64} and scatterview_elev.{octv,u64}; the last option leaves the raw grid unwritten\n"
+              << "--scatter-maps[=MINCOUNT] (with --scatter-grid; default 1): the grid reduced along time on the GPU -- per wave type\n"
+              << "and cell the first frame with MINCOUNT events, the frame and count of the peak, the total -- as scattermaps.octv,\n"
+              << "scattermaps_{first,peakframe,peakcount}.u32, scattermaps_total.u64 and two first-arrival stills,\n"
+              << "scattermaps_first_{above,elev}.u32\n"
               << "--error-batches=B (2..64, one device): the histories run as B id-partitioned batches and every bin's\n"
               << "standard error is written to seis_NNN_err.octv beside seis_NNN.octv\n\n";
     return 0;
@@ -391,6 +464,7 @@ int main(int argc, char* argv[]) {
         grid.dir = dir;
         grid.views = mission.bScatterViews, grid.raw_file = !mission.bNoScatterGridFile, grid.group = mission.ViewGroup;
         grid.azimuth = mission.ViewAzimuth, grid.half_width = mission.ViewHalfWidth;
+        grid.maps = mission.bScatterMaps, grid.min_count = mission.MapMinCount;
         grid.raw_name = mission.ScatterGridFile + ".u32";
         grid.raw_path = dir + grid.raw_name, grid.header_path = dir + mission.ScatterGridFile + ".octv";
         check_grid_job(grid, devices.size());

@@ -230,6 +230,14 @@ class Model:
             return None
         return dict(group=int(group.value), azimuth=azi[0], half_width=azi[1], no_grid_file=bool(no_file.value))
 
+    @property
+    def scatter_maps(self):
+        """What --scatter-maps[=MINCOUNT] asked for: None, or the threshold MINCOUNT (default 1)."""
+        min_count = C.c_uint32(0)
+        if not self._lib.r3dh_scatter_maps(self._h, C.byref(min_count)):
+            return None
+        return int(min_count.value)
+
     def new_result(self):
         return Result(self.n_seismometers, self.n_bins)
 
@@ -420,6 +428,54 @@ def project_volume(counters, desc, frame_begin, frame_end, frame_group=1, range_
     if lib.r3d_volume_project(dev.index or 0, counters.data_ptr(), C.byref(desc), C.byref(views), stream):
         raise RuntimeError("r3d_volume_project failed: " + lib.r3d_last_error().decode())
     return a, e, o
+
+
+def neutral_time_maps(desc, device, first=True, peak=True, total=True):
+    """The maps of time_maps_volume in their neutral state (include/r3d.h): (first, peak_frame, peak_count, total), int32
+    device tensors [2][nz][ny][nx] holding uint32 bits -- first and peak_frame all 0xFFFFFFFF, peak_count 0 -- and an
+    int64 one for total, 0; None for a map not asked for."""
+    import torch
+    nx, ny, nz = (int(d) for d in desc.dims)
+    shape = (2, nz, ny, nx)
+    never = lambda: torch.full(shape, -1, dtype=torch.int32, device=device)   # noqa: E731
+    return (never() if first else None, never() if peak else None,
+            torch.zeros(shape, dtype=torch.int32, device=device) if peak else None,
+            torch.zeros(shape, dtype=torch.int64, device=device) if total else None)
+
+
+def time_maps_volume(counters, desc, frame_begin, frame_end, min_count=1, first=True, peak=True, total=True, outputs=None,
+                     stream=None):
+    """r3d_volume_time_maps on torch tensors: `counters` is a grid of the shape `desc` (a volume_desc) on a GPU, 32-bit.
+    Returns (first, peak_frame, peak_count, total) as neutral_time_maps() makes them, UPDATED with the frames
+    [frame_begin, frame_end): the first frame with min_count events, the frame and count of the peak, the sum (a map
+    not asked for is None).  `outputs`: the same four from an earlier call, to be brought up to date with this call's
+    frames; frames are absolute, pieces of a range in any order give the maps of one call.  Asynchronous on `stream`
+    (a raw hipStream_t; None: torch's current one).  include/r3d.h has the definition."""
+    import torch
+    lib = _ffi.hip_lib()
+    if not counters.is_cuda or not counters.is_contiguous() or counters.element_size() != 4:
+        raise ValueError("the grid must be a contiguous tensor of 32-bit counters on a GPU")
+    nx, ny, nz = (int(d) for d in desc.dims)
+    if counters.numel() != 2 * int(desc.n_frames) * nz * ny * nx:
+        raise ValueError("the grid does not have the description's size")
+    dev = counters.device
+    if outputs is None:
+        outputs = neutral_time_maps(desc, dev, first, peak, total)
+    fi, pf, pc, to = outputs
+    if (not first and fi is not None) or (not peak and (pf is not None or pc is not None)) or (not total and to is not None):
+        raise ValueError("`outputs` holds a map that this call does not ask for")
+    for t, dtype in ((fi, torch.int32), (pf, torch.int32), (pc, torch.int32), (to, torch.int64)):
+        if t is not None and (tuple(t.shape) != (2, nz, ny, nx) or t.dtype != dtype or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"a map to update must be a contiguous {dtype} tensor {(2, nz, ny, nx)} on the grid's GPU")
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    maps = _ffi.VolumeMaps(size=C.sizeof(_ffi.VolumeMaps), frame_begin=int(frame_begin), frame_end=int(frame_end),
+                           min_count=int(min_count), d_first=ptr(fi), d_peak_frame=ptr(pf), d_peak_count=ptr(pc),
+                           d_total=ptr(to))
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    if lib.r3d_volume_time_maps(dev.index or 0, counters.data_ptr(), C.byref(desc), C.byref(maps), stream):
+        raise RuntimeError("r3d_volume_time_maps failed: " + lib.r3d_last_error().decode())
+    return fi, pf, pc, to
 
 
 class Engine:

@@ -486,6 +486,20 @@ class DeviceVolume:
             raise RuntimeError(f"only frames {(lo, hi)} of this rank's grid hold job totals (reduce_scatter_frames_)")
         return project_volume(self.counters, self.desc, frame_begin, frame_end, frame_group, range_bin, n_range, above, outputs)
 
+    def time_maps(self, frame_begin=None, frame_end=None, min_count=1, first=True, peak=True, total=True, outputs=None):
+        """The grid reduced along time over frames [frame_begin, frame_end) (default: the frames this rank holds job
+        totals for): device tensors (first, peak_frame, peak_count, total) -- model.py time_maps_volume, include/r3d.h
+        r3d_volume_time_maps.  Frames outside `owned` are refused, as every read is."""
+        from .model import time_maps_volume
+        if self.owned == ():
+            self._valid_runs()
+        lo, hi = (0, self.n_frames) if self.owned is None else self.owned
+        frame_begin = lo if frame_begin is None else int(frame_begin)
+        frame_end = hi if frame_end is None else int(frame_end)
+        if frame_begin < frame_end and not (lo <= frame_begin and frame_end <= hi):
+            raise RuntimeError(f"only frames {(lo, hi)} of this rank's grid hold job totals (reduce_scatter_frames_)")
+        return time_maps_volume(self.counters, self.desc, frame_begin, frame_end, min_count, first, peak, total, outputs)
+
     def frames_numpy(self):
         """(lo, hi, counts[2][hi - lo][z][y][x]) of the frames this rank holds job totals for."""
         import numpy as np
