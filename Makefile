@@ -31,7 +31,7 @@ HIPFLAGS_SPH ?= -mllvm -amdgpu-sched-strategy=max-ilp
 LIBDIR   := radiative3d_amd/lib
 HOSTDIR  := radiative3d_amd/host
 CSRC     := radiative3d_amd/csrc
-STATSDIR := radiative3d_amd/stats
+COMMON   := radiative3d_amd/common
 
 HOST_SRC := $(HOSTDIR)/ecs.cpp $(HOSTDIR)/grid.cpp $(HOSTDIR)/model.cpp \
             $(HOSTDIR)/models_builtin.cpp $(HOSTDIR)/cmdline.cpp $(HOSTDIR)/dataout.cpp \
@@ -39,23 +39,27 @@ HOST_SRC := $(HOSTDIR)/ecs.cpp $(HOSTDIR)/grid.cpp $(HOSTDIR)/model.cpp \
 HOST_HDR := $(wildcard $(HOSTDIR)/*.hpp) include/r3d.h include/r3d_host.h
 ENGINE_SRC := $(CSRC)/r3d_engine.hip $(CSRC)/r3d_tables_build.hip $(CSRC)/r3d_kernels_kind.hip $(CSRC)/r3d_volume.hip
 ENGINE_HDR := $(wildcard $(CSRC)/*.h) include/r3d.h
-# per-bin standard errors from batches (r3d_batch_moments, r3d_run_device_batched): on top of the engine's C-ABI
-STATS_SRC := $(STATSDIR)/r3d_batch_stats.hip
-STATS_HDR := $(STATSDIR)/r3d_batch_moments.h include/r3d.h
-# the two video views of the scatter-event grid (r3d_volume_project, r3d_volume_range_bins): a device-level call
-VIEWSDIR  := radiative3d_amd/views
-VIEWS_SRC := $(VIEWSDIR)/r3d_volume_project.hip
-VIEWS_HDR := $(VIEWSDIR)/r3d_volume_views.h include/r3d.h
-# the grid reduced along its frame axis: arrival-time, peak and total maps (r3d_volume_time_maps): a device-level call
-MAPSDIR  := radiative3d_amd/maps
-MAPS_SRC := $(MAPSDIR)/r3d_volume_time_maps.hip
-MAPS_HDR := $(MAPSDIR)/r3d_volume_time_maps.h include/r3d.h
+# The add-ons: what stands beside the engine on its C-ABI, each a directory radiative3d_amd/<name>/ of ONE .hip and
+# its headers, which includes $(COMMON)/r3d_entry.h and include/r3d.h and nothing from csrc/.  A new one is a word here.
+#   stats  per-bin standard errors from batches (r3d_batch_moments, r3d_run_device_batched)
+#   views  the two video views of the scatter-event grid (r3d_volume_project, r3d_volume_range_bins)
+#   maps   the grid reduced along its frame axis: arrival-time, peak and total maps (r3d_volume_time_maps)
+ADDONS := stats views maps
+addon_src = $(wildcard radiative3d_amd/$(1)/*.hip)
+addon_hdr = $(wildcard radiative3d_amd/$(1)/*.h) $(COMMON)/r3d_entry.h include/r3d.h
 OBJDIR   := build/obj
 
 # (the default goal is the first target of the file: it has to come before the generated object rules)
 .PHONY: default all host engine repro oracle cli clean
 default: all
-# engine_objects(tag, extra flags): the nine objects of one engine build
+# addon_object(tag, extra flags, add-on): its object in one engine build
+define addon_object
+$(OBJDIR)/$(1)_$(3).o: $(call addon_src,$(3)) $(call addon_hdr,$(3))
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(call addon_src,$(3))
+
+endef
+# engine_objects(tag, extra flags): the objects of one engine build, six of the engine and one per add-on
 define engine_objects
 $(OBJDIR)/$(1)_engine.o: $(CSRC)/r3d_engine.hip $(ENGINE_HDR)
 	@mkdir -p $(OBJDIR)
@@ -63,7 +67,7 @@ $(OBJDIR)/$(1)_engine.o: $(CSRC)/r3d_engine.hip $(ENGINE_HDR)
 $(OBJDIR)/$(1)_tables.o: $(CSRC)/r3d_tables_build.hip $(ENGINE_HDR)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(CSRC)/r3d_tables_build.hip
-$(OBJDIR)/$(1)_volume.o: $(CSRC)/r3d_volume.hip $(ENGINE_HDR)
+$(OBJDIR)/$(1)_volume.o: $(CSRC)/r3d_volume.hip $(ENGINE_HDR) $(COMMON)/r3d_entry.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(CSRC)/r3d_volume.hip
 $(OBJDIR)/$(1)_cyl.o: $(CSRC)/r3d_kernels_kind.hip $(ENGINE_HDR)
@@ -75,17 +79,9 @@ $(OBJDIR)/$(1)_tet.o: $(CSRC)/r3d_kernels_kind.hip $(ENGINE_HDR)
 $(OBJDIR)/$(1)_sph.o: $(CSRC)/r3d_kernels_kind.hip $(ENGINE_HDR)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_SPH) $(2) -DR3D_KIND=2 -c -o $$@ $(CSRC)/r3d_kernels_kind.hip
-$(OBJDIR)/$(1)_stats.o: $(STATS_SRC) $(STATS_HDR)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(STATS_SRC)
-$(OBJDIR)/$(1)_views.o: $(VIEWS_SRC) $(VIEWS_HDR)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(VIEWS_SRC)
-$(OBJDIR)/$(1)_maps.o: $(MAPS_SRC) $(MAPS_HDR)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(MAPS_SRC)
+$(foreach a,$(ADDONS),$(call addon_object,$(1),$(2),$(a)))
 endef
-engine_objs = $(OBJDIR)/$(1)_stats.o $(OBJDIR)/$(1)_views.o $(OBJDIR)/$(1)_maps.o $(OBJDIR)/$(1)_engine.o $(OBJDIR)/$(1)_tables.o $(OBJDIR)/$(1)_volume.o $(OBJDIR)/$(1)_cyl.o $(OBJDIR)/$(1)_tet.o $(OBJDIR)/$(1)_sph.o
+engine_objs = $(foreach a,$(ADDONS),$(OBJDIR)/$(1)_$(a).o) $(OBJDIR)/$(1)_engine.o $(OBJDIR)/$(1)_tables.o $(OBJDIR)/$(1)_volume.o $(OBJDIR)/$(1)_cyl.o $(OBJDIR)/$(1)_tet.o $(OBJDIR)/$(1)_sph.o
 $(eval $(call engine_objects,main,))
 $(eval $(call engine_objects,repro,-DR3D_REPRODUCIBLE -ffp-contract=off))
 
@@ -144,18 +140,16 @@ clean:
 # an older object to be linked in its place.
 VOBJ = $(OBJDIR)/v$(NAME)
 VDEFS = -DR3D_DEV_BUILD $(DEFS)
+VOBJS = $(foreach o,engine tables volume cyl tet sph $(ADDONS),$(VOBJ)_$(o).o)
 variant:
 	@mkdir -p $(OBJDIR)
-	rm -f $(VOBJ)_engine.o $(VOBJ)_tables.o $(VOBJ)_volume.o $(VOBJ)_cyl.o $(VOBJ)_tet.o $(VOBJ)_sph.o $(VOBJ)_stats.o $(VOBJ)_views.o $(VOBJ)_maps.o $(LIBDIR)/variant_$(NAME).so
+	rm -f $(VOBJS) $(LIBDIR)/variant_$(NAME).so
 	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_engine.o $(CSRC)/r3d_engine.hip & p1=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_tables.o $(CSRC)/r3d_tables_build.hip & p2=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_volume.o $(CSRC)/r3d_volume.hip & p6=$$!; \
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_stats.o $(STATS_SRC) & p7=$$!; \
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_views.o $(VIEWS_SRC) & p8=$$!; \
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_maps.o $(MAPS_SRC) & p9=$$!; \
+	$(foreach a,$(ADDONS),$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_$(a).o $(call addon_src,$(a)) & p_$(a)=$$!;) \
 	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_CYL) $(VDEFS) $(DEFS_CYL) -DR3D_KIND=0 -c -o $(VOBJ)_cyl.o $(CSRC)/r3d_kernels_kind.hip & p3=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_TET) $(VDEFS) $(DEFS_TET) -DR3D_KIND=1 -c -o $(VOBJ)_tet.o $(CSRC)/r3d_kernels_kind.hip & p4=$$!; \
 	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_SPH) $(VDEFS) $(DEFS_SPH) -DR3D_KIND=2 -c -o $(VOBJ)_sph.o $(CSRC)/r3d_kernels_kind.hip & p5=$$!; \
-	rc=0; for p in $$p1 $$p2 $$p3 $$p4 $$p5 $$p6 $$p7 $$p8 $$p9; do wait $$p || rc=1; done; exit $$rc
-	$(HIPCC) --offload-arch=gfx950 -shared -pthread -o $(LIBDIR)/variant_$(NAME).so $(VOBJ)_engine.o \
-	    $(VOBJ)_tables.o $(VOBJ)_volume.o $(VOBJ)_cyl.o $(VOBJ)_tet.o $(VOBJ)_sph.o $(VOBJ)_stats.o $(VOBJ)_views.o $(VOBJ)_maps.o $(RCCL_LIBS)
+	rc=0; for p in $$p1 $$p2 $$p3 $$p4 $$p5 $$p6 $(foreach a,$(ADDONS),$$p_$(a)); do wait $$p || rc=1; done; exit $$rc
+	$(HIPCC) --offload-arch=gfx950 -shared -pthread -o $(LIBDIR)/variant_$(NAME).so $(VOBJS) $(RCCL_LIBS)

@@ -16,13 +16,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <string>
 
-#include "../../include/r3d.h"
+#include "../common/r3d_entry.h"
 
 namespace r3d {
-extern thread_local std::string g_error;
-
 namespace {
 
 constexpr int kCompactBlock = 256;
@@ -136,36 +133,30 @@ int r3d_volume_compact(int device, const uint32_t* d_counters, uint64_t begin, u
   if (end < begin) return g_error = "r3d_volume_compact: end before begin", 1;
   if (end > (uint64_t(1) << 32)) return g_error = "r3d_volume_compact: indices beyond 2^32 do not fit a pair", 1;
   if (end == begin) return 0;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) return g_error = "r3d_volume_compact: no HIP device", 1;
-  if (prev != device && hipSetDevice(device) != hipSuccess) return g_error = "r3d_volume_compact: bad device", 1;
+  OnDevice on(device);
+  if (const char* why = on.refusal()) return refuse("r3d_volume_compact", why);
   const uint64_t tiles = (end - begin + kTileCounters - 1) / kTileCounters;
   // (enough workgroups to keep every CU's memory pipeline full -- 8 x 256 threads per CU --, grid-stride beyond)
   const unsigned grid = (unsigned)(tiles < 2048 * 4 ? tiles : 2048 * 4);
   volume_compact_kernel<<<dim3(grid), dim3(kCompactBlock), 0, reinterpret_cast<hipStream_t>(stream)>>>(
       d_counters, begin, end, reinterpret_cast<uint2*>(d_pairs), capacity, reinterpret_cast<unsigned long long*>(d_n));
   const hipError_t err = hipGetLastError();
-  if (prev != device) (void)hipSetDevice(prev);
-  if (err != hipSuccess) return g_error = std::string("r3d_volume_compact: ") + hipGetErrorString(err), 1;
-  return 0;
+  return err == hipSuccess ? 0 : refuse("r3d_volume_compact", err);
 }
 
 int r3d_volume_scatter_add(int device, uint32_t* d_counters, uint64_t len, const uint32_t* d_pairs, uint64_t n,
                            uint64_t* d_flags, void* stream) {
   if (!d_counters || !d_flags || (n && !d_pairs)) return g_error = "r3d_volume_scatter_add: null argument", 1;
   if (n == 0) return 0;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) return g_error = "r3d_volume_scatter_add: no HIP device", 1;
-  if (prev != device && hipSetDevice(device) != hipSuccess) return g_error = "r3d_volume_scatter_add: bad device", 1;
+  OnDevice on(device);
+  if (const char* why = on.refusal()) return refuse("r3d_volume_scatter_add", why);
   const uint64_t blocks = (n + 255) / 256;
   const unsigned grid = (unsigned)(blocks < 2048 * 8 ? blocks : 2048 * 8);
   unsigned long long* flags = reinterpret_cast<unsigned long long*>(d_flags);
   volume_scatter_add_kernel<<<dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream)>>>(
       d_counters, len, reinterpret_cast<const uint2*>(d_pairs), n, flags, flags + 1);
   const hipError_t err = hipGetLastError();
-  if (prev != device) (void)hipSetDevice(prev);
-  if (err != hipSuccess) return g_error = std::string("r3d_volume_scatter_add: ") + hipGetErrorString(err), 1;
-  return 0;
+  return err == hipSuccess ? 0 : refuse("r3d_volume_scatter_add", err);
 }
 
 }  // extern "C"

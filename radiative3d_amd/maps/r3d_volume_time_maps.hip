@@ -17,15 +17,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <string>
 #include <vector>
 
-#include "../../include/r3d.h"
+#include "../common/r3d_entry.h"
 #include "r3d_volume_time_maps.h"
 
 namespace r3d {
-extern thread_local std::string g_error;
-
 namespace {
 
 constexpr int kMapsBlock = 256;
@@ -143,13 +140,9 @@ __global__ __launch_bounds__(kMapsBlock) void volume_time_maps_kernel(const uint
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // what both calls refuse on the frame range and the threshold alone
 const char* bad_range(const r3d_volume_desc* v, uint32_t frame_begin, uint32_t frame_end, uint32_t min_count) {
-  if (v->dims[0] == 0 || v->dims[1] == 0 || v->dims[2] == 0) return "empty grid";
-  if (frame_begin > frame_end) return "frame_end before frame_begin";
-  if (frame_end > v->n_frames) return "frame_end beyond the grid's frames";
+  if (const char* why = bad_frame_range(v, frame_begin, frame_end)) return why;
   if (min_count == 0) return "min_count 0 (the threshold of `first` is at least one event)";
   return nullptr;
 }
@@ -166,8 +159,7 @@ int r3d_volume_time_maps(int device, const uint32_t* d_counters, const r3d_volum
   if (!d_counters || !v || !m) return g_error = "r3d_volume_time_maps: null grid, description or maps", 1;
   if (m->size != sizeof(r3d_volume_maps))
     return g_error = "r3d_volume_time_maps: r3d_volume_maps.size is not this library's sizeof(r3d_volume_maps)", 1;
-  if (const char* why = bad_range(v, m->frame_begin, m->frame_end, m->min_count))
-    return g_error = std::string("r3d_volume_time_maps: ") + why, 1;
+  if (const char* why = bad_range(v, m->frame_begin, m->frame_end, m->min_count)) return refuse("r3d_volume_time_maps", why);
   if (!m->d_first && !m->d_peak_frame && !m->d_peak_count && !m->d_total)
     return g_error = "r3d_volume_time_maps: no map asked for", 1;
   if (!m->d_peak_frame != !m->d_peak_count)
@@ -176,18 +168,15 @@ int r3d_volume_time_maps(int device, const uint32_t* d_counters, const r3d_volum
   const uint64_t n_blocks = (p.n_quads + kMapsBlock - 1) / kMapsBlock;
   if (n_blocks > 0x7FFFFFFFull) return g_error = "r3d_volume_time_maps: too many cells for one launch", 1;
   if (m->frame_begin == m->frame_end) return 0;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) return g_error = "r3d_volume_time_maps: no HIP device", 1;
-  if (prev != device && hipSetDevice(device) != hipSuccess) return g_error = "r3d_volume_time_maps: bad device", 1;
+  OnDevice on(device);
+  if (const char* why = on.refusal()) return refuse("r3d_volume_time_maps", why);
   const bool quads = p.nx % 4 == 0 && aligned16(d_counters) && aligned16(m->d_first) && aligned16(m->d_peak_frame) &&
                      aligned16(m->d_peak_count) && aligned16(m->d_total);
   const auto kernel = quads ? volume_time_maps_kernel<true> : volume_time_maps_kernel<false>;
   kernel<<<dim3((unsigned)n_blocks), dim3(kMapsBlock), 0, reinterpret_cast<hipStream_t>(stream)>>>(
       d_counters, p, m->d_first, m->d_peak_frame, m->d_peak_count, reinterpret_cast<ull*>(m->d_total));
   const hipError_t err = hipGetLastError();
-  if (prev != device) (void)hipSetDevice(prev);
-  if (err != hipSuccess) return g_error = std::string("r3d_volume_time_maps: ") + hipGetErrorString(err), 1;
-  return 0;
+  return err == hipSuccess ? 0 : refuse("r3d_volume_time_maps", err);
 }
 
 // The same for a host that holds no device memory of its own (./main): scratch maps on the device at the neutral
@@ -195,49 +184,38 @@ int r3d_volume_time_maps(int device, const uint32_t* d_counters, const r3d_volum
 int r3d_volume_time_maps_to_host(int device, const uint32_t* d_counters, const r3d_volume_desc* v, uint32_t frame_begin,
                                  uint32_t frame_end, uint32_t min_count, uint32_t* first, uint32_t* peak_frame,
                                  uint32_t* peak_count, uint64_t* total) {
+  const char* const who = "r3d_volume_time_maps_to_host";
   if (!d_counters || !v) return g_error = "r3d_volume_time_maps_to_host: null grid or description", 1;
-  if (const char* why = bad_range(v, frame_begin, frame_end, min_count))
-    return g_error = std::string("r3d_volume_time_maps_to_host: ") + why, 1;
+  if (const char* why = bad_range(v, frame_begin, frame_end, min_count)) return refuse(who, why);
   if (!first && !peak_frame && !peak_count && !total) return g_error = "r3d_volume_time_maps_to_host: no map asked for", 1;
   if (!peak_frame != !peak_count)
     return g_error = "r3d_volume_time_maps_to_host: the peak's frame and count go together (both or neither)", 1;
   if (frame_begin == frame_end) return 0;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) return g_error = "r3d_volume_time_maps_to_host: no HIP device", 1;
-  if (prev != device && hipSetDevice(device) != hipSuccess) return g_error = "r3d_volume_time_maps_to_host: bad device", 1;
+  OnDevice on(device);
+  if (const char* why = on.refusal()) return refuse(who, why);
   const uint64_t n = 2ull * v->dims[2] * v->dims[1] * v->dims[0];     // cells of a map
   const uint64_t n4 = (n + 3) / 4 * 4;                                 // (every scratch map starts 16-byte aligned)
   // scratch: total [n4] uint64 | first, peak_frame, peak_count [n4] uint32 each
   const uint64_t bytes = n4 * (sizeof(uint64_t) + 3 * sizeof(uint32_t));
-  char* d_all = nullptr;
-  std::string err;
-  auto check = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && err.empty()) err = std::string("r3d_volume_time_maps_to_host: ") + what + ": " + hipGetErrorString(e);
-    return err.empty();
-  };
-  std::vector<uint64_t> h_total;
-  std::vector<uint32_t> h_u32;
-  if (check(hipMalloc(reinterpret_cast<void**>(&d_all), bytes), "maps on the device") &&
-      check(hipMemset(d_all, 0, n4 * sizeof(uint64_t)), "the neutral start of the maps") &&
-      check(hipMemset(d_all + n4 * sizeof(uint64_t), 0xFF, 2 * n4 * sizeof(uint32_t)), "the neutral start of the maps") &&
-      check(hipMemset(d_all + n4 * (sizeof(uint64_t) + 2 * sizeof(uint32_t)), 0, n4 * sizeof(uint32_t)), "the neutral start of the maps")) {
-    uint32_t* const d_u32 = reinterpret_cast<uint32_t*>(d_all + n4 * sizeof(uint64_t));
-    r3d_volume_maps m{};
-    m.size = sizeof(m), m.frame_begin = frame_begin, m.frame_end = frame_end, m.min_count = min_count;
-    m.d_total = total ? reinterpret_cast<uint64_t*>(d_all) : nullptr;
-    m.d_first = first ? d_u32 : nullptr;
-    m.d_peak_frame = peak_count ? d_u32 + n4 : nullptr, m.d_peak_count = peak_count ? d_u32 + 2 * n4 : nullptr;
-    if (r3d_volume_time_maps(device, d_counters, v, &m, nullptr)) {
-      err = g_error;
-    } else {
-      h_total.resize(n4), h_u32.resize(3 * n4);
-      check(hipMemcpy(h_total.data(), d_all, n4 * sizeof(uint64_t), hipMemcpyDeviceToHost), "reading the maps") &&   // (waits for the launch)
-          check(hipMemcpy(h_u32.data(), d_u32, 3 * n4 * sizeof(uint32_t), hipMemcpyDeviceToHost), "reading the maps");
-    }
-  }
-  if (d_all) (void)hipFree(d_all);
-  if (prev != device) (void)hipSetDevice(prev);
-  if (!err.empty()) return g_error = err, 1;
+  DeviceBuffer all;
+  if (hipError_t e = all.alloc(bytes); e != hipSuccess) return refuse(who, e, "maps on the device");
+  char* const d_all = all.as<char>();
+  uint32_t* const d_u32 = reinterpret_cast<uint32_t*>(d_all + n4 * sizeof(uint64_t));
+  hipError_t e = hipMemset(d_all, 0, n4 * sizeof(uint64_t));
+  if (e == hipSuccess) e = hipMemset(d_u32, 0xFF, 2 * n4 * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemset(d_u32 + 2 * n4, 0, n4 * sizeof(uint32_t));
+  if (e != hipSuccess) return refuse(who, e, "the neutral start of the maps");
+  r3d_volume_maps m{};
+  m.size = sizeof(m), m.frame_begin = frame_begin, m.frame_end = frame_end, m.min_count = min_count;
+  m.d_total = total ? reinterpret_cast<uint64_t*>(d_all) : nullptr;
+  m.d_first = first ? d_u32 : nullptr;
+  m.d_peak_frame = peak_count ? d_u32 + n4 : nullptr, m.d_peak_count = peak_count ? d_u32 + 2 * n4 : nullptr;
+  if (r3d_volume_time_maps(device, d_counters, v, &m, nullptr)) return 1;   // (its message stands)
+  std::vector<uint64_t> h_total(n4);
+  std::vector<uint32_t> h_u32(3 * n4);
+  e = hipMemcpy(h_total.data(), d_all, n4 * sizeof(uint64_t), hipMemcpyDeviceToHost);   // (waits for the launch)
+  if (e == hipSuccess) e = hipMemcpy(h_u32.data(), d_u32, 3 * n4 * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return refuse(who, e, "reading the maps");
   for (uint64_t i = 0; i < n; i++) {
     maps::State a = maps::neutral();
     if (first) a.first = first[i];

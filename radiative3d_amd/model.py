@@ -382,6 +382,16 @@ def range_bins(desc, epicentre, dr, n_range, azimuth_deg=0.0, half_width_deg=180
     return out
 
 
+def _grid_shape(counters, desc):
+    """(nx, ny, nz, device) of a grid tensor, held against its description (a volume_desc)."""
+    if not counters.is_cuda or not counters.is_contiguous() or counters.element_size() != 4:
+        raise ValueError("the grid must be a contiguous tensor of 32-bit counters on a GPU")
+    nx, ny, nz = (int(d) for d in desc.dims)
+    if counters.numel() != 2 * int(desc.n_frames) * nz * ny * nx:
+        raise ValueError("the grid does not have the description's size")
+    return nx, ny, nz, counters.device
+
+
 def project_volume(counters, desc, frame_begin, frame_end, frame_group=1, range_bin=None, n_range=0, above=True,
                    outputs=None, stream=None):
     """r3d_volume_project on torch tensors: `counters` is a grid of the shape `desc` (a volume_desc) on a GPU, 32-bit.
@@ -392,12 +402,7 @@ def project_volume(counters, desc, frame_begin, frame_end, frame_group=1, range_
     current one).  include/r3d.h has the definition of the views."""
     import torch
     lib = _ffi.hip_lib()
-    if not counters.is_cuda or not counters.is_contiguous() or counters.element_size() != 4:
-        raise ValueError("the grid must be a contiguous tensor of 32-bit counters on a GPU")
-    nx, ny, nz = (int(d) for d in desc.dims)
-    if counters.numel() != 2 * int(desc.n_frames) * nz * ny * nx:
-        raise ValueError("the grid does not have the description's size")
-    dev = counters.device
+    nx, ny, nz, dev = _grid_shape(counters, desc)
     n_out = max(0, -(-(int(frame_end) - int(frame_begin)) // max(1, int(frame_group))))
     elev_on = range_bin is not None
     if elev_on and not torch.is_tensor(range_bin):
@@ -453,12 +458,7 @@ def time_maps_volume(counters, desc, frame_begin, frame_end, min_count=1, first=
     (a raw hipStream_t; None: torch's current one).  include/r3d.h has the definition."""
     import torch
     lib = _ffi.hip_lib()
-    if not counters.is_cuda or not counters.is_contiguous() or counters.element_size() != 4:
-        raise ValueError("the grid must be a contiguous tensor of 32-bit counters on a GPU")
-    nx, ny, nz = (int(d) for d in desc.dims)
-    if counters.numel() != 2 * int(desc.n_frames) * nz * ny * nx:
-        raise ValueError("the grid does not have the description's size")
-    dev = counters.device
+    nx, ny, nz, dev = _grid_shape(counters, desc)
     if outputs is None:
         outputs = neutral_time_maps(desc, dev, first, peak, total)
     fi, pf, pc, to = outputs

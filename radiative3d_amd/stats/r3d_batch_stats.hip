@@ -16,12 +16,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/r3d.h"
+#include "../common/r3d_entry.h"
 #include "r3d_batch_moments.h"
 
 namespace r3d {
-extern thread_local std::string g_error;   // (csrc/r3d_engine.hip: what r3d_last_error returns)
-
 namespace {
 
 constexpr int kMomentsBlock = 256;
@@ -61,31 +59,6 @@ unsigned moments_grid(uint64_t len) {
   // (enough workgroups to keep every CU's memory pipeline busy -- 256 CUs x 8 x 256 work-items --, grid-stride beyond)
   const uint64_t blocks = (len + kMomentsBlock - 1) / kMomentsBlock;
   return (unsigned)(blocks < 2048 ? blocks : 2048);
-}
-
-// The caller's current device kept across an entry point (as the engine's own entry points do).
-struct OnDevice {
-  int prev = -1;
-  hipError_t status;
-  explicit OnDevice(int device) {
-    status = hipGetDevice(&prev);
-    if (status != hipSuccess) {
-      prev = -1;
-      return;
-    }
-    if (prev == device) prev = -1;
-    else status = hipSetDevice(device);
-  }
-  ~OnDevice() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  OnDevice(const OnDevice&) = delete;
-  OnDevice& operator=(const OnDevice&) = delete;
-};
-
-int fail(const char* where, hipError_t err) {
-  g_error = std::string(where) + ": " + hipGetErrorString(err);
-  return 1;
 }
 
 // The streams the batches overlap on and the events that tie them to the caller's stream: made once per device,
@@ -148,29 +121,27 @@ int enqueue_moments(uint32_t n_batches, const double* d_batch_energy, uint64_t n
     batch_moments_u64_kernel<<<dim3(moments_grid(n_scalars)), dim3(kMomentsBlock), 0, s>>>(d_batch_scalars, n_scalars, n_batches,
                                                                                         d_scalars, nullptr);
   const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : fail("r3d_batch_moments", err);
+  return err == hipSuccess ? 0 : refuse("r3d_batch_moments", err);
 }
 
 // What a batched run cannot be combined with, asked of the engine through its public calls.
 int refuse_engine_state(r3d_engine* e, const char* who) {
   if (r3d_engine_carry_pending(e))
-    return g_error = std::string(who) + ": histories carried over by r3d_run_device_carry await their flush; a batch must be a "
-                     "self-contained launch", 1;
+    return refuse(who, "histories carried over by r3d_run_device_carry await their flush; a batch must be a self-contained launch");
   if (r3d_event_log_read(e, nullptr, 0, 0) != ~uint64_t(0))
-    return g_error = std::string(who) + ": an event log is attached (its launches run the diagnostic kernel, one at a time); "
-                     "detach it first", 1;
+    return refuse(who, "an event log is attached (its launches run the diagnostic kernel, one at a time); detach it first");
   if (r3d_production_finals_read(e, nullptr, 0, 0) == 0)
-    return g_error = std::string(who) + ": a production-finals buffer is attached; detach it first", 1;
+    return refuse(who, "a production-finals buffer is attached; detach it first");
   return 0;
 }
 
 int check_batches(const char* who, uint64_t n, uint32_t n_batches) {
   if (n_batches < 2)
-    return g_error = std::string(who) + ": at least 2 batches are needed for a variance (got " + std::to_string(n_batches) + ")", 1;
+    return refuse(who, "at least 2 batches are needed for a variance (got " + std::to_string(n_batches) + ")");
   if (n_batches > kMaxBatches)
-    return g_error = std::string(who) + ": at most 64 batches (the engine's launches in flight), got " + std::to_string(n_batches), 1;
+    return refuse(who, "at most 64 batches (the engine's launches in flight), got " + std::to_string(n_batches));
   if (n < n_batches)
-    return g_error = std::string(who) + ": fewer histories (" + std::to_string(n) + ") than batches (" + std::to_string(n_batches) + ")", 1;
+    return refuse(who, "fewer histories (" + std::to_string(n) + ") than batches (" + std::to_string(n_batches) + ")");
   return 0;
 }
 
@@ -191,7 +162,7 @@ int r3d_batch_moments(int device, uint32_t n_batches, const double* d_batch_ener
       (d_batch_scalars && n_scalars && !d_scalars))
     return g_error = "r3d_batch_moments: null argument", 1;
   OnDevice on(device);
-  if (on.status != hipSuccess) return g_error = "r3d_batch_moments: no HIP device (or a bad device index)", 1;
+  if (on.status != hipSuccess) return refuse("r3d_batch_moments", "no HIP device (or a bad device index)");
   return enqueue_moments(n_batches, d_batch_energy, n_energy, d_batch_counts, n_counts, d_batch_scalars, n_scalars, d_energy,
                          d_counts, d_scalars, d_energy_se, d_counts_se, reinterpret_cast<hipStream_t>(stream));
 }
@@ -205,21 +176,21 @@ int r3d_run_device_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_
   if (check_batches(who, n, n_batches)) return 1;
   if (refuse_engine_state(e, who)) return 1;
   const int device = device_of(d_energy);
-  if (device < 0) return g_error = std::string(who) + ": d_energy is not device memory", 1;
+  if (device < 0) return refuse(who, "d_energy is not device memory");
   OnDevice on(device);
-  if (on.status != hipSuccess) return fail(who, on.status);
+  if (on.status != hipSuccess) return refuse(who, on.status);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint64_t ne = r3d_energy_len(e), nc = r3d_counts_len(e), ns = R3D_N_SCALARS, B = n_batches;
 
   std::lock_guard<std::mutex> lock(g_lanes_lock);
   Lanes* lanes = nullptr;
-  if (hipError_t err = lanes_for(device, &lanes); err != hipSuccess) return fail(who, err);
+  if (hipError_t err = lanes_for(device, &lanes); err != hipSuccess) return refuse(who, err);
 
   // the batches' blocks: the caller's, or scratch that lives in stream order from here to behind the moments kernel
   // (the scalars' blocks are always scratch); every block starts from zero
   const uint64_t own_e = d_batch_energy ? 0 : B * ne, own_c = d_batch_counts ? 0 : B * nc;
   void* scratch = nullptr;
-  if (hipError_t err = hipMallocAsync(&scratch, (own_e + own_c + B * ns) * 8, s); err != hipSuccess) return fail(who, err);
+  if (hipError_t err = hipMallocAsync(&scratch, (own_e + own_c + B * ns) * 8, s); err != hipSuccess) return refuse(who, err);
   uint64_t* const bs = reinterpret_cast<uint64_t*>(scratch);
   double* const be = d_batch_energy ? d_batch_energy : reinterpret_cast<double*>(bs + B * ns);
   uint64_t* const bc = d_batch_counts ? d_batch_counts : bs + B * ns + own_e;
@@ -228,7 +199,7 @@ int r3d_run_device_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_
   if (err == hipSuccess && d_batch_counts && nc) err = hipMemsetAsync(bc, 0, B * nc * 8, s);
   if (err == hipSuccess) err = hipEventRecord(lanes->begin, s);
   for (int k = 0; k < kStreams && err == hipSuccess; k++) err = hipStreamWaitEvent(lanes->stream[k], lanes->begin, 0);
-  int rc = err == hipSuccess ? 0 : fail(who, err);
+  int rc = err == hipSuccess ? 0 : refuse(who, err);
   // batch j: ids [first_id + floor(j n / B), first_id + floor((j + 1) n / B)), round-robin over the streams so that a
   // batch's drain phase overlaps the batches behind it
   for (uint64_t j = 0; j < B && rc == 0; j++) {
@@ -240,11 +211,11 @@ int r3d_run_device_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_
   for (int k = 0; k < kStreams; k++) {
     hipError_t j = hipEventRecord(lanes->done[k], lanes->stream[k]);
     if (j == hipSuccess) j = hipStreamWaitEvent(s, lanes->done[k], 0);
-    if (j != hipSuccess && rc == 0) rc = fail(who, j);
+    if (j != hipSuccess && rc == 0) rc = refuse(who, j);
   }
   if (rc == 0)
     rc = enqueue_moments(n_batches, be, ne, bc, nc, bs, ns, d_energy, d_counts, d_scalars, d_energy_se, d_counts_se, s);
-  if (hipError_t f = hipFreeAsync(scratch, s); f != hipSuccess && rc == 0) rc = fail(who, f);
+  if (hipError_t f = hipFreeAsync(scratch, s); f != hipSuccess && rc == 0) rc = refuse(who, f);
   return rc;
 }
 
@@ -268,15 +239,15 @@ int r3d_run_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed,
     device = device_of(r3d_volume_device_ptr(e));
     if (r3d_engine_set_volume(e, nullptr)) return 1;
   }
-  if (device < 0) return g_error = std::string(who) + ": the engine's device could not be determined", 1;
+  if (device < 0) return refuse(who, "the engine's device could not be determined");
   OnDevice on(device);
-  if (on.status != hipSuccess) return fail(who, on.status);
+  if (on.status != hipSuccess) return refuse(who, on.status);
   const size_t ne = r3d_energy_len(e), nc = r3d_counts_len(e), ns = R3D_N_SCALARS;
   // one block: totals (energy, counts, scalars), then the two se arrays
-  void* block = nullptr;
+  DeviceBuffer block;
   const size_t words = 2 * ne + 2 * nc + ns;
-  if (hipError_t err = hipMalloc(&block, words * 8); err != hipSuccess) return fail(who, err);
-  double* const d_e = reinterpret_cast<double*>(block);
+  if (hipError_t err = block.alloc(words * 8); err != hipSuccess) return refuse(who, err);
+  double* const d_e = block.as<double>();
   uint64_t* const d_c = reinterpret_cast<uint64_t*>(d_e + ne);
   uint64_t* const d_s = d_c + nc;
   double* const d_ese = reinterpret_cast<double*>(d_s + ns);
@@ -284,16 +255,15 @@ int r3d_run_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed,
   std::vector<uint64_t> host(words);
   hipStream_t s = nullptr;
   hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-  if (err == hipSuccess) err = hipMemsetAsync(block, 0, words * 8, s);
-  int rc = err == hipSuccess ? 0 : fail(who, err);
+  if (err == hipSuccess) err = hipMemsetAsync(block.p, 0, words * 8, s);
+  int rc = err == hipSuccess ? 0 : refuse(who, err);
   if (rc == 0) rc = r3d_run_device_batched(e, n, first_id, seed, n_batches, d_e, d_c, d_s, d_ese, d_cse, nullptr, nullptr, s);
   if (s) {   // (also after a refusal: what was enqueued reads the block)
     err = hipStreamSynchronize(s);
-    if (err == hipSuccess && rc == 0) err = hipMemcpy(host.data(), block, words * 8, hipMemcpyDeviceToHost);
-    if (err != hipSuccess && rc == 0) rc = fail(who, err);
+    if (err == hipSuccess && rc == 0) err = hipMemcpy(host.data(), block.p, words * 8, hipMemcpyDeviceToHost);
+    if (err != hipSuccess && rc == 0) rc = refuse(who, err);
     (void)hipStreamDestroy(s);
   }
-  (void)hipFree(block);
   if (rc) return rc;
   const double* const he = reinterpret_cast<const double*>(host.data());
   const uint64_t* const hc = host.data() + ne;

@@ -15,15 +15,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <string>
 #include <vector>
 
-#include "../../include/r3d.h"
+#include "../common/r3d_entry.h"
 #include "r3d_volume_views.h"
 
 namespace r3d {
-extern thread_local std::string g_error;
-
 namespace {
 
 constexpr int kProjectBlock = 512;
@@ -158,9 +155,7 @@ int r3d_volume_project(int device, const uint32_t* d_counters, const r3d_volume_
   if (!d_counters || !v || !views) return g_error = "r3d_volume_project: null grid, description or views", 1;
   if (views->size != sizeof(r3d_volume_views))
     return g_error = "r3d_volume_project: r3d_volume_views.size is not this library's sizeof(r3d_volume_views)", 1;
-  if (v->dims[0] == 0 || v->dims[1] == 0 || v->dims[2] == 0) return g_error = "r3d_volume_project: empty grid", 1;
-  if (views->frame_begin > views->frame_end) return g_error = "r3d_volume_project: frame_end before frame_begin", 1;
-  if (views->frame_end > v->n_frames) return g_error = "r3d_volume_project: frame_end beyond the grid's frames", 1;
+  if (const char* why = bad_frame_range(v, views->frame_begin, views->frame_end)) return refuse("r3d_volume_project", why);
   if (views->frame_group == 0) return g_error = "r3d_volume_project: frame_group 0", 1;
   if (!views->d_above && !views->d_elev) return g_error = "r3d_volume_project: neither view asked for", 1;
   if (views->d_elev && (!views->d_range_bin || views->n_range == 0))
@@ -174,11 +169,9 @@ int r3d_volume_project(int device, const uint32_t* d_counters, const r3d_volume_
                                          views->frame_end, views->frame_group, views->d_elev ? views->n_range : 0u,
                                          kTargetBlocks, kProjectBlock);
   if (views::n_blocks(p) > 0x7FFFFFFFull) return g_error = "r3d_volume_project: too many output frames for one launch", 1;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) return g_error = "r3d_volume_project: no HIP device", 1;
-  if (prev != device && hipSetDevice(device) != hipSuccess) return g_error = "r3d_volume_project: bad device", 1;
-  const bool quads = p.nx % 4 == 0 && (reinterpret_cast<uintptr_t>(d_counters) & 15u) == 0 &&
-                     (!views->d_elev || (reinterpret_cast<uintptr_t>(views->d_range_bin) & 15u) == 0);
+  OnDevice on(device);
+  if (const char* why = on.refusal()) return refuse("r3d_volume_project", why);
+  const bool quads = p.nx % 4 == 0 && aligned16(d_counters) && (!views->d_elev || aligned16(views->d_range_bin));
   const auto kernel = quads ? volume_project_kernel<true> : volume_project_kernel<false>;
   const uint64_t hist_bytes = views->d_elev ? (uint64_t)p.nz * p.n_range * sizeof(uint32_t) : 0;
   const uint32_t lds = hist_bytes && hist_bytes <= kLdsMost ? (uint32_t)hist_bytes : 0u;
@@ -191,9 +184,7 @@ int r3d_volume_project(int device, const uint32_t* d_counters, const r3d_volume_
         reinterpret_cast<ull*>(views->d_outside), lds);
     err = hipGetLastError();
   }
-  if (prev != device) (void)hipSetDevice(prev);
-  if (err != hipSuccess) return g_error = std::string("r3d_volume_project: ") + hipGetErrorString(err), 1;
-  return 0;
+  return err == hipSuccess ? 0 : refuse("r3d_volume_project", err);
 }
 
 // The same for a host that holds no device memory of its own (./main): scratch views on the device, projected,
@@ -212,41 +203,31 @@ int r3d_volume_project_to_host(int device, const uint32_t* d_counters, const r3d
   const uint32_t n_out = views::n_out_frames(frame_begin, frame_end, frame_group);
   if ((uint64_t)out_frame0 + n_out > n_out_total)
     return g_error = "r3d_volume_project_to_host: the output frames do not fit the host's views", 1;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) return g_error = "r3d_volume_project_to_host: no HIP device", 1;
-  if (prev != device && hipSetDevice(device) != hipSuccess) return g_error = "r3d_volume_project_to_host: bad device", 1;
+  const char* const who = "r3d_volume_project_to_host";
+  OnDevice on(device);
+  if (const char* why = on.refusal()) return refuse(who, why);
   const uint64_t nx = v->dims[0], ny = v->dims[1], nz = v->dims[2];
   const uint64_t per_above = ny * nx, per_elev = nz * n_range;   // per (type, output frame)
   const uint64_t n_above = above ? 2 * n_out * per_above : 0, n_elev = elev ? 2 * n_out * per_elev : 0;
   const uint64_t n_all = n_above + n_elev + 2;
-  uint64_t* d_all = nullptr;
-  uint32_t* d_map = nullptr;
-  std::string err;
-  auto check = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && err.empty()) err = std::string("r3d_volume_project_to_host: ") + what + ": " + hipGetErrorString(e);
-    return err.empty();
-  };
-  std::vector<uint64_t> host;
-  if (check(hipMalloc(reinterpret_cast<void**>(&d_all), n_all * sizeof(uint64_t)), "views on the device") &&
-      check(hipMemset(d_all, 0, n_all * sizeof(uint64_t)), "zeroing the views") &&
-      (!elev || (check(hipMalloc(reinterpret_cast<void**>(&d_map), per_above * sizeof(uint32_t)), "column map on the device") &&
-                 check(hipMemcpy(d_map, range_bin, per_above * sizeof(uint32_t), hipMemcpyHostToDevice), "column map upload")))) {
-    r3d_volume_views vw{};
-    vw.size = sizeof(vw), vw.frame_begin = frame_begin, vw.frame_end = frame_end, vw.frame_group = frame_group;
-    vw.n_range = elev ? n_range : 0, vw.d_range_bin = d_map;
-    vw.d_above = above ? d_all : nullptr, vw.d_elev = elev ? d_all + n_above : nullptr;
-    vw.d_outside = elev ? d_all + n_above + n_elev : nullptr;
-    if (r3d_volume_project(device, d_counters, v, &vw, nullptr)) {
-      err = g_error;
-    } else {
-      host.resize(n_all);
-      check(hipMemcpy(host.data(), d_all, n_all * sizeof(uint64_t), hipMemcpyDeviceToHost), "reading the views");   // (waits for the launch)
-    }
+  DeviceBuffer map, all;
+  if (hipError_t e = all.alloc(n_all * sizeof(uint64_t)); e != hipSuccess) return refuse(who, e, "views on the device");
+  if (hipError_t e = hipMemset(all.p, 0, n_all * sizeof(uint64_t)); e != hipSuccess) return refuse(who, e, "zeroing the views");
+  if (elev) {
+    if (hipError_t e = map.alloc(per_above * sizeof(uint32_t)); e != hipSuccess) return refuse(who, e, "column map on the device");
+    if (hipError_t e = hipMemcpy(map.p, range_bin, per_above * sizeof(uint32_t), hipMemcpyHostToDevice); e != hipSuccess)
+      return refuse(who, e, "column map upload");
   }
-  if (d_all) (void)hipFree(d_all);
-  if (d_map) (void)hipFree(d_map);
-  if (prev != device) (void)hipSetDevice(prev);
-  if (!err.empty()) return g_error = err, 1;
+  uint64_t* const d_all = all.as<uint64_t>();
+  r3d_volume_views vw{};
+  vw.size = sizeof(vw), vw.frame_begin = frame_begin, vw.frame_end = frame_end, vw.frame_group = frame_group;
+  vw.n_range = elev ? n_range : 0, vw.d_range_bin = map.as<uint32_t>();
+  vw.d_above = above ? d_all : nullptr, vw.d_elev = elev ? d_all + n_above : nullptr;
+  vw.d_outside = elev ? d_all + n_above + n_elev : nullptr;
+  if (r3d_volume_project(device, d_counters, v, &vw, nullptr)) return 1;   // (its message stands)
+  std::vector<uint64_t> host(n_all);   // (the copy waits for the launch)
+  if (hipError_t e = hipMemcpy(host.data(), d_all, n_all * sizeof(uint64_t), hipMemcpyDeviceToHost); e != hipSuccess)
+    return refuse(who, e, "reading the views");
   for (uint64_t t = 0; t < 2; t++)
     for (uint64_t F = 0; F < n_out; F++) {
       if (above) {

@@ -208,3 +208,50 @@ def test_batch_calls_fail_loudly_without_a_gpu():
     assert "no HIP device" in L.r3d_last_error().decode()
     assert L.r3d_batch_moments(0, 1, p, 1, p, 1, None, 0, p, p, None, p, p, None) != 0
     assert "2 .. 64" in L.r3d_last_error().decode()
+
+
+def test_device_level_calls_fail_loudly_without_a_gpu():
+    """The seven calls that take a device index, well-formed and over a non-empty range, on a machine without a GPU:
+    each says that there is no device, under its own name, and leaves the host's arrays alone."""
+    import torch
+    if torch.cuda.is_available():
+        return   # (the GPU tests run them)
+    from radiative3d_amd.model import volume_desc
+    L = _ffi.hip_lib()
+    nx, ny, nz, nf, n_range = 8, 4, 2, 6, 4
+    desc = volume_desc((0, 0, 0), (1, 1, 1), (nx, ny, nz), nf, 1.0)
+    p = C.c_void_p(4096)       # (never dereferenced: no call below gets as far as a launch)
+    rng = np.random.default_rng(5)
+    range_bin = rng.integers(0, n_range, (ny, nx)).astype(np.uint32)
+    above = rng.integers(0, 1 << 40, (2, nf, ny, nx)).astype(np.uint64)
+    elev = rng.integers(0, 1 << 40, (2, nf, nz, n_range)).astype(np.uint64)
+    outside = rng.integers(0, 1 << 40, 2).astype(np.uint64)
+    first, peak_frame, peak_count = (rng.integers(0, nf, (2, nz, ny, nx)).astype(np.uint32) for _ in range(3))
+    total = rng.integers(0, 1 << 40, (2, nz, ny, nx)).astype(np.uint64)
+    host = (range_bin, above, elev, outside, first, peak_frame, peak_count, total)
+    before = [a.copy() for a in host]
+    at = lambda a: a.ctypes.data   # noqa: E731
+    views = _ffi.VolumeViews(size=C.sizeof(_ffi.VolumeViews), frame_begin=0, frame_end=nf, frame_group=1, n_range=n_range,
+                             d_range_bin=p, d_above=p, d_elev=p, d_outside=p)
+    maps = _ffi.VolumeMaps(size=C.sizeof(_ffi.VolumeMaps), frame_begin=0, frame_end=nf, min_count=1, d_first=p,
+                           d_peak_frame=p, d_peak_count=p, d_total=p)
+    no_device = ": no HIP device"
+    calls = (
+        ("r3d_volume_compact", no_device, lambda: L.r3d_volume_compact(0, p, 0, 2 * nf * nz * ny * nx, p, 16, p, None)),
+        ("r3d_volume_scatter_add", no_device, lambda: L.r3d_volume_scatter_add(0, p, 2 * nf * nz * ny * nx, p, 16, p, None)),
+        ("r3d_volume_project", no_device, lambda: L.r3d_volume_project(0, p, C.byref(desc), C.byref(views), None)),
+        ("r3d_volume_project_to_host", no_device,
+         lambda: L.r3d_volume_project_to_host(0, p, C.byref(desc), 0, nf, 1, at(range_bin), n_range, 0, nf, at(above),
+                                              at(elev), at(outside))),
+        ("r3d_volume_time_maps", no_device, lambda: L.r3d_volume_time_maps(0, p, C.byref(desc), C.byref(maps), None)),
+        ("r3d_volume_time_maps_to_host", no_device,
+         lambda: L.r3d_volume_time_maps_to_host(0, p, C.byref(desc), 0, nf, 1, at(first), at(peak_frame), at(peak_count),
+                                                at(total))),
+        ("r3d_batch_moments", ": no HIP device (or a bad device index)",
+         lambda: L.r3d_batch_moments(0, 2, p, 1, p, 1, None, 0, p, p, None, p, p, None)),
+    )
+    for name, why, call in calls:
+        assert call() != 0, name
+        assert L.r3d_last_error().decode() == name + why
+    for a, b in zip(host, before):
+        assert (a == b).all()
