@@ -1,5 +1,5 @@
 """The scatter-event grid's maps along time from the command line: --scatter-maps[=MINCOUNT] (radiative3d_amd/host/
-cmdline.cpp, main.cpp), the header writer (include/r3d_host.h r3dh_write_maps_header) against a stored text, and -- on
+cmdline.cpp, scatter_out.cpp), the header writer (include/r3d_host.h r3dh_write_maps_header) against a stored text, and -- on
 the GPU -- ./main end to end: the map files equal the numpy maps of the scattergrid.u32 the same run wrote."""
 import ctypes as C
 import os

@@ -1,5 +1,5 @@
 """The two video views of the scatter-event grid from the command line: --scatter-views[=GROUP],
---scatter-view-azimuth=AZI,HALFWIDTH and --no-scatter-grid-file (radiative3d_amd/host/cmdline.cpp, main.cpp), the view
+--scatter-view-azimuth=AZI,HALFWIDTH and --no-scatter-grid-file (radiative3d_amd/host/cmdline.cpp, scatter_out.cpp), the view
 header writer (include/r3d_host.h r3dh_write_view_header) against a stored text, and -- on the GPU -- ./main end to
 end: the view files equal the projection of the scattergrid.u32 the same run wrote."""
 import ctypes as C
