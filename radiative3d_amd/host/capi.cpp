@@ -136,15 +136,8 @@ int r3dh_scatter_views(const r3dh_model* m, uint32_t* group, double azimuth[2], 
 
 int r3dh_write_view_header(const r3dh_view_header* h, const char* path) {
   if (!h || !path || !h->raw_file) return g_error = "r3dh_write_view_header: null argument", 1;
-  ScatterViewInfo v;
-  v.elevation = h->elevation != 0;
-  for (int k = 0; k < 2; k++)
-    v.dims[k] = h->dims[k], v.lo[k] = h->lo[k], v.hi[k] = h->hi[k], v.epicentre[k] = h->epicentre[k];
-  v.frames = h->frames, v.group = h->group, v.frame_seconds = h->frame_seconds, v.dr = h->dr;
-  v.azimuth = h->azimuth, v.half_width = h->half_width, v.raw_file = h->raw_file;
-  v.events_in_view = h->events_in_view, v.events_outside = h->events_outside;
   std::ofstream f(path);
-  OutputScatterViewHeader(v, f);
+  OutputScatterViewHeader(*h, f);
   if (!f) return g_error = std::string("r3dh_write_view_header: cannot write ") + path, 1;
   return 0;
 }
@@ -157,13 +150,8 @@ int r3dh_scatter_maps(const r3dh_model* m, uint32_t* min_count) {
 
 int r3dh_write_maps_header(const r3dh_maps_header* h, const char* path) {
   if (!h || !path || !h->prefix) return g_error = "r3dh_write_maps_header: null argument", 1;
-  ScatterMapsInfo v;
-  for (int k = 0; k < 3; k++) v.dims[k] = h->dims[k], v.lo[k] = h->lo[k], v.hi[k] = h->hi[k];
-  v.frames = h->frames, v.min_count = h->min_count, v.frame_seconds = h->frame_seconds;
-  v.n_range = h->n_range, v.dr = h->dr, v.epicentre[0] = h->epicentre[0], v.epicentre[1] = h->epicentre[1];
-  v.azimuth = h->azimuth, v.half_width = h->half_width, v.prefix = h->prefix;
   std::ofstream f(path);
-  OutputScatterMapsHeader(v, f);
+  OutputScatterMapsHeader(*h, f);
   if (!f) return g_error = std::string("r3dh_write_maps_header: cannot write ") + path, 1;
   return 0;
 }

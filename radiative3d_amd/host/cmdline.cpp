@@ -7,6 +7,8 @@
 #include <iostream>
 #include <map>
 
+#include "dataout.hpp"
+
 namespace {
 
 enum OptID {
@@ -229,13 +231,7 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
         if (!o.has()) mission.Reports = "ALL_ON";
         while (o.has()) {
           std::string kw = o.text();
-          static const char* ok[] = {"ALL_ON", "ALL_OFF", "GEN", "SCT", "REF", "COL",
-                                     "CEL",    "LST",     "TMO", "INV", "SCATTERS"};
-          bool known = false;
-          for (const char* k : ok) known |= (kw == k);
-          if (!known)
-            throw Runtime("Valid report keywords are: ALL_ON, ALL_OFF, GEN, SCT, REF, COL, "
-                          "CEL, LST, TMO, INV, or SCATTERS.");
+          ApplyReportKeyword(0, kw);   // (throws for a word that is no keyword)
           mission.Reports += (mission.Reports.empty() ? "" : ",") + kw;
         }
         break;

@@ -15,6 +15,7 @@
 #include <ostream>
 #include <string>
 
+#include "../../include/r3d_host.h"   // r3dh_view_header, r3dh_maps_header
 #include "model.hpp"
 
 // ModelParams::Output (model.cpp:88-132) and ::OutputOctaveText (:134-197)
@@ -43,7 +44,9 @@ void OutputSeismometerErrors(const Model& model, const double* energy_se, const 
                              const std::string& outdir);
 
 // --reports keywords (reference main.cpp:223-258) -> R3D_RPT_* mask.  `csv` is the keyword
-// list as given ("ALL_ON", "GEN,SCT,REF", "SCATTERS", ...); empty = none.
+// list as given ("ALL_ON", "GEN,SCT,REF", "SCATTERS", ...); empty = none.  ApplyReportKeyword: `mask` after ONE
+// keyword of the list; both throw the one sentence that names the valid keywords for any other word.
+uint32_t ApplyReportKeyword(uint32_t mask, const std::string& keyword);
 uint32_t ReportMaskFromKeywords(const std::string& csv);
 
 // DataReporter::output_phonon_dataline (dataout.cpp:484-520) for every record, grouped by
@@ -62,17 +65,8 @@ void OutputReports(const r3d_event* ev, size_t n, std::ostream& out);
 // ir the range bin of width `dr` about `epicentre`, columns outside azimuth +- half_width (degrees; >= 180: none)
 // left out.  The raw file beside it holds little-endian uint64, the first of ViewDims fastest -- in Octave:
 //   v = reshape(fread(fopen(ViewFile), Inf, "uint64"), ViewDims(1), ViewDims(2), ViewFrames, 2);
-struct ScatterViewInfo {
-  bool elevation;
-  unsigned dims[2];              // above: nx, ny; elevation: n_range, nz
-  unsigned frames, group;        // output frames; grid frames per output frame
-  double frame_seconds;          // grid frame length x group
-  double lo[2], hi[2];           // above: x, y of the box; elevation: range 0 .. n_range dr, z of the box
-  double dr, epicentre[2], azimuth, half_width;
-  std::string raw_file;
-  unsigned long long events_in_view, events_outside;
-};
-void OutputScatterViewHeader(const ScatterViewInfo& v, std::ostream& out);
+// The fields are include/r3d_host.h r3dh_view_header's.
+void OutputScatterViewHeader(const r3dh_view_header& v, std::ostream& out);
 
 // Header of the grid's maps along time (--scatter-maps; include/r3d.h r3d_volume_time_maps): per wave type and cell the
 // first frame with `min_count` events, the peak's frame and count, the total; and two stills of the first arrival, its
@@ -80,19 +74,20 @@ void OutputScatterViewHeader(const ScatterViewInfo& v, std::ostream& out);
 // columns outside azimuth +- half_width left out).  A frame index of MapNever = 4294967295 means "never"; the time
 // of frame f is (f + 1) * MapFrameSeconds.  The raw files are little-endian, x fastest -- in Octave:
 //   first = reshape(fread(fopen("<prefix>_first.u32"), Inf, "uint32"), MapDims(1), MapDims(2), MapDims(3), 2);
-struct ScatterMapsInfo {
-  unsigned dims[3], frames, min_count;
-  double frame_seconds, lo[3], hi[3];
-  unsigned n_range;
-  double dr, epicentre[2], azimuth, half_width;
-  std::string prefix;            // the raw files are <prefix>_first.u32, ... (kScatterMapFiles)
-};
-// suffixes of the raw files, in the order MapFiles lists them: [2][nz][ny][nx] x 4, then [2][ny][nx] and [2][nz][n_range]
+// The fields are include/r3d_host.h r3dh_maps_header's.  kScatterMapFiles: what follows <prefix> in the raw files' names,
+// in the order MapFiles lists them: [2][nz][ny][nx] x 4, then [2][ny][nx] and [2][nz][n_range]
 extern const char* const kScatterMapFiles[6];
-void OutputScatterMapsHeader(const ScatterMapsInfo& m, std::ostream& out);
+void OutputScatterMapsHeader(const r3dh_maps_header& m, std::ostream& out);
 
-void OutputScatterGridHeader(const unsigned dims[3], unsigned frames, const double lo[3], const double hi[3],
-                             double frame_dt, const std::string& raw_file, unsigned long long events_binned,
-                             unsigned long long saturated_cells, std::ostream& out);
+// What the grid's own header (the first paragraph above) says.
+struct ScatterGridInfo {
+  const uint32_t* dims;          // nx, ny, nz
+  uint32_t frames;
+  const double *lo, *hi;         // the box's corners, x y z
+  double frame_seconds;
+  std::string raw_file;
+  unsigned long long events_binned, saturated_cells;
+};
+void OutputScatterGridHeader(const ScatterGridInfo& g, std::ostream& out);
 
 #endif

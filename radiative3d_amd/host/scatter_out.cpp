@@ -88,13 +88,13 @@ void write_scatter_views(const GridJob& grid, const r3d_model_desc& d, const std
   write_raw(grid.dir + "scatterview_above.u64", above.data(), above.size() * sizeof(uint64_t));
   write_raw(grid.dir + "scatterview_elev.u64", elev.data(), elev.size() * sizeof(uint64_t));
   const scatter_plan::Box box = scatter_plan::grid_box(v);
-  ScatterViewInfo a;
-  a.elevation = false, a.dims[0] = nx, a.dims[1] = ny, a.frames = n_out, a.group = group, a.frame_seconds = v.frame_dt * group;
+  r3dh_view_header a = {};
+  a.elevation = 0, a.dims[0] = nx, a.dims[1] = ny, a.frames = n_out, a.group = group, a.frame_seconds = v.frame_dt * group;
   a.lo[0] = box.lo[0], a.lo[1] = box.lo[1], a.hi[0] = box.hi[0], a.hi[1] = box.hi[1];
   a.dr = range.dr, a.epicentre[0] = range.epi[0], a.epicentre[1] = range.epi[1], a.azimuth = 0.0, a.half_width = 180.0;   // (no filter from above)
   a.raw_file = "scatterview_above.u64", a.events_in_view = in_above, a.events_outside = 0;
-  ScatterViewInfo e = a;
-  e.elevation = true, e.dims[0] = n_range, e.dims[1] = nz;
+  r3dh_view_header e = a;
+  e.elevation = 1, e.dims[0] = n_range, e.dims[1] = nz;
   e.lo[0] = 0.0, e.lo[1] = box.lo[2], e.hi[0] = range.dr * n_range, e.hi[1] = box.hi[2];
   e.azimuth = grid.azimuth, e.half_width = grid.half_width;
   e.raw_file = "scatterview_elev.u64", e.events_in_view = in_elev, e.events_outside = outside[0] + outside[1];
@@ -129,11 +129,11 @@ void write_scatter_maps(const GridJob& grid, const r3d_model_desc& d, const std:
   const size_t bytes[6] = {cells * 4, cells * 4, cells * 4, cells * 8, above.size() * 4, elev.size() * 4};
   for (int k = 0; k < 6; k++) write_raw(grid.dir + prefix + kScatterMapFiles[k], data[k], bytes[k]);
   const scatter_plan::Box box = scatter_plan::grid_box(v);
-  ScatterMapsInfo h;
+  r3dh_maps_header h = {};
   for (int k = 0; k < 3; k++) h.dims[k] = v.dims[k], h.lo[k] = box.lo[k], h.hi[k] = box.hi[k];
   h.frames = v.n_frames, h.min_count = grid.min_count, h.frame_seconds = v.frame_dt;
   h.n_range = range.n_range, h.dr = range.dr, h.epicentre[0] = range.epi[0], h.epicentre[1] = range.epi[1];
-  h.azimuth = grid.azimuth, h.half_width = grid.half_width, h.prefix = prefix;
+  h.azimuth = grid.azimuth, h.half_width = grid.half_width, h.prefix = prefix.c_str();   // (`prefix` outlives the call)
   std::ostringstream out;
   OutputScatterMapsHeader(h, out);
   const std::string text = out.str();
@@ -165,7 +165,7 @@ void write_scatter_grid(const GridJob& grid, const std::vector<r3d_engine*>& eng
   }
   std::ofstream hdr(grid.header_path.c_str());
   const scatter_plan::Box box = scatter_plan::grid_box(v);
-  OutputScatterGridHeader(v.dims, v.n_frames, box.lo, box.hi, v.frame_dt, grid.raw_name, binned, saturated, hdr);
+  OutputScatterGridHeader({v.dims, v.n_frames, box.lo, box.hi, v.frame_dt, grid.raw_name, binned, saturated}, hdr);
   std::cout << "|  Scatter-event grid: " << binned << " events binned into " << v.dims[0] << " x " << v.dims[1] << " x " << v.dims[2]
             << " cells x " << nf << " frames x 2 wave types -> " << grid.raw_path << "\n";
 }

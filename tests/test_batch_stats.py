@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 
 from batch_cases import BATCHES, check_se, count_families, families, sum_in_order
+from cli_support import main_exe
+from octave_text import read_octave
 from radiative3d_amd import Model, _ffi
 from tests.configs import halfspace
 
@@ -100,12 +102,6 @@ def test_error_batches_option_refuses_bad_values(value, message):
         Model(halfspace(3) + ["--error-batches=" + value])
 
 
-def main_exe():
-    exe = os.path.join(REPO, "main")
-    assert os.path.exists(exe), "./main was not built"
-    return exe
-
-
 def test_cli_refuses_bad_error_batches_and_more_than_one_shard(tmp_path):
     r = subprocess.run([main_exe()] + halfspace(3) + ["--error-batches=65"], cwd=tmp_path, capture_output=True, text=True,
                        timeout=300)
@@ -119,27 +115,6 @@ def test_cli_refuses_bad_error_batches_and_more_than_one_shard(tmp_path):
 
 
 # ---- seis_NNN_err.octv ----------------------------------------------------------------------------------------------
-def parse_octave_matrices(text):
-    """name -> 2-D array (matrices) or float (scalars) of an Octave text file as dataout.cpp writes them."""
-    out, lines, i = {}, text.splitlines(), 0
-    while i < len(lines):
-        m = re.match(r"# name: (\w+)", lines[i])
-        if not m:
-            i += 1
-            continue
-        name, kind = m.group(1), lines[i + 1].split(":")[1].strip()
-        if kind == "scalar":
-            out[name] = float(lines[i + 2])
-            i += 3
-        elif kind == "matrix":
-            rows, cols = int(lines[i + 2].split(":")[1]), int(lines[i + 3].split(":")[1])
-            out[name] = np.array([[float(v) for v in lines[i + 4 + r].split()] for r in range(rows)]).reshape(rows, cols)
-            i += 4 + rows
-        else:
-            i += 2
-    return out
-
-
 def test_write_errors_writes_err_files_beside_untouched_seis_files(tmp_path):
     m = Model(halfspace(3))
     rng = np.random.default_rng(5)
@@ -158,7 +133,7 @@ def test_write_errors_writes_err_files_beside_untouched_seis_files(tmp_path):
     for s in range(m.n_seismometers):
         name = f"seis_{s:03d}.octv"
         assert (both / name).read_bytes() == before[name] == (plain / name).read_bytes()
-        got = parse_octave_matrices((both / f"seis_{s:03d}_err.octv").read_text())
+        got = read_octave(both / f"seis_{s:03d}_err.octv")
         assert got["NumBatches"] == 16 and got["NumBins"] == m.n_bins
         # (the files print 6 significant digits, like seis_NNN.octv)
         assert np.allclose(got["TraceXYZ_se"], ese[s][:, 0:3], rtol=1e-5, atol=0)

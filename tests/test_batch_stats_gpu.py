@@ -8,11 +8,12 @@ import pytest
 import torch
 
 from batch_cases import check_se, count_families, families, sum_in_order
+from cli_support import main_exe
+from octave_text import read_octave
 from oracle import oracle_ffi as O
 from oracle.check import assert_aggregates_equal
 from radiative3d_amd import Engine, _ffi, batch_moments
 from tests.configs import halfspace
-from tests.test_batch_stats import main_exe, parse_octave_matrices
 from tests.test_gpu_parity import energies_agree
 
 pytestmark = pytest.mark.gpu
@@ -237,13 +238,13 @@ def test_cli_error_batches_end_to_end(tmp_path):
     assert len(names) == 144
     some_error = 0
     for name in names:
-        a, b = parse_octave_matrices((plain / name).read_text()), parse_octave_matrices((batched / name).read_text())
+        a, b = read_octave(plain / name), read_octave(batched / name)
         assert (a["CountPS"] == b["CountPS"]).all(), name
         # (the files print 6 digits: the totals agree to summation order, far below the last printed digit --
         #  one unit of it is allowed for a value that rounds the other way)
         ea, eb = np.hstack([a["TraceXYZ"], a["TracePS"]]), np.hstack([b["TraceXYZ"], b["TracePS"]])
         assert np.allclose(ea, eb, rtol=2e-6, atol=0), name
-        err = parse_octave_matrices((batched / name.replace(".octv", "_err.octv")).read_text())
+        err = read_octave(batched / name.replace(".octv", "_err.octv"))
         assert err["NumBatches"] == 16
         assert err["TraceXYZ_se"].shape == a["TraceXYZ"].shape and err["CountPS_se"].shape == a["CountPS"].shape
         assert (err["TracePS_se"] >= 0).all() and ((err["CountPS_se"] > 0) <= (a["CountPS"] > 0)).all()

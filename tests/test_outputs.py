@@ -8,35 +8,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from octave_text import read_octave
 from oracle import oracle_ffi as O
 from radiative3d_amd import Model, _ffi
 from tests.configs import halfspace, lopnor
 
 MAIN = os.path.join(_ffi.REPO, "main")
-
-
-def parse_octave_struct(text):
-    """Minimal reader of the GNU-Octave text struct the reference writes."""
-    out, lines, i = {}, text.splitlines(), 0
-    while i < len(lines):
-        m = re.match(r"# name: (\w+)", lines[i])
-        if not m or m.group(1) == "SEIS":
-            i += 1
-            continue
-        name, kind = m.group(1), lines[i + 1].split(":")[1].strip()
-        i += 2
-        if kind == "scalar":
-            out[name] = float(lines[i].split()[0])
-        elif kind == "string":
-            out[name] = lines[i + 2]
-        elif kind == "matrix":
-            rows = int(lines[i].split(":")[1])
-            cols = int(lines[i + 1].split(":")[1])
-            vals = [[float(x) for x in lines[i + 2 + r].split()] for r in range(rows)]
-            assert all(len(v) == cols for v in vals), name
-            out[name] = np.array(vals)
-        i += 1
-    return out
 
 
 def test_seismometer_files_carry_the_result(tmp_path):
@@ -48,7 +25,7 @@ def test_seismometer_files_carry_the_result(tmp_path):
     assert "(Diag: 0x0)" in summary
     files = sorted(f for f in os.listdir(tmp_path) if f.startswith("seis_") and f.endswith(".octv"))
     assert files == [f"seis_{i:03d}.octv" for i in range(144)]
-    s = parse_octave_struct(open(tmp_path / "seis_060.octv").read())
+    s = read_octave(tmp_path / "seis_060.octv")
     assert s["NumBins"] == 400 and s["Frequency"] == 2 and s["AxesDesc"] == "RTZ"
     assert s["TimeWindow"].tolist() == [[0, 200]]
     assert s["EventLoc"].tolist() == [[0, 0, -5]]
@@ -66,7 +43,7 @@ def test_seismometer_files_carry_the_result(tmp_path):
     assert len(block) == 400 and all(len(r.split()) == 7 for r in block)
     assert sum(int(r.split()[5]) for r in block) == int(res.counts[60, :, 0].sum())
     # parameter file
-    p = parse_octave_struct(open(tmp_path / "out_mparams.octv").read())
+    p = read_octave(tmp_path / "out_mparams.octv")
     assert p["TOA_Degree"] == 4 and p["PhononTTL"] == 200 and p["CylinderRange"] == 900
     assert p["CompiledArgs"].shape == (1, 18)
 
@@ -122,7 +99,7 @@ def test_main_cli_end_to_end_on_gpu(tmp_path):
     m = Model(halfspace(4))
     want = O.run(m, 200000, seed=7)
     assert (lost, tmo) == (want.n_lost, want.n_timeout)
-    s = parse_octave_struct(open(tmp_path / "seis_100.octv").read())
+    s = read_octave(tmp_path / "seis_100.octv")
     assert (s["CountPS"] == want.counts[100]).all()
     assert np.allclose(s["TracePS"], want.energy[100, :, 3:], rtol=1e-5)
     assert os.path.exists(tmp_path / "seis_traces_asc.dat") and os.path.exists(tmp_path / "out_mparams.octv")
@@ -214,7 +191,7 @@ def test_main_cli_writes_the_scatter_grid_of_a_video_run_on_gpu(tmp_path):
                                  "--scatter-grid-file=grid"]
     run = subprocess.run([MAIN] + args, capture_output=True, text=True, cwd=tmp_path)
     assert run.returncode == 0, run.stdout[-2000:]
-    hdr = parse_octave_struct(open(tmp_path / "grid.octv").read())
+    hdr = read_octave(tmp_path / "grid.octv")
     assert list(hdr["GridDims"].reshape(-1)) == list(dims) and int(hdr["GridFrames"]) == frames
     assert float(hdr["GridFrameSeconds"]) == pytest.approx(350.0 / frames)
     got = np.fromfile(tmp_path / "grid.u32", dtype="<u4").reshape(2, frames, dims[2], dims[1], dims[0])

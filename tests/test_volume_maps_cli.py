@@ -3,19 +3,19 @@ cmdline.cpp, scatter_out.cpp), the header writer (include/r3d_host.h r3dh_write_
 the GPU -- ./main end to end: the map files equal the numpy maps of the scattergrid.u32 the same run wrote."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
+from cli_support import GRID_OPT, grid_desc, main_exe, run
+from octave_text import read_octave
 from radiative3d_amd import Model, _ffi
-from tests.configs import crustpinch, halfspace
+from tests.configs import halfspace
 from volume_maps_cases import NEVER, time_maps_numpy
 from volume_views_cases import range_bins_numpy
 
 REPO = _ffi.REPO
-GRID_OPT = "--scatter-grid=64,60,14,35,-200,-600,-130,1080,600,10"
 MAP_FILES = ["scattermaps_first.u32", "scattermaps_peakframe.u32", "scattermaps_peakcount.u32", "scattermaps_total.u64",
              "scattermaps_first_above.u32", "scattermaps_first_elev.u32"]
 
@@ -46,12 +46,6 @@ def test_the_option_refuses_what_it_cannot_do(extra, message):
         Model(halfspace(3) + extra)
 
 
-def main_exe():
-    exe = os.path.join(REPO, "main")
-    assert os.path.exists(exe), "./main was not built"
-    return exe
-
-
 def test_cli_refuses_the_option_without_a_grid_and_lists_it(tmp_path):
     for extra, message in ((["--scatter-maps"], "--scatter-maps needs --scatter-grid"),
                            ([GRID_OPT, "--scatter-maps=0"], "must be positive")):
@@ -64,17 +58,6 @@ def test_cli_refuses_the_option_without_a_grid_and_lists_it(tmp_path):
     assert "--scatter-maps[=MINCOUNT]" in text
 
 
-def read_header(path):
-    """name -> float, list of floats, or list of strings, of an Octave text file as the writers here make it."""
-    out = {}
-    for b in re.split(r"^# name: ", open(path).read(), flags=re.M)[1:]:
-        lines = [ln.strip() for ln in b.split("\n")]
-        name, kind = lines[0], lines[1].replace("# type: ", "")
-        body = [ln for ln in lines[2:] if ln and not ln.startswith("#")]
-        out[name] = body if kind == "string" else float(body[0]) if kind == "scalar" else [float(x) for x in body[0].split()]
-    return out
-
-
 def test_the_maps_header_is_the_stored_text(tmp_path):
     L = _ffi.host_lib()
     h = _ffi.MapsHeader(dims=(C.c_uint32 * 3)(256, 256, 64), frames=300, min_count=2, n_range=182, frame_seconds=3.5,
@@ -84,12 +67,12 @@ def test_the_maps_header_is_the_stored_text(tmp_path):
     assert L.r3dh_write_maps_header(C.byref(h), str(out).encode()) == 0
     want = open(os.path.join(REPO, "tests", "golden", "scattermaps_header.octv")).read()
     assert out.read_text() == want
-    head = read_header(out)
-    assert head["MapDims"] == [256.0, 256.0, 64.0] and head["MapFrames"] == 300.0 and head["MapFrameSeconds"] == 3.5
+    head = read_octave(out)
+    assert head["MapDims"].tolist() == [[256.0, 256.0, 64.0]] and head["MapFrames"] == 300.0 and head["MapFrameSeconds"] == 3.5
     assert head["MapMinCount"] == 2.0 and head["MapNever"] == 4294967295.0 == float(NEVER) and head["MapWaveTypes"] == 2.0
-    assert head["MapBoxLo"] == [-1000.0, -1000.0, -250.0] and head["MapBoxHi"] == [1000.0, 1000.0, 0.0]
-    assert head["MapRangeBins"] == 182.0 and head["MapRangeBin"] == 7.8125 and head["MapEpicentre"] == [0.0, 12.5]
-    assert head["MapAzimuthFilter"] == [22.5, 15.0] and head["MapFiles"] == MAP_FILES
+    assert head["MapBoxLo"].tolist() == [[-1000.0, -1000.0, -250.0]] and head["MapBoxHi"].tolist() == [[1000.0, 1000.0, 0.0]]
+    assert head["MapRangeBins"] == 182.0 and head["MapRangeBin"] == 7.8125 and head["MapEpicentre"].tolist() == [[0.0, 12.5]]
+    assert head["MapAzimuthFilter"].tolist() == [[22.5, 15.0]] and head["MapFiles"] == MAP_FILES
     assert L.r3dh_write_maps_header(None, str(out).encode()) != 0
     assert L.r3dh_write_maps_header(C.byref(h), str(tmp_path / "no" / "such" / "dir.octv").encode()) != 0
     h.prefix = None
@@ -103,28 +86,17 @@ def test_main_writes_the_maps_of_the_grid_it_wrote(tmp_path):
     and no .part file remains.  Once more as two shards on one GPU (--devices=0,0: each engine's own frames, merged)
     and with the views' azimuth filter: the same bytes in every file but the elevation still, which is the filtered
     map's."""
-    args = crustpinch(4) + ["--overridemfp=25,50", "--nodeflect", "--timetolive=350", "--num-phonons=20K", GRID_OPT]
     map_files = set(MAP_FILES) | {"scattermaps.octv"}
-
-    def run(name, extra):
-        out = tmp_path / name
-        out.mkdir()
-        r = subprocess.run([main_exe()] + args + extra + [f"--output-dir={out}"], cwd=out, capture_output=True, text=True,
-                           timeout=600)
-        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-        files = set(os.listdir(out))
-        assert not [f for f in files if f.endswith(".part")]
-        return out, files, r.stdout
-
-    one, one_files, stdout = run("one", ["--scatter-maps=2"])
+    one, one_files, stdout = run(tmp_path, "one", ["--scatter-maps=2"])
     assert one_files >= map_files | {"scattergrid.octv", "scattergrid.u32"} and "Scatter-event maps:" in stdout
     assert not [f for f in one_files if "scatterview" in f]
     grid = np.fromfile(one / "scattergrid.u32", dtype=np.uint32).reshape(2, 35, 14, 60, 64)
-    head = read_header(one / "scattermaps.octv")
-    assert head["MapDims"] == [64.0, 60.0, 14.0] and head["MapFrames"] == 35.0 and head["MapFrameSeconds"] == 10.0
+    head = read_octave(one / "scattermaps.octv")
+    assert head["MapDims"].tolist() == [[64.0, 60.0, 14.0]] and head["MapFrames"] == 35.0 and head["MapFrameSeconds"] == 10.0
     assert head["MapMinCount"] == 2.0 and head["MapFiles"] == MAP_FILES and head["MapNever"] == float(NEVER)
-    assert head["MapBoxLo"] == [-200.0, -600.0, -130.0] and head["MapBoxHi"] == [1080.0, 600.0, 10.0]
-    assert head["MapRangeBin"] == 20.0 and head["MapEpicentre"] == [0.0, 0.0] and head["MapAzimuthFilter"] == [0.0, 180.0]
+    assert head["MapBoxLo"].tolist() == [[-200.0, -600.0, -130.0]] and head["MapBoxHi"].tolist() == [[1080.0, 600.0, 10.0]]
+    assert head["MapRangeBin"] == 20.0 and head["MapEpicentre"].tolist() == [[0.0, 0.0]]
+    assert head["MapAzimuthFilter"].tolist() == [[0.0, 180.0]]
     n_range = int(head["MapRangeBins"])
     assert n_range == int(np.hypot(1080.0, 600.0) / 20.0) + 1          # the corner farthest from the epicentre (0, 0)
     first, peak_frame, peak_count, total = time_maps_numpy(grid, 0, 35, 2)
@@ -135,9 +107,7 @@ def test_main_writes_the_maps_of_the_grid_it_wrote(tmp_path):
         assert (np.fromfile(out / MAP_FILES[1], dtype=np.uint32).reshape(shape) == peak_frame).all()
         assert (np.fromfile(out / MAP_FILES[2], dtype=np.uint32).reshape(shape) == peak_count).all()
         assert (np.fromfile(out / MAP_FILES[3], dtype=np.uint64).reshape(shape) == total).all()
-        from radiative3d_amd.model import volume_desc
-        desc = volume_desc((-200.0, -600.0, -130.0), (20.0, 20.0, 10.0), (64, 60, 14), 35, 10.0)
-        rb = range_bins_numpy(desc, head["MapEpicentre"], head["MapRangeBin"], n_range, azimuth, half_width)
+        rb = range_bins_numpy(grid_desc(), head["MapEpicentre"][0], head["MapRangeBin"], n_range, azimuth, half_width)
         elev = np.full((2, 14, n_range), NEVER, dtype=np.uint32)
         inside = rb < n_range
         for t in range(2):
@@ -150,10 +120,10 @@ def test_main_writes_the_maps_of_the_grid_it_wrote(tmp_path):
     elev = check(one, 0.0, 180.0)
     assert int(total.sum()) == int(grid.sum(dtype=np.uint64)) > 10000
     assert (first != NEVER).sum() > 100 and (peak_count == 1).sum() > 100 and (elev != NEVER).any()   # (MINCOUNT 2 decided cells)
-    two, two_files, _ = run("two", ["--scatter-maps=2", "--devices=0,0", "--scatter-views", "--scatter-view-azimuth=30,100"])
+    two, two_files, _ = run(tmp_path, "two", ["--scatter-maps=2", "--devices=0,0", "--scatter-views", "--scatter-view-azimuth=30,100"])
     assert two_files >= one_files and "scatterview_elev.u64" in two_files
     assert (two / "scattergrid.u32").read_bytes() == (one / "scattergrid.u32").read_bytes()
     for f in MAP_FILES[:5]:
         assert (two / f).read_bytes() == (one / f).read_bytes(), f
-    assert read_header(two / "scattermaps.octv")["MapAzimuthFilter"] == [30.0, 100.0]
+    assert read_octave(two / "scattermaps.octv")["MapAzimuthFilter"].tolist() == [[30.0, 100.0]]
     assert (check(two, 30.0, 100.0) != elev).any()

@@ -4,18 +4,18 @@ header writer (include/r3d_host.h r3dh_write_view_header) against a stored text,
 end: the view files equal the projection of the scattergrid.u32 the same run wrote."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
+from cli_support import GRID_OPT, grid_desc, main_exe, run
+from octave_text import read_octave
 from radiative3d_amd import Model, _ffi
-from tests.configs import crustpinch, halfspace
+from tests.configs import halfspace
 from volume_views_cases import project_numpy, range_bins_numpy
 
 REPO = _ffi.REPO
-GRID_OPT = "--scatter-grid=64,60,14,35,-200,-600,-130,1080,600,10"
 
 
 def test_the_view_options_parse_and_are_off_by_default():
@@ -49,12 +49,6 @@ def test_the_view_options_refuse_what_they_cannot_do(extra, message):
         Model(halfspace(3) + extra)
 
 
-def main_exe():
-    exe = os.path.join(REPO, "main")
-    assert os.path.exists(exe), "./main was not built"
-    return exe
-
-
 def test_cli_refuses_the_view_options_without_a_grid_and_lists_them(tmp_path):
     for extra, message in ((["--scatter-views"], "--scatter-views needs --scatter-grid"),
                            ([GRID_OPT, "--no-scatter-grid-file"], "--no-scatter-grid-file needs --scatter-views"),
@@ -76,12 +70,12 @@ def test_the_view_header_is_the_stored_text(tmp_path):
     assert L.r3dh_write_view_header(C.byref(h), str(out).encode()) == 0
     want = open(os.path.join(REPO, "tests", "golden", "scatterview_elev_header.octv")).read()
     assert out.read_text() == want
-    head = read_header(out)
-    assert head["ViewKind"] == "elevation" and head["ViewDims"] == [182.0, 64.0] and head["ViewFrameGroup"] == 3.0
-    assert head["ViewAzimuthFilter"] == [22.5, 15.0] and head["ViewEventsInView"] == 123456789012.0
+    head = read_octave(out)
+    assert head["ViewKind"] == "elevation" and head["ViewDims"].tolist() == [[182.0, 64.0]] and head["ViewFrameGroup"] == 3.0
+    assert head["ViewAzimuthFilter"].tolist() == [[22.5, 15.0]] and head["ViewEventsInView"] == 123456789012.0
     h.elevation = 0
     assert L.r3dh_write_view_header(C.byref(h), str(out).encode()) == 0
-    assert read_header(out)["ViewKind"] == "above" and read_header(out)["ViewAxes"] == "x,y"
+    assert read_octave(out)["ViewKind"] == "above" and read_octave(out)["ViewAxes"] == "x,y"
     assert L.r3dh_write_view_header(None, str(out).encode()) != 0
     assert L.r3dh_write_view_header(C.byref(h), str(tmp_path / "no" / "such" / "dir.octv").encode()) != 0
     src = tmp_path / "s.c"
@@ -93,59 +87,31 @@ def test_the_view_header_is_the_stored_text(tmp_path):
     assert got == [C.sizeof(_ffi.ViewHeader), _ffi.ViewHeader.raw_file.offset, _ffi.ViewHeader.events_outside.offset]
 
 
-def read_header(path):
-    """name -> float, list of floats or string, of an Octave text file as the writers here make it."""
-    out = {}
-    blocks = re.split(r"^# name: ", open(path).read(), flags=re.M)[1:]
-    for b in blocks:
-        lines = [ln.strip() for ln in b.split("\n")]
-        name, kind = lines[0], lines[1].replace("# type: ", "")
-        body = [ln for ln in lines[2:] if ln and not ln.startswith("#")]
-        if kind == "string":
-            out[name] = body[0]
-        elif kind == "scalar":
-            out[name] = float(body[0])
-        else:
-            out[name] = [float(x) for x in body[0].split()]
-    return out
-
-
 @pytest.mark.gpu
 def test_main_writes_the_views_of_the_grid_it_wrote(tmp_path):
     """./main on a small tetra model: the view files equal the numpy projection of the scattergrid.u32 of the same run
     (the map made from what the headers say); with --no-scatter-grid-file the raw grid is absent and the view files
     are byte for byte the same; two shards on one GPU (--devices=0,0: 18 + 17 frames, so that with GROUP = 4 an output
     frame straddles the owners) give the same bytes; a run without the new options leaves no view file."""
-    args = crustpinch(4) + ["--overridemfp=25,50", "--nodeflect", "--timetolive=350", "--num-phonons=20K", GRID_OPT]
     view_files = {"scatterview_above.octv", "scatterview_above.u64", "scatterview_elev.octv", "scatterview_elev.u64"}
-
-    def run(name, extra):
-        out = tmp_path / name
-        out.mkdir()
-        r = subprocess.run([main_exe()] + args + extra + [f"--output-dir={out}"], cwd=out, capture_output=True, text=True,
-                           timeout=600)
-        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-        return out, set(os.listdir(out)), r.stdout
-
-    plain, plain_files, _ = run("plain", [])
+    plain, plain_files, _ = run(tmp_path, "plain", [])
     assert {"scattergrid.octv", "scattergrid.u32"} <= plain_files
     assert not [f for f in plain_files if "scatterview" in f or f.endswith(".part")]
     views = ["--scatter-views=4", "--scatter-view-azimuth=30,100"]
-    both, both_files, stdout = run("both", views)
+    both, both_files, stdout = run(tmp_path, "both", views)
     assert both_files == plain_files | view_files and "Scatter-event views:" in stdout
     assert (both / "scattergrid.u32").read_bytes() == (plain / "scattergrid.u32").read_bytes()
     grid = np.fromfile(both / "scattergrid.u32", dtype=np.uint32).reshape(2, 35, 14, 60, 64)
-    ha, he = read_header(both / "scatterview_above.octv"), read_header(both / "scatterview_elev.octv")
-    assert ha["ViewKind"] == "above" and ha["ViewDims"] == [64.0, 60.0] and ha["ViewFrames"] == 9.0 == he["ViewFrames"]
+    ha, he = read_octave(both / "scatterview_above.octv"), read_octave(both / "scatterview_elev.octv")
+    assert ha["ViewKind"] == "above" and ha["ViewDims"].tolist() == [[64.0, 60.0]] and ha["ViewFrames"] == 9.0 == he["ViewFrames"]
     assert ha["ViewFrameGroup"] == 4.0 and ha["ViewFrameSeconds"] == 40.0 and ha["ViewFile"] == "scatterview_above.u64"
-    assert ha["ViewBoxLo"] == [-200.0, -600.0] and ha["ViewBoxHi"] == [1080.0, 600.0]
-    assert he["ViewKind"] == "elevation" and he["ViewAzimuthFilter"] == [30.0, 100.0] and he["ViewRangeBin"] == 20.0
-    assert he["ViewBoxLo"] == [0.0, -130.0] and he["ViewDims"][1] == 14.0 and he["ViewEpicentre"] == [0.0, 0.0]
-    n_range = int(he["ViewDims"][0])
+    assert ha["ViewBoxLo"].tolist() == [[-200.0, -600.0]] and ha["ViewBoxHi"].tolist() == [[1080.0, 600.0]]
+    assert he["ViewKind"] == "elevation" and he["ViewAzimuthFilter"].tolist() == [[30.0, 100.0]] and he["ViewRangeBin"] == 20.0
+    assert he["ViewBoxLo"].tolist() == [[0.0, -130.0]] and he["ViewDims"][0, 1] == 14.0
+    assert he["ViewEpicentre"].tolist() == [[0.0, 0.0]]
+    n_range = int(he["ViewDims"][0, 0])
     assert n_range == int(np.hypot(1080.0, 600.0) / 20.0) + 1          # the corner farthest from the epicentre (0, 0)
-    from radiative3d_amd.model import volume_desc
-    desc = volume_desc((-200.0, -600.0, -130.0), (20.0, 20.0, 10.0), (64, 60, 14), 35, 10.0)
-    rb = range_bins_numpy(desc, he["ViewEpicentre"], he["ViewRangeBin"], n_range, 30.0, 100.0)
+    rb = range_bins_numpy(grid_desc(), he["ViewEpicentre"][0], he["ViewRangeBin"], n_range, 30.0, 100.0)
     wa, we, wo = project_numpy(grid, 0, 35, 4, rb, n_range)
     above = np.fromfile(both / "scatterview_above.u64", dtype=np.uint64).reshape(2, 9, 60, 64)
     elev = np.fromfile(both / "scatterview_elev.u64", dtype=np.uint64).reshape(2, 9, 14, n_range)
@@ -153,9 +119,9 @@ def test_main_writes_the_views_of_the_grid_it_wrote(tmp_path):
     assert ha["ViewEventsInView"] == float(wa.sum()) and he["ViewEventsInView"] == float(we.sum())
     assert he["ViewEventsOutside"] == float(wo.sum()) and ha["ViewEventsOutside"] == 0.0
 
-    only, only_files, _ = run("only", views + ["--no-scatter-grid-file"])
+    only, only_files, _ = run(tmp_path, "only", views + ["--no-scatter-grid-file"])
     assert only_files == (plain_files | view_files) - {"scattergrid.octv", "scattergrid.u32"}
-    two, two_files, _ = run("two", views + ["--devices=0,0"])
+    two, two_files, _ = run(tmp_path, "two", views + ["--devices=0,0"])
     assert two_files == both_files
     for f in sorted(view_files):
         assert (only / f).read_bytes() == (both / f).read_bytes(), f
