@@ -680,6 +680,55 @@ int r3d_run_device_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_
 int r3d_run_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
                     r3d_result* out, double* energy_se, double* counts_se);
 
+/* ---- the same standard errors for a job sharded over several devices ------------
+ * THE ESTIMATOR.  A job covers the ids [first_id, first_id + n) on D shards in N = D * B batches, 2 <= B <= 64 (N itself
+ * may pass 64): batch j is the ids [first_id + floor(j n / N), first_id + floor((j + 1) n / N)), shard g owns the
+ * batches [g B, (g + 1) B) -- the ids [first_id + floor(g n / D), first_id + floor((g + 1) n / D)), since
+ * floor(g B n / N) = floor(g n / D).  The batches are cut over the WHOLE id range, so the result does not depend on
+ * how they are dealt to devices.  Each batch is one self-contained launch into its own zeroed block X_j, as above, and
+ * for every entry of the energy and of the counts array
+ *     T  = sum over all N batches of X_j                    ADDED into the caller's result
+ *     se = sqrt( N/(N-1) * sum_j (X_j - T/N)^2 )            WRITTEN
+ * With S_g the sum of shard g's batches and ss_g = sum_{j in g} (X_j - S_g/B)^2 the sum of squares splits exactly,
+ *     sum_j (X_j - T/N)^2 = sum_g ss_g + (1/B) * sum_g (S_g - T/D)^2,
+ * into what every shard can take from its own blocks where they lie and a term between the shards' sums: two arrays per
+ * shard travel, not B blocks.  Energies: S_g is the fp64 sum in batch order, T the fp64 sum of the S_g in shard order.
+ * Counts and scalars: exact in u64, their ss in fp64 from integer differences.  The arithmetic is that of
+ * r3d_batch_moments (radiative3d_amd/stats/r3d_batch_moments.h: two passes over x_j - x_0, then two over S_g - S_0; no
+ * multiply fused into an add, on the device as on the host), with its bound for N in place of B; merging D = 1 gives
+ * r3d_batch_moments' T and se to the bit, and batches that are all equal give se = 0 exactly for any D.
+ *
+ * r3d_batch_partial: a shard's half, device level like r3d_batch_moments -- blocks [B][len] on `device`, only read;
+ * d_energy_sum / d_energy_ss [n_energy], d_counts_sum / d_counts_ss [n_counts], d_scalars_sum [n_scalars] (with
+ * d_batch_scalars; may be NULL) are WRITTEN.  r3d_batch_merge: the root's half -- d_*_sum, d_*_ss are [D][len], shard
+ * after shard, only read; T is ADDED into d_energy / d_counts / d_scalars, se WRITTEN into d_energy_se / d_counts_se
+ * (either may be NULL, and then its ss array too).  Both asynchronous on `stream`; one work-item per entry, fixed order,
+ * no atomics: the same bits on every run.  REFUSED (non-zero, r3d_last_error, nothing enqueued): a null input or
+ * output, B < 2, B > 64, D == 0, an se array without its ss.
+ *
+ * r3d_node_run_batched: the job on a node -- n_batches is the job's N; every shard's engine runs its B = N / D batches
+ * on its own device and reduces them there, the (S_g, ss_g) go to shard 0's device (hipMemcpyPeerAsync behind an event
+ * of the shard's stream; shards that share a device take the same path), r3d_batch_merge runs there, and the host reads
+ * T, the scalars (ADDED into *out, as r3d_node_run does) and the two se arrays (WRITTEN; either may be NULL).  Note that
+ * r3d_node_run deals a remainder of n / D to the first shards, this call by the floors above: the totals of the two
+ * agree as any two partitions do.  REFUSED (nothing run, *out and the se arrays untouched): N not a multiple of D,
+ * N / D < 2, N / D > 64, n < N, any engine with a carry chain that awaits its flush, an attached event log or an
+ * attached production-finals buffer.  An attached event grid is fine.                                            */
+int r3d_batch_partial(int device, uint32_t n_batches,
+                      const double* d_batch_energy, uint64_t n_energy,
+                      const uint64_t* d_batch_counts, uint64_t n_counts,
+                      const uint64_t* d_batch_scalars, uint64_t n_scalars,
+                      double* d_energy_sum, double* d_energy_ss, uint64_t* d_counts_sum, double* d_counts_ss,
+                      uint64_t* d_scalars_sum, void* stream);
+int r3d_batch_merge(int device, uint32_t n_shards, uint32_t n_batches,
+                    const double* d_energy_sum, const double* d_energy_ss, uint64_t n_energy,
+                    const uint64_t* d_counts_sum, const double* d_counts_ss, uint64_t n_counts,
+                    const uint64_t* d_scalars_sum, uint64_t n_scalars,
+                    double* d_energy, uint64_t* d_counts, uint64_t* d_scalars,
+                    double* d_energy_se, double* d_counts_se, void* stream);
+int r3d_node_run_batched(r3d_node* node, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                         r3d_result* out, double* energy_se, double* counts_se);
+
 /* Self-test hook: evaluates one of the kernel's own elementary functions
  * (radiative3d_amd/csrc/r3d_math.h -- the traversal uses these instead of the
  * device library's exp / log / atanh / asin / atan2 / sincos) on the device,

@@ -57,10 +57,13 @@ const char* r3dh_write_outputs(r3dh_model* m, const r3d_result* result, const ch
 /* The standard errors of a batched run (r3d.h r3d_run_batched: energy_se / counts_se laid out as the result's
  * energy / counts) as seis_NNN_err.octv beside each seis_NNN.octv in `outdir` ("" = cwd), same Octave text
  * conventions: matrices TraceXYZ_se, TracePS_se, CountPS_se and the scalars NumBins, NumBatches.  Returns 0 ok.
- * r3dh_error_batches: what --error-batches=B in the model's arguments asked for (2..64; 0 if absent).        */
+ * r3dh_error_batches: what --error-batches=B in the model's arguments asked for (2..64; 0 if absent).
+ * r3dh_job_error_batches: what --job-error-batches=N asked for -- the batches of the whole job, a multiple of the
+ * shards that --gpus / --devices name with 2..64 per shard (r3d.h r3d_node_run_batched; 0 if absent).            */
 int r3dh_write_errors(r3dh_model* m, const double* energy_se, const double* counts_se, uint32_t n_batches,
                       const char* outdir);
 uint32_t r3dh_error_batches(const r3dh_model* m);
+uint32_t r3dh_job_error_batches(const r3dh_model* m);
 
 /* --scatter-views[=GROUP] [--scatter-view-azimuth=AZI,HALFWIDTH] [--no-scatter-grid-file] in the model's arguments
  * (all three refused without --scatter-grid, the last two without --scatter-views): returns 1 and fills *group

@@ -205,6 +205,8 @@ def host_lib():
         L.r3dh_write_errors.argtypes = [C.c_void_p, _dp, _dp, C.c_uint32, C.c_char_p]
         L.r3dh_error_batches.restype = C.c_uint32
         L.r3dh_error_batches.argtypes = [C.c_void_p]
+        L.r3dh_job_error_batches.restype = C.c_uint32
+        L.r3dh_job_error_batches.argtypes = [C.c_void_p]
         L.r3dh_scatter_views.restype = C.c_int
         L.r3dh_scatter_views.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), _dp, C.POINTER(C.c_int)]
         L.r3dh_write_view_header.restype = C.c_int
@@ -377,6 +379,16 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_run_batched.restype = C.c_int
         L.r3d_run_batched.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
                                       _dp, _dp]
+        L.r3d_batch_partial.restype = C.c_int
+        L.r3d_batch_partial.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.r3d_batch_merge.restype = C.c_int
+        L.r3d_batch_merge.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                      C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        L.r3d_node_run_batched.restype = C.c_int
+        L.r3d_node_run_batched.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
+                                           _dp, _dp]
         L.r3d_last_error.restype = C.c_char_p
         L.r3d_version.restype = C.c_char_p
         _hip[key] = L

@@ -125,6 +125,7 @@ int r3dh_write_errors(r3dh_model* m, const double* energy_se, const double* coun
 }
 
 uint32_t r3dh_error_batches(const r3dh_model* m) { return m ? m->mission.ErrorBatches : 0; }
+uint32_t r3dh_job_error_batches(const r3dh_model* m) { return m ? m->mission.JobErrorBatches : 0; }
 
 int r3dh_scatter_views(const r3dh_model* m, uint32_t* group, double azimuth[2], int* no_grid_file) {
   if (!m || !m->mission.bScatterViews) return 0;

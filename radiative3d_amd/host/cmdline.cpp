@@ -18,7 +18,7 @@ enum OptID {
   OPT_SEISARRAY, OPT_SEIS_P2P, OPT_SEIS_P2PW, OPTM_HELP, OPTM_DUMPGRID, OPTM_PARAMOUTFN,
   OPTM_RTTEST, OPTM_EVENTTEST, OPTM_RUNSIM, OPTX_SEED, OPTX_GPUS, OPTX_DEVTABLES, OPTX_HOSTTABLES,
   OPTX_DEVICES, OPTX_SCATGRID, OPTX_SCATGRID_FILE, OPTX_ERRBATCHES,
-  OPTX_SCATVIEWS, OPTX_SCATVIEW_AZI, OPTX_NO_SCATGRID_FILE, OPTX_SCATMAPS
+  OPTX_SCATVIEWS, OPTX_SCATVIEW_AZI, OPTX_NO_SCATGRID_FILE, OPTX_SCATMAPS, OPTX_JOBERRBATCHES
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -50,7 +50,7 @@ const std::map<std::string, OptID>& option_table() {
       {"--seed", OPTX_SEED}, {"--gpus", OPTX_GPUS}, {"--device-tables", OPTX_DEVTABLES},
       {"--host-tables", OPTX_HOSTTABLES}, {"--devices", OPTX_DEVICES},
       {"--scatter-grid", OPTX_SCATGRID}, {"--scatter-grid-file", OPTX_SCATGRID_FILE},
-      {"--error-batches", OPTX_ERRBATCHES},
+      {"--error-batches", OPTX_ERRBATCHES}, {"--job-error-batches", OPTX_JOBERRBATCHES},
       {"--scatter-views", OPTX_SCATVIEWS}, {"--scatter-view-azimuth", OPTX_SCATVIEW_AZI},
       {"--no-scatter-grid-file", OPTX_NO_SCATGRID_FILE}, {"--scatter-maps", OPTX_SCATMAPS}};
   return t;
@@ -289,6 +289,13 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
         mission.ErrorBatches = (unsigned)b;
         break;
       }
+      case OPTX_JOBERRBATCHES: {
+        const long b = o.integer();
+        if (b < 2 || b > 0x7FFFFFFFL)
+          throw Runtime("--job-error-batches=N: the job needs at least 2 batches (got " + std::to_string(b) + ").");
+        mission.JobErrorBatches = (unsigned)b;
+        break;
+      }
       case OPTX_SCATVIEWS: {
         const long g = o.has() ? o.integer() : 1;
         if (g < 1 || g > 0xFFFFFFFFL)
@@ -317,6 +324,21 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }
+  }
+  // --job-error-batches=N deals the job's N batches evenly to the shards that --gpus / --devices name
+  if (mission.JobErrorBatches) {
+    const unsigned long shards = mission.Devices.empty() ? (unsigned long)std::max(1, mission.Gpus) : mission.Devices.size();
+    const unsigned long N = mission.JobErrorBatches;
+    const std::string over = std::to_string(N) + " batches over " + std::to_string(shards) + (shards == 1 ? " shard" : " shards");
+    if (mission.ErrorBatches)
+      throw Runtime("--job-error-batches cannot be combined with --error-batches: the first cuts the whole job into its N "
+                    "batches, the second one device's share into B.");
+    if (ReportMaskFromKeywords(mission.Reports))
+      throw Runtime("--job-error-batches cannot be combined with --reports (the event log's launches run one at a time).");
+    if (N % shards)
+      throw Runtime("--job-error-batches=N: N must be a multiple of the number of shards (got " + over + ").");
+    if (N / shards < 2 || N / shards > 64)
+      throw Runtime("--job-error-batches=N: every shard runs N / shards batches, which must be 2 .. 64 (got " + over + ").");
   }
   // the views and the maps are made from the grid: none of their options means anything without it
   if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile || mission.bScatterMaps))

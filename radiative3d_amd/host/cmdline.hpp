@@ -5,7 +5,8 @@
 // `--key=v1,v2,...`, `--key value`, bare `--key`, and the single-letter
 // aliases -F -N -T -A -E -L.  Integer values take K/M/B suffixes
 // (cmdline.cpp:343-390).  Engine-only additions: --seed, --gpus, --devices, --host-tables / --device-tables,
-// --scatter-grid / --scatter-grid-file (the scatter-event histogram of a video run, written as a file).
+// --scatter-grid / --scatter-grid-file (the scatter-event histogram of a video run, written as a file),
+// --error-batches / --job-error-batches (per-bin standard errors).
 #ifndef R3DH_CMDLINE_HPP_
 #define R3DH_CMDLINE_HPP_
 
@@ -37,6 +38,9 @@ struct MissionParams {
   // --error-batches=B (2..64): run the histories as B id-partitioned batches and write each bin's standard error
   // (seis_NNN_err.octv beside seis_NNN.octv; include/r3d.h r3d_run_batched); 0 = not asked for
   unsigned ErrorBatches = 0;
+  // --job-error-batches=N: the same for a job on any number of shards -- the WHOLE job is cut into N batches, N / shards
+  // (2..64) of them per shard, and the shards' moments are merged on the GPU (include/r3d.h r3d_node_run_batched)
+  unsigned JobErrorBatches = 0;
   // --scatter-views[=GROUP]: the grid's two video views (include/r3d.h r3d_volume_project), GROUP grid frames per
   // frame of the views, as scatterview_above.{octv,u64} and scatterview_elev.{octv,u64};
   // --scatter-view-azimuth=AZI,HALFWIDTH (degrees): the elevation view keeps the columns in that cone about the

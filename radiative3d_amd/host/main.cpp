@@ -6,8 +6,9 @@
 // is one call into the engine's C-ABI.  What a run with --scatter-grid writes afterwards (the grid, its views, its maps)
 // is the output stage of scatter_out.cpp; this file builds its job, has it checked before the run and calls it once.
 //
-// Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...` and `--error-batches=B`
-// are accepted (the reference seeds from the clock, is single-process, has no event histogram and no error bars); the `--reports` stream is written
+// Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B` and
+// `--job-error-batches=N` (error bars of a job on any number of shards) are accepted (the reference seeds from the clock,
+// is single-process, has no event histogram and no error bars); the `--reports` stream is written
 // after the run, grouped by history, where the reference writes its lines as they happen (the engine appends binary
 // records in HBM: include/r3d.h r3d_event); tables are built in HBM unless `--host-tables` is given.
 #include <cstdio>
@@ -174,6 +175,13 @@ SimulationOutput run_simulation(const Model& model, const MissionParams& mission
     if (r3d_run_batched(engines[0], n, 0, seed, mission.ErrorBatches, &out.total, out.energy_se.data(), out.counts_se.data()))
       throw Runtime(r3d_last_error());
     std::cout << "|  Batches: " << mission.ErrorBatches << " (standard errors from batch means)\n";
+  } else if (mission.JobErrorBatches) {
+    // --job-error-batches: the whole job as N batches dealt to the shards, every shard's moments taken on its device
+    // and merged on shard 0's (include/r3d.h r3d_node_run_batched)
+    out.energy_se.assign(ne, 0.0), out.counts_se.assign(nc, 0.0);
+    if (r3d_node_run_batched(node, n, 0, seed, mission.JobErrorBatches, &out.total, out.energy_se.data(), out.counts_se.data()))
+      throw Runtime(r3d_last_error());
+    std::cout << "|  Batches: " << mission.JobErrorBatches << " over " << gpus << " shards\n";
   } else if (r3d_node_run(node, n, 0, seed, &out.total)) {
     throw Runtime(r3d_last_error());
   }
@@ -224,7 +232,9 @@ int main(int argc, char* argv[]) {
               << "scattermaps_{first,peakframe,peakcount}.u32, scattermaps_total.u64 and two first-arrival stills,\n"
               << "scattermaps_first_{above,elev}.u32\n"
               << "--error-batches=B (2..64, one device): the histories run as B id-partitioned batches and every bin's\n"
-              << "standard error is written to seis_NNN_err.octv beside seis_NNN.octv\n\n";
+              << "standard error is written to seis_NNN_err.octv beside seis_NNN.octv\n"
+              << "--job-error-batches=N: the same for a job on any number of shards (--gpus / --devices) -- the whole job is cut\n"
+              << "into N batches, N / shards (2..64) on every shard, and the shards' moments are merged on the GPU\n\n";
     return 0;
   }
   // A simulation run makes its tables where it uses them (seconds of host work and GBs of upload
@@ -262,7 +272,8 @@ int main(int argc, char* argv[]) {
       const std::vector<int>& devices = mission.Devices;
       if (mission.bRunSim && mission.ErrorBatches && devices.size() > 1)
         throw Runtime("--error-batches runs on one device: --gpus / --devices name " + std::to_string(devices.size()) +
-                      " shards (standard errors over several devices are not built: DESIGN.md section 5).");
+                      " shards (standard errors over several devices are not built: DESIGN.md section 5)." +
+                      "  --job-error-batches=N cuts the whole job into N batches over any number of shards.");
       if (mission.bRunSim && mission.ErrorBatches && report_mask)
         throw Runtime("--error-batches cannot be combined with --reports (the event log's launches run one at a time).");
       const GridJob grid = make_grid_job(mission, par);
@@ -307,8 +318,9 @@ int main(int argc, char* argv[]) {
         // seis_traces_asc.dat is opened in the CWD whatever --output-dir says (dataout.hpp:332)
         std::ofstream trace("seis_traces_asc.dat");
         OutputPostSimSummary(model, run.total, mission.OutputDir, std::cout, trace);
-        if (mission.ErrorBatches)
-          OutputSeismometerErrors(model, run.energy_se.data(), run.counts_se.data(), mission.ErrorBatches, mission.OutputDir);
+        if (mission.ErrorBatches || mission.JobErrorBatches)
+          OutputSeismometerErrors(model, run.energy_se.data(), run.counts_se.data(),
+                                  mission.ErrorBatches ? mission.ErrorBatches : mission.JobErrorBatches, mission.OutputDir);
       }
     }
   } catch (std::exception& e) {

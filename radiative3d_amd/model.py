@@ -222,6 +222,12 @@ class Model:
         return int(self._lib.r3dh_error_batches(self._h))
 
     @property
+    def job_error_batches(self):
+        """What --job-error-batches=N in the model's arguments asked for: the batches of the whole job, over whatever
+        shards --gpus / --devices name (0: absent)."""
+        return int(self._lib.r3dh_job_error_batches(self._h))
+
+    @property
     def scatter_views(self):
         """What --scatter-views[=GROUP] [--scatter-view-azimuth=AZI,HALFWIDTH] [--no-scatter-grid-file] asked for:
         None, or dict(group, azimuth, half_width, no_grid_file)."""
@@ -283,6 +289,89 @@ def batch_moments(batch_energy, batch_counts, batch_scalars=None, energy=None, c
     return energy, counts, scalars, energy_se, counts_se
 
 
+def _check_blocks(blocks, lead, what):
+    """[lead, ...] contiguous 8-byte tensors on one GPU, float64 first, 64-bit integers after it (None: skipped)."""
+    import torch
+    first = blocks[0]
+    for k, t in enumerate(blocks):
+        if t is None:
+            continue
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != 8 or t.shape[0] != lead or t.device != first.device:
+            raise ValueError(f"{what} must be contiguous 8-byte tensors [{lead}, ...] on one GPU")
+        if (k == 0 and t.dtype != torch.float64) or (k > 0 and t.dtype.is_floating_point):
+            raise ValueError(f"{what}: the energies are float64, counts and scalars 64-bit integers")
+
+
+def batch_partial(batch_energy, batch_counts, batch_scalars=None, stream=None):
+    """r3d_batch_partial on torch tensors of one device: a shard's half of a sharded job's standard errors.  The B batch
+    blocks as for batch_moments; returns (energy_sum, energy_ss, counts_sum, counts_ss, scalars_sum) -- every entry's sum
+    over the blocks and its sum of squared deviations from their mean (float64), scalars_sum None without
+    batch_scalars.  batch_merge finishes from the states of all shards (include/r3d.h has the estimator).
+    Asynchronous on `stream` (a raw hipStream_t; None: torch's current one)."""
+    import torch
+    lib = _ffi.hip_lib()
+    B = int(batch_energy.shape[0])
+    _check_blocks((batch_energy, batch_counts, batch_scalars), B, "batch blocks")
+    dev = batch_energy.device
+    ne, nc = batch_energy[0].numel(), batch_counts[0].numel()
+    energy_sum = torch.empty(batch_energy.shape[1:], dtype=torch.float64, device=dev)
+    energy_ss = torch.empty_like(energy_sum)
+    counts_sum = torch.empty(batch_counts.shape[1:], dtype=batch_counts.dtype, device=dev)
+    counts_ss = torch.empty(batch_counts.shape[1:], dtype=torch.float64, device=dev)
+    scalars_sum = None
+    if batch_scalars is not None:
+        scalars_sum = torch.empty(batch_scalars.shape[1:], dtype=batch_scalars.dtype, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.r3d_batch_partial(dev.index or 0, B, batch_energy.data_ptr(), ne, batch_counts.data_ptr(), nc,
+                               batch_scalars.data_ptr() if batch_scalars is not None else None,
+                               batch_scalars[0].numel() if batch_scalars is not None else 0,
+                               energy_sum.data_ptr(), energy_ss.data_ptr(), counts_sum.data_ptr(), counts_ss.data_ptr(),
+                               scalars_sum.data_ptr() if scalars_sum is not None else None, stream)
+    if rc:
+        raise RuntimeError("r3d_batch_partial failed: " + lib.r3d_last_error().decode())
+    return energy_sum, energy_ss, counts_sum, counts_ss, scalars_sum
+
+
+def batch_merge(energy_sum, energy_ss, counts_sum, counts_ss, n_batches, scalars_sum=None, energy=None, counts=None,
+                scalars=None, stream=None):
+    """r3d_batch_merge on torch tensors of one device: the states of D shards, stacked [D, ...] in shard order (what
+    batch_partial returned on each, n_batches blocks per shard), merged into the job's totals and the standard errors
+    of its D * n_batches batches.  Returns (energy, counts, scalars, energy_se, counts_se) as batch_moments does: the
+    totals ADDED into `energy` / `counts` / `scalars` (made and zeroed here when None).  Asynchronous on `stream`."""
+    import torch
+    lib = _ffi.hip_lib()
+    D = int(energy_sum.shape[0])
+    _check_blocks((energy_sum, counts_sum, scalars_sum), D, "shard sums")
+    dev = energy_sum.device
+    for t, like in ((energy_ss, energy_sum), (counts_ss, counts_sum)):
+        if t.dtype != torch.float64 or t.shape != like.shape or t.device != dev or not t.is_contiguous():
+            raise ValueError("the squared deviations must be contiguous float64 tensors shaped like their sums")
+    if energy is None:
+        energy = torch.zeros(energy_sum.shape[1:], dtype=torch.float64, device=dev)
+    if counts is None:
+        counts = torch.zeros(counts_sum.shape[1:], dtype=counts_sum.dtype, device=dev)
+    if scalars is None and scalars_sum is not None:
+        scalars = torch.zeros(scalars_sum.shape[1:], dtype=scalars_sum.dtype, device=dev)
+    ne, nc = energy_sum[0].numel(), counts_sum[0].numel()
+    for t, n in ((energy, ne), (counts, nc)):
+        if t.device != dev or not t.is_contiguous() or t.numel() != n or t.element_size() != 8:
+            raise ValueError("totals must be contiguous 8-byte tensors of a shard state's size on the states' GPU")
+    energy_se = torch.empty(energy_sum.shape[1:], dtype=torch.float64, device=dev)
+    counts_se = torch.empty(counts_sum.shape[1:], dtype=torch.float64, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.r3d_batch_merge(dev.index or 0, D, int(n_batches), energy_sum.data_ptr(), energy_ss.data_ptr(), ne,
+                             counts_sum.data_ptr(), counts_ss.data_ptr(), nc,
+                             scalars_sum.data_ptr() if scalars_sum is not None else None,
+                             scalars_sum[0].numel() if scalars_sum is not None else 0,
+                             energy.data_ptr(), counts.data_ptr(), scalars.data_ptr() if scalars is not None else None,
+                             energy_se.data_ptr(), counts_se.data_ptr(), stream)
+    if rc:
+        raise RuntimeError("r3d_batch_merge failed: " + lib.r3d_last_error().decode())
+    return energy, counts, scalars, energy_se, counts_se
+
+
 def run_model(model, n, first_id=0, seed=0x5EED, n_gpus=1, devices=None):
     """r3d_run_model: the whole seam in one call, sharded over devices 0 .. n_gpus-1 -- or, with
     `devices`, r3d_run_model_on: shard g on devices[g] (a device may be named more than once)."""
@@ -333,6 +422,29 @@ class Node:
             raise RuntimeError("r3d_node_run failed: " + self._lib.r3d_last_error().decode())
         res._from_c(c)
         return res
+
+    def run_batched(self, n, n_batches, first_id=0, seed=0x5EED, result=None):
+        """r3d_node_run_batched: the job's ids as n_batches id-partitioned batches, n_batches / len(self) (2..64) of
+        them on every shard; the shards' moments are merged on the GPU.  Returns (Result, energy_se, counts_se) as
+        Engine.run_batched does -- the job's totals (ADDED into `result` when one is given) and the standard error of
+        every energy and count entry from the spread of all n_batches batches."""
+        res = result if result is not None else self.model.new_result()
+        shape = (self.model.n_seismometers, self.model.n_bins)
+        ese = np.zeros(shape + (_ffi.R3D_N_ENERGY,))
+        cse = np.zeros(shape + (_ffi.R3D_N_COUNT,))
+        c = res._as_c()
+        if self._lib.r3d_node_run_batched(self._n, n, first_id, seed, n_batches, C.byref(c), ese.ctypes.data_as(_ffi._dp),
+                                          cse.ctypes.data_as(_ffi._dp)):
+            raise RuntimeError("r3d_node_run_batched failed: " + self._lib.r3d_last_error().decode())
+        res._from_c(c)
+        return res, ese, cse
+
+    def engine(self, shard):
+        """r3d_node_engine: shard g's engine as a raw handle for the library's calls (it stays the node's)."""
+        e = self._lib.r3d_node_engine(self._n, int(shard))
+        if not e:
+            raise IndexError(shard)
+        return e
 
     def close(self):
         if self._n:

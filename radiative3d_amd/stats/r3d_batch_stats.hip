@@ -1,11 +1,14 @@
 // r3d_batch_stats.hip -- per-bin standard errors from id-partitioned batches (include/r3d.h r3d_batch_moments,
-// r3d_run_device_batched, r3d_run_batched).
+// r3d_run_device_batched, r3d_run_batched; for a job sharded over several devices r3d_batch_partial, r3d_batch_merge,
+// r3d_node_run_batched).
 //
 // A run of ids [first_id, first_id + n) is cut into B contiguous batches; each is one self-contained
 // r3d_run_device launch into its own zeroed block.  Histories are keyed by id, so the blocks are independent
 // samples of one distribution and the spread of a bin over them gives the standard error of the bin's total
 // (batch means; the per-entry arithmetic is r3d_batch_moments.h).  The moments are taken where the blocks live:
-// one streaming kernel over [B][len] in HBM instead of B copies to the host.
+// one streaming kernel over [B][len] in HBM instead of B copies to the host.  A job of D shards is D * B batches: every
+// shard stops that kernel before the root (its sum S and its sum of squared deviations ss), the D pairs travel to
+// shard 0's device, and one kernel there finishes (within-shard plus between-shard deviations).
 //
 // This file stands ON TOP of the engine: it calls only what include/r3d.h declares and owns the streams and
 // events it overlaps the batches with; nothing in csrc/ knows about it.
@@ -52,6 +55,74 @@ __global__ __launch_bounds__(kMomentsBlock) void batch_moments_u64_kernel(const 
     batch_moments_u64(x + i, len, n_batches, &total, &se);
     total_out[i] += total;
     if (se_out) se_out[i] = se;
+  }
+}
+
+// A shard's half of a sharded job: the same loads in the same order, the sum and the squared deviations WRITTEN
+// (ss_out may be NULL: the scalars have no se).
+__global__ __launch_bounds__(kMomentsBlock) void batch_partial_f64_kernel(const double* __restrict__ x, uint64_t len,
+                                                                          uint32_t n_batches, double* __restrict__ sum_out,
+                                                                          double* __restrict__ ss_out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += stride) {
+    double sum, ss;
+    batch_partial_f64(x + i, len, n_batches, &sum, &ss);
+    sum_out[i] = sum;
+    if (ss_out) ss_out[i] = ss;
+  }
+}
+
+__global__ __launch_bounds__(kMomentsBlock) void batch_partial_u64_kernel(const uint64_t* __restrict__ x, uint64_t len,
+                                                                          uint32_t n_batches, uint64_t* __restrict__ sum_out,
+                                                                          double* __restrict__ ss_out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += stride) {
+    uint64_t sum;
+    double ss;
+    batch_partial_u64(x + i, len, n_batches, &sum, &ss);
+    sum_out[i] = sum;
+    if (ss_out) ss_out[i] = ss;
+  }
+}
+
+// The root's half: D shard states, shard g's entry i at [g * shard_stride + i] (the lanes of a wave read 64 consecutive
+// entries of one shard), merged in shard order.  total_out += T; se_out = (NULL: `ss` is not read, a plain sum).
+__global__ __launch_bounds__(kMomentsBlock) void batch_merge_f64_kernel(const double* __restrict__ sum,
+                                                                        const double* __restrict__ ss, uint64_t shard_stride,
+                                                                        uint64_t len, uint32_t n_shards, uint32_t n_batches,
+                                                                        double* __restrict__ total_out,
+                                                                        double* __restrict__ se_out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += stride) {
+    double total, se;
+    if (se_out) {
+      batch_merge_f64(sum + i, ss + i, shard_stride, n_shards, n_batches, &total, &se);
+      se_out[i] = se;
+    } else {
+      total = 0.0;
+      for (uint32_t g = 0; g < n_shards; g++) total += sum[(uint64_t)g * shard_stride + i];
+    }
+    total_out[i] += total;
+  }
+}
+
+__global__ __launch_bounds__(kMomentsBlock) void batch_merge_u64_kernel(const uint64_t* __restrict__ sum,
+                                                                        const double* __restrict__ ss, uint64_t shard_stride,
+                                                                        uint64_t len, uint32_t n_shards, uint32_t n_batches,
+                                                                        uint64_t* __restrict__ total_out,
+                                                                        double* __restrict__ se_out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += stride) {
+    uint64_t total;
+    if (se_out) {
+      double se;
+      batch_merge_u64(sum + i, ss + i, shard_stride, n_shards, n_batches, &total, &se);
+      se_out[i] = se;
+    } else {
+      total = 0;
+      for (uint32_t g = 0; g < n_shards; g++) total += sum[(uint64_t)g * shard_stride + i];
+    }
+    total_out[i] += total;
   }
 }
 
@@ -124,6 +195,42 @@ int enqueue_moments(uint32_t n_batches, const double* d_batch_energy, uint64_t n
   return err == hipSuccess ? 0 : refuse("r3d_batch_moments", err);
 }
 
+int enqueue_partial(uint32_t n_batches, const double* d_batch_energy, uint64_t n_energy, const uint64_t* d_batch_counts,
+                    uint64_t n_counts, const uint64_t* d_batch_scalars, uint64_t n_scalars, double* d_energy_sum,
+                    double* d_energy_ss, uint64_t* d_counts_sum, double* d_counts_ss, uint64_t* d_scalars_sum, hipStream_t s) {
+  if (n_energy)
+    batch_partial_f64_kernel<<<dim3(moments_grid(n_energy)), dim3(kMomentsBlock), 0, s>>>(d_batch_energy, n_energy, n_batches,
+                                                                                       d_energy_sum, d_energy_ss);
+  if (n_counts)
+    batch_partial_u64_kernel<<<dim3(moments_grid(n_counts)), dim3(kMomentsBlock), 0, s>>>(d_batch_counts, n_counts, n_batches,
+                                                                                       d_counts_sum, d_counts_ss);
+  if (d_batch_scalars && n_scalars)
+    batch_partial_u64_kernel<<<dim3(moments_grid(n_scalars)), dim3(kMomentsBlock), 0, s>>>(d_batch_scalars, n_scalars, n_batches,
+                                                                                        d_scalars_sum, nullptr);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : refuse("r3d_batch_partial", err);
+}
+
+// (shard_stride: entries from one shard's state to the next -- the array's own length for the [D][len] arrays of the
+//  C-ABI, a whole record where the node keeps a shard's five arrays together)
+int enqueue_merge(uint32_t n_shards, uint32_t n_batches, uint64_t shard_stride_e, uint64_t shard_stride_c,
+                  uint64_t shard_stride_s, const double* d_energy_sum, const double* d_energy_ss, uint64_t n_energy,
+                  const uint64_t* d_counts_sum, const double* d_counts_ss, uint64_t n_counts, const uint64_t* d_scalars_sum,
+                  uint64_t n_scalars, double* d_energy, uint64_t* d_counts, uint64_t* d_scalars, double* d_energy_se,
+                  double* d_counts_se, hipStream_t s) {
+  if (n_energy)
+    batch_merge_f64_kernel<<<dim3(moments_grid(n_energy)), dim3(kMomentsBlock), 0, s>>>(
+        d_energy_sum, d_energy_ss, shard_stride_e, n_energy, n_shards, n_batches, d_energy, d_energy_se);
+  if (n_counts)
+    batch_merge_u64_kernel<<<dim3(moments_grid(n_counts)), dim3(kMomentsBlock), 0, s>>>(
+        d_counts_sum, d_counts_ss, shard_stride_c, n_counts, n_shards, n_batches, d_counts, d_counts_se);
+  if (d_scalars_sum && n_scalars)
+    batch_merge_u64_kernel<<<dim3(moments_grid(n_scalars)), dim3(kMomentsBlock), 0, s>>>(
+        d_scalars_sum, nullptr, shard_stride_s, n_scalars, n_shards, n_batches, d_scalars, nullptr);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : refuse("r3d_batch_merge", err);
+}
+
 // What a batched run cannot be combined with, asked of the engine through its public calls.
 int refuse_engine_state(r3d_engine* e, const char* who) {
   if (r3d_engine_carry_pending(e))
@@ -143,6 +250,49 @@ int check_batches(const char* who, uint64_t n, uint32_t n_batches) {
   if (n < n_batches)
     return refuse(who, "fewer histories (" + std::to_string(n) + ") than batches (" + std::to_string(n_batches) + ")");
   return 0;
+}
+
+// Batches [j0, j0 + B) of a job of N batches over the ids [first_id, first_id + n), batch j0 + k into block k of `be`,
+// `bc`, `bs` (zeroed on `s` by the caller): ordered behind what `s` holds now, round-robin over the device's lanes so
+// that a batch's drain phase overlaps the batches behind it, and joined back into `s` -- also when a launch was
+// refused: whatever was enqueued is waited for by `s`.  floor(j n / N) is taken as j (n / N) + floor(j (n % N) / N):
+// no product here passes N^2.  The caller holds g_lanes_lock and has the engine's device current.
+int enqueue_batches(const char* who, r3d_engine* e, Lanes* lanes, uint64_t n, uint64_t first_id, uint64_t seed, uint64_t j0,
+                    uint64_t B, uint64_t N, double* be, uint64_t* bc, uint64_t* bs, uint64_t ne, uint64_t nc, uint64_t ns,
+                    hipStream_t s) {
+  hipError_t err = hipEventRecord(lanes->begin, s);
+  for (int k = 0; k < kStreams && err == hipSuccess; k++) err = hipStreamWaitEvent(lanes->stream[k], lanes->begin, 0);
+  int rc = err == hipSuccess ? 0 : refuse(who, err);
+  for (uint64_t k = 0; k < B && rc == 0; k++) {
+    const uint64_t j = j0 + k;
+    const uint64_t lo = j * (n / N) + j * (n % N) / N, hi = (j + 1) * (n / N) + (j + 1) * (n % N) / N;
+    rc = r3d_run_device(e, hi - lo, first_id + lo, seed, be + k * ne, bc + k * nc, bs + k * ns, nullptr,
+                        lanes->stream[k % kStreams]);   // (its message stands)
+  }
+  for (int k = 0; k < kStreams; k++) {
+    hipError_t j = hipEventRecord(lanes->done[k], lanes->stream[k]);
+    if (j == hipSuccess) j = hipStreamWaitEvent(s, lanes->done[k], 0);
+    if (j != hipSuccess && rc == 0) rc = refuse(who, j);
+  }
+  return rc;
+}
+
+// The engine's device, learned from an address it owns: the only one the interface hands out is its event grid's,
+// so an engine without a grid gets one of a single cell for the length of the question.  -1 with the message set.
+int engine_device(r3d_engine* e, const char* who) {
+  int device = -1;
+  if (r3d_volume_len(e)) {
+    device = device_of(r3d_volume_device_ptr(e));
+  } else {
+    r3d_volume_desc one{};
+    one.cell_size[0] = one.cell_size[1] = one.cell_size[2] = 1.0, one.dims[0] = one.dims[1] = one.dims[2] = 1;
+    one.n_frames = 1, one.frame_dt = 1.0;
+    if (r3d_engine_set_volume(e, &one)) return -1;
+    device = device_of(r3d_volume_device_ptr(e));
+    if (r3d_engine_set_volume(e, nullptr)) return -1;
+  }
+  if (device < 0) refuse(who, "the engine's device could not be determined");
+  return device;
 }
 
 }  // namespace
@@ -197,22 +347,9 @@ int r3d_run_device_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_
   hipError_t err = hipMemsetAsync(scratch, 0, (own_e + own_c + B * ns) * 8, s);
   if (err == hipSuccess && d_batch_energy && ne) err = hipMemsetAsync(be, 0, B * ne * 8, s);
   if (err == hipSuccess && d_batch_counts && nc) err = hipMemsetAsync(bc, 0, B * nc * 8, s);
-  if (err == hipSuccess) err = hipEventRecord(lanes->begin, s);
-  for (int k = 0; k < kStreams && err == hipSuccess; k++) err = hipStreamWaitEvent(lanes->stream[k], lanes->begin, 0);
-  int rc = err == hipSuccess ? 0 : refuse(who, err);
-  // batch j: ids [first_id + floor(j n / B), first_id + floor((j + 1) n / B)), round-robin over the streams so that a
-  // batch's drain phase overlaps the batches behind it
-  for (uint64_t j = 0; j < B && rc == 0; j++) {
-    const uint64_t lo = j * (n / B) + j * (n % B) / B, hi = (j + 1) * (n / B) + (j + 1) * (n % B) / B;
-    rc = r3d_run_device(e, hi - lo, first_id + lo, seed, be + j * ne, bc + j * nc, bs + j * ns, nullptr,
-                        lanes->stream[j % kStreams]);   // (its message stands)
-  }
-  // join: whatever was enqueued is waited for by the caller's stream, also when a launch was refused
-  for (int k = 0; k < kStreams; k++) {
-    hipError_t j = hipEventRecord(lanes->done[k], lanes->stream[k]);
-    if (j == hipSuccess) j = hipStreamWaitEvent(s, lanes->done[k], 0);
-    if (j != hipSuccess && rc == 0) rc = refuse(who, j);
-  }
+  // batch j: ids [first_id + floor(j n / B), first_id + floor((j + 1) n / B))
+  int rc = err == hipSuccess ? enqueue_batches(who, e, lanes, n, first_id, seed, 0, B, B, be, bc, bs, ne, nc, ns, s)
+                             : refuse(who, err);
   if (rc == 0)
     rc = enqueue_moments(n_batches, be, ne, bc, nc, bs, ns, d_energy, d_counts, d_scalars, d_energy_se, d_counts_se, s);
   if (hipError_t f = hipFreeAsync(scratch, s); f != hipSuccess && rc == 0) rc = refuse(who, f);
@@ -226,20 +363,8 @@ int r3d_run_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed,
   if (!out || !out->energy || !out->counts) return g_error = "null result", 1;
   if (check_batches(who, n, n_batches)) return 1;
   if (refuse_engine_state(e, who)) return 1;
-  // The engine's device, learned from an address it owns: the only one the interface hands out is its event grid's,
-  // so an engine without a grid gets one of a single cell for the length of the question.
-  int device = -1;
-  if (r3d_volume_len(e)) {
-    device = device_of(r3d_volume_device_ptr(e));
-  } else {
-    r3d_volume_desc one{};
-    one.cell_size[0] = one.cell_size[1] = one.cell_size[2] = 1.0, one.dims[0] = one.dims[1] = one.dims[2] = 1;
-    one.n_frames = 1, one.frame_dt = 1.0;
-    if (r3d_engine_set_volume(e, &one)) return 1;
-    device = device_of(r3d_volume_device_ptr(e));
-    if (r3d_engine_set_volume(e, nullptr)) return 1;
-  }
-  if (device < 0) return refuse(who, "the engine's device could not be determined");
+  const int device = engine_device(e, who);
+  if (device < 0) return 1;
   OnDevice on(device);
   if (on.status != hipSuccess) return refuse(who, on.status);
   const size_t ne = r3d_energy_len(e), nc = r3d_counts_len(e), ns = R3D_N_SCALARS;
@@ -265,6 +390,191 @@ int r3d_run_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed,
     (void)hipStreamDestroy(s);
   }
   if (rc) return rc;
+  const double* const he = reinterpret_cast<const double*>(host.data());
+  const uint64_t* const hc = host.data() + ne;
+  const uint64_t* const hs = hc + nc;
+  const double* const hese = reinterpret_cast<const double*>(hs + ns);
+  for (size_t i = 0; i < ne; i++) out->energy[i] += he[i];
+  for (size_t i = 0; i < nc; i++) out->counts[i] += hc[i];
+  out->n_lost += hs[0], out->n_timeout += hs[1], out->n_invalid += hs[2];
+  for (int r = 0; r < R3D_INV_NUM; r++) out->invalid_reasons[r] += hs[3 + r];
+  for (int k = 0; k < R3D_EV_NUM; k++) out->events[k] += hs[3 + R3D_INV_NUM + k];
+  if (energy_se)
+    for (size_t i = 0; i < ne; i++) energy_se[i] = hese[i];
+  if (counts_se)
+    for (size_t i = 0; i < nc; i++) counts_se[i] = hese[ne + i];
+  return 0;
+}
+
+int r3d_batch_partial(int device, uint32_t n_batches, const double* d_batch_energy, uint64_t n_energy,
+                      const uint64_t* d_batch_counts, uint64_t n_counts, const uint64_t* d_batch_scalars, uint64_t n_scalars,
+                      double* d_energy_sum, double* d_energy_ss, uint64_t* d_counts_sum, double* d_counts_ss,
+                      uint64_t* d_scalars_sum, void* stream) {
+  if (n_batches < 2 || n_batches > kMaxBatches)
+    return g_error = "r3d_batch_partial: the number of batches must be 2 .. 64, got " + std::to_string(n_batches), 1;
+  if ((n_energy && (!d_batch_energy || !d_energy_sum || !d_energy_ss)) ||
+      (n_counts && (!d_batch_counts || !d_counts_sum || !d_counts_ss)) || (d_batch_scalars && n_scalars && !d_scalars_sum))
+    return g_error = "r3d_batch_partial: null argument", 1;
+  OnDevice on(device);
+  if (on.status != hipSuccess) return refuse("r3d_batch_partial", "no HIP device (or a bad device index)");
+  return enqueue_partial(n_batches, d_batch_energy, n_energy, d_batch_counts, n_counts, d_batch_scalars, n_scalars,
+                         d_energy_sum, d_energy_ss, d_counts_sum, d_counts_ss, d_scalars_sum,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
+int r3d_batch_merge(int device, uint32_t n_shards, uint32_t n_batches, const double* d_energy_sum, const double* d_energy_ss,
+                    uint64_t n_energy, const uint64_t* d_counts_sum, const double* d_counts_ss, uint64_t n_counts,
+                    const uint64_t* d_scalars_sum, uint64_t n_scalars, double* d_energy, uint64_t* d_counts,
+                    uint64_t* d_scalars, double* d_energy_se, double* d_counts_se, void* stream) {
+  if (n_shards == 0) return g_error = "r3d_batch_merge: no shard to merge (n_shards == 0)", 1;
+  if (n_batches < 2 || n_batches > kMaxBatches)
+    return g_error = "r3d_batch_merge: the number of batches of a shard must be 2 .. 64, got " + std::to_string(n_batches), 1;
+  if ((n_energy && (!d_energy_sum || !d_energy)) || (n_counts && (!d_counts_sum || !d_counts)) ||
+      (d_scalars_sum && n_scalars && !d_scalars))
+    return g_error = "r3d_batch_merge: null argument", 1;
+  if ((n_energy && d_energy_se && !d_energy_ss) || (n_counts && d_counts_se && !d_counts_ss))
+    return g_error = "r3d_batch_merge: a standard error is asked for without the shards' squared deviations", 1;
+  OnDevice on(device);
+  if (on.status != hipSuccess) return refuse("r3d_batch_merge", "no HIP device (or a bad device index)");
+  return enqueue_merge(n_shards, n_batches, n_energy, n_counts, n_scalars, d_energy_sum, d_energy_ss, n_energy, d_counts_sum,
+                       d_counts_ss, n_counts, d_scalars_sum, n_scalars, d_energy, d_counts, d_scalars, d_energy_se,
+                       d_counts_se, reinterpret_cast<hipStream_t>(stream));
+}
+
+int r3d_node_run_batched(r3d_node* node, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches, r3d_result* out,
+                         double* energy_se, double* counts_se) {
+  const char* const who = "r3d_node_run_batched";
+  if (!node) return g_error = "null node", 1;
+  if (!out || !out->energy || !out->counts) return g_error = "null result", 1;
+  const uint32_t D = (uint32_t)r3d_node_size(node);
+  if (D == 0) return refuse(who, "a node without shards");
+  if (n_batches % D)
+    return refuse(who, "the job's " + std::to_string(n_batches) + " batches are not a multiple of the node's " +
+                           std::to_string(D) + " shards (every shard runs the same number)");
+  const uint32_t B = n_batches / D;
+  if (B < 2)
+    return refuse(who, "at least 2 batches per shard are needed (got " + std::to_string(n_batches) + " over " +
+                           std::to_string(D) + " shards)");
+  if (B > kMaxBatches)
+    return refuse(who, "at most 64 batches per shard (an engine's launches in flight), got " + std::to_string(n_batches) +
+                           " over " + std::to_string(D) + " shards");
+  if (n < n_batches)
+    return refuse(who, "fewer histories (" + std::to_string(n) + ") than batches (" + std::to_string(n_batches) + ")");
+  std::vector<r3d_engine*> engines(D);
+  for (uint32_t g = 0; g < D; g++) {
+    engines[g] = r3d_node_engine(node, (int)g);
+    if (!engines[g]) return 1;
+    if (refuse_engine_state(engines[g], who)) return g_error = "shard " + std::to_string(g) + ": " + g_error, 1;
+  }
+  const uint64_t ne = r3d_energy_len(engines[0]), nc = r3d_counts_len(engines[0]), ns = R3D_N_SCALARS;
+  // a shard's state as it travels, one record: S and ss of the energies, S and ss of the counts, S of the scalars
+  const uint64_t rec = 2 * ne + 2 * nc + ns;
+
+  // What a shard holds for the length of the call; released -- after everything enqueued on it has run out -- on
+  // every way out of the function.
+  struct Shard {
+    int device = -1;
+    hipStream_t s = nullptr;
+    hipEvent_t ready = nullptr;
+    void* blocks = nullptr;   // [B][ne] energies, [B][nc] counts, [B][ns] scalars
+    void* state = nullptr;    // one record
+  };
+  struct Shards {
+    std::vector<Shard> v;
+    void* root = nullptr;     // on shard 0's device: [D] records, then the job's totals and the two se arrays
+    ~Shards() {
+      for (Shard& sh : v) {
+        if (sh.device < 0) continue;
+        OnDevice on(sh.device);
+        if (sh.s) (void)hipStreamSynchronize(sh.s);
+      }
+      for (Shard& sh : v) {
+        if (sh.device < 0) continue;
+        OnDevice on(sh.device);
+        if (sh.ready) (void)hipEventDestroy(sh.ready);
+        if (sh.s) (void)hipStreamDestroy(sh.s);
+        if (sh.blocks) (void)hipFree(sh.blocks);
+        if (sh.state) (void)hipFree(sh.state);
+      }
+      if (root && !v.empty() && v[0].device >= 0) {
+        OnDevice on(v[0].device);
+        (void)hipFree(root);
+      }
+    }
+  } shards;
+  shards.v.resize(D);
+  for (uint32_t g = 0; g < D; g++) {
+    const int device = engine_device(engines[g], who);
+    if (device < 0) return 1;
+    shards.v[g].device = device;
+  }
+
+  // every shard: its B batches into its own zeroed blocks, reduced where they lie to (S_g, ss_g)
+  for (uint32_t g = 0; g < D; g++) {
+    Shard& sh = shards.v[g];
+    OnDevice on(sh.device);
+    if (on.status != hipSuccess) return refuse(who, on.status);
+    const uint64_t block_words = (uint64_t)B * (ne + nc + ns);
+    hipError_t err = hipStreamCreateWithFlags(&sh.s, hipStreamNonBlocking);
+    if (err == hipSuccess) err = hipEventCreateWithFlags(&sh.ready, hipEventDisableTiming);
+    if (err == hipSuccess) err = hipMalloc(&sh.blocks, block_words * 8);
+    if (err == hipSuccess) err = hipMalloc(&sh.state, rec * 8);
+    if (err == hipSuccess) err = hipMemsetAsync(sh.blocks, 0, block_words * 8, sh.s);
+    if (err != hipSuccess) return refuse(who, err, ("shard " + std::to_string(g)).c_str());
+    double* const be = static_cast<double*>(sh.blocks);
+    uint64_t* const bc = reinterpret_cast<uint64_t*>(be + (uint64_t)B * ne);
+    uint64_t* const bs = bc + (uint64_t)B * nc;
+    double* const st_e = static_cast<double*>(sh.state);
+    uint64_t* const st_c = reinterpret_cast<uint64_t*>(st_e + 2 * ne);
+    uint64_t* const st_s = st_c + 2 * nc;
+    int rc;
+    {
+      std::lock_guard<std::mutex> lock(g_lanes_lock);
+      Lanes* lanes = nullptr;
+      if (hipError_t l = lanes_for(sh.device, &lanes); l != hipSuccess) return refuse(who, l);
+      rc = enqueue_batches(who, engines[g], lanes, n, first_id, seed, (uint64_t)g * B, B, n_batches, be, bc, bs, ne, nc, ns,
+                           sh.s);
+    }
+    if (rc == 0)
+      rc = enqueue_partial(B, be, ne, bc, nc, bs, ns, st_e, st_e + ne, st_c, reinterpret_cast<double*>(st_c + nc), st_s, sh.s);
+    if (rc == 0)
+      if (hipError_t r = hipEventRecord(sh.ready, sh.s); r != hipSuccess) rc = refuse(who, r);
+    if (rc) return g_error = "shard " + std::to_string(g) + " (device " + std::to_string(sh.device) + "): " + g_error, 1;
+  }
+
+  // the records travel to shard 0's device, each behind its shard's reduction; the merge follows them on that stream
+  const Shard& root = shards.v[0];
+  const uint64_t result_words = 2 * ne + 2 * nc + ns;   // totals (energy, counts, scalars), then the two se arrays
+  std::vector<uint64_t> host(result_words);
+  {
+    OnDevice on(root.device);
+    if (on.status != hipSuccess) return refuse(who, on.status);
+    hipError_t err = hipMalloc(&shards.root, ((uint64_t)D * rec + result_words) * 8);
+    if (err != hipSuccess) return shards.root = nullptr, refuse(who, err);
+    uint64_t* const gathered = static_cast<uint64_t*>(shards.root);
+    uint64_t* const result = gathered + (uint64_t)D * rec;
+    err = hipMemsetAsync(result, 0, result_words * 8, root.s);
+    for (uint32_t g = 0; g < D && err == hipSuccess; g++) {
+      err = hipStreamWaitEvent(root.s, shards.v[g].ready, 0);
+      if (err == hipSuccess)
+        err = hipMemcpyPeerAsync(gathered + (uint64_t)g * rec, root.device, shards.v[g].state, shards.v[g].device, rec * 8,
+                                 root.s);
+    }
+    if (err != hipSuccess) return refuse(who, err);
+    const double* const g_e = reinterpret_cast<const double*>(gathered);
+    const uint64_t* const g_c = gathered + 2 * ne;
+    double* const r_e = reinterpret_cast<double*>(result);
+    uint64_t* const r_c = result + ne;
+    uint64_t* const r_s = r_c + nc;
+    double* const r_ese = reinterpret_cast<double*>(r_s + ns);
+    if (enqueue_merge(D, B, rec, rec, rec, g_e, g_e + ne, ne, g_c, reinterpret_cast<const double*>(g_c + nc), nc,
+                      g_c + 2 * nc, ns, r_e, r_c, r_s, r_ese, r_ese + ne, root.s))
+      return 1;
+    err = hipStreamSynchronize(root.s);
+    if (err == hipSuccess) err = hipMemcpy(host.data(), result, result_words * 8, hipMemcpyDeviceToHost);
+    if (err != hipSuccess) return refuse(who, err);
+  }
+  // (nothing was added to *out until every shard had run and the merged block was read)
   const double* const he = reinterpret_cast<const double*>(host.data());
   const uint64_t* const hc = host.data() + ne;
   const uint64_t* const hs = hc + nc;
