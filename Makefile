@@ -36,12 +36,12 @@ COMMON   := radiative3d_amd/common
 HOST_SRC := $(HOSTDIR)/ecs.cpp $(HOSTDIR)/grid.cpp $(HOSTDIR)/model.cpp \
             $(HOSTDIR)/models_builtin.cpp $(HOSTDIR)/cmdline.cpp $(HOSTDIR)/dataout.cpp \
             $(HOSTDIR)/capi.cpp
-HOST_HDR := $(wildcard $(HOSTDIR)/*.hpp) include/r3d.h include/r3d_host.h
+HOST_HDR := $(wildcard $(HOSTDIR)/*.hpp) include/r3d.h include/r3d_host.h radiative3d_amd/stats/r3d_window_sums.h
 ENGINE_SRC := $(CSRC)/r3d_engine.hip $(CSRC)/r3d_tables_build.hip $(CSRC)/r3d_kernels_kind.hip $(CSRC)/r3d_volume.hip
 ENGINE_HDR := $(wildcard $(CSRC)/*.h) include/r3d.h
 # The add-ons: what stands beside the engine on its C-ABI, each a directory radiative3d_amd/<name>/ of ONE .hip and
 # its headers, which includes $(COMMON)/r3d_entry.h and include/r3d.h and nothing from csrc/.  A new one is a word here.
-#   stats  per-bin standard errors from batches (r3d_batch_moments, r3d_run_device_batched)
+#   stats  per-bin standard errors from batches (r3d_batch_moments, r3d_run_device_batched), lapse-window sums (r3d_window_sums)
 #   views  the two video views of the scatter-event grid (r3d_volume_project, r3d_volume_range_bins)
 #   maps   the grid reduced along its frame axis: arrival-time, peak and total maps (r3d_volume_time_maps)
 ADDONS := stats views maps

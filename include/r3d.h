@@ -729,6 +729,61 @@ int r3d_batch_merge(int device, uint32_t n_shards, uint32_t n_batches,
 int r3d_node_run_batched(r3d_node* node, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
                          r3d_result* out, double* energy_se, double* counts_se);
 
+/* ---- lapse-window energies with batch standard errors ------------------------------
+ * What vis/seisplot/lapsetimecurve.m takes from a finished run -- the energy in a window of bins behind a phase edge,
+ * per seismometer, and the two coda ratios R1, R2 made of such sums -- with error bars.  A window sum's standard error
+ * cannot be made from the per-bin errors (the bins of one batch are correlated): it comes from the batches' own window
+ * sums, so the windows are summed on the device where the batch blocks lie, and r3d_batch_moments turns the
+ * batch-major block of sums into T and se like any other.  radiative3d_amd/stats/r3d_window_sums.h has the arithmetic:
+ *     THE BIN RULE (r3d_window_bins, host only): seismometer at distance r, phase edge (v, t0), window o .. e seconds
+ *       behind it, bins of dt:  t_begin = t0 + r / v + o,  begin = max(1, ceil(t_begin / dt)) - 1,
+ *       end = begin + floor((e - o) / dt + 0.5); end clipped to n_bins, begin to end, *clipped says so (may be NULL).
+ *       Refused: a null out, dt <= 0, v <= 0, e < o, n_bins == 0, anything not finite.
+ *     THE WINDOW SUM of one block over bins [begin, end) with component weights w[5] over (X, Y, Z, P, S):
+ *       e_b = (((w0 x_b0 + w1 x_b1) + w2 x_b2) + w3 x_b3) + w4 x_b4, no multiply fused into an add; 64 interleaved
+ *       strands p_l = e_(begin+l) + e_(begin+l+64) + ... from +0.0; then p_l += p_(l+h) for l < h, h = 32 .. 1; Y = p_0.
+ *       The same bits on every run, machine and launch geometry;  |Y - exact| <= d u / (1 - d u) sum |w_c x_bc| with
+ *       d = ceil((end - begin) / 64) + 10.  Window counts are exact u64 sums per wave type.
+ *     THE JACKKNIFE (r3d_window_log_ratio, host only) of theta = log10(sum_j a_j / sum_j b_j) over N batch values
+ *       `stride` doubles apart: leave-one-out sums taken directly, theta_(j) = log10(A_(j) / B_(j)) with mean m,
+ *       se = sqrt((N-1)/N sum_j (theta_(j) - m)^2).  theta and se are NaN if any full or leave-one-out sum is not
+ *       positive; N == 1 gives theta and se = NaN.  Refused: a null argument, N == 0, stride == 0.
+ *
+ * r3d_window_sums: device level, like r3d_batch_moments -- B >= 1 batch-major blocks d_batch_energy [B][n_seis][n_bins][5]
+ * (and d_batch_counts [B][n_seis][n_bins][2], or NULL) on `device`, only read; one plain result block is B = 1.
+ * d_window_energy [B][n_seis][n_windows] and d_window_counts [B][n_seis][n_windows][2] (or NULL) are WRITTEN, every entry
+ * by one group of work-items: no two writers, nothing added across groups, fixed order.  Windows may overlap and may be
+ * empty (begin == end gives +0.0 and no counts).  The bins lie on the device and cannot be checked by the call: a pair with
+ * begin > end or end > n_bins is never read through, contributes 0, and d_bad (one uint64 on the device, or NULL) is
+ * WRITTEN with the number of such pairs among the spec's n_seis * n_windows.  Asynchronous on `stream`.
+ * REFUSED (non-zero, r3d_last_error, nothing enqueued, no buffer touched; all checked before any HIP call): a null
+ * blocks pointer, spec, bins or d_window_energy, a size mismatch, n_batches == 0, n_seismometers == 0, n_bins == 0,
+ * n_windows == 0, a weight that is not finite, d_window_counts without d_batch_counts.
+ *
+ * r3d_run_batched_windows: r3d_run_batched (same arguments, refusals, out / energy_se / counts_se) that keeps its batch
+ * blocks on the device, sums the windows of *w there -- for THIS call w->d_bins is a HOST array, checked here: a pair
+ * with begin > end or end > n_bins is refused, as is a spec whose n_seismometers / n_bins are not the model's -- and
+ * reads back only the small arrays: window_energy [S][W] and window_counts [S][W][2] (may be NULL) are ADDED into,
+ * window_se [S][W] is WRITTEN, batch_window_energy [B][S][W] (may be NULL; the jackknife's input) is WRITTEN.  A refusal
+ * touches nothing.  A job sharded over several devices (r3d_node_run_batched) has no windows call: out of scope.       */
+typedef struct r3d_window_spec {
+  uint32_t size;                    /* sizeof(r3d_window_spec): a mismatch is refused          */
+  uint32_t n_seismometers, n_bins;
+  uint32_t n_windows;               /* windows per seismometer, >= 1                           */
+  const uint32_t* d_bins;           /* [n_seis][n_windows][2] begin, end; device               */
+  double weight[R3D_N_ENERGY];
+} r3d_window_spec;
+int r3d_window_sums(int device, uint32_t n_batches, const double* d_batch_energy, const uint64_t* d_batch_counts,
+                    const r3d_window_spec* w, double* d_window_energy, uint64_t* d_window_counts, uint64_t* d_bad,
+                    void* stream);
+int r3d_window_bins(double dt, uint32_t n_bins, double r, double v, double t0, double o, double e, uint32_t out[2],
+                    int* clipped);
+int r3d_window_log_ratio(uint32_t n, const double* a, const double* b, uint64_t stride, double* theta, double* se);
+int r3d_run_batched_windows(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                            r3d_result* out, double* energy_se, double* counts_se, const r3d_window_spec* w,
+                            double* window_energy, uint64_t* window_counts, double* window_se,
+                            double* batch_window_energy);
+
 /* Self-test hook: evaluates one of the kernel's own elementary functions
  * (radiative3d_amd/csrc/r3d_math.h -- the traversal uses these instead of the
  * device library's exp / log / atanh / asin / atan2 / sincos) on the device,

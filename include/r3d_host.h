@@ -101,6 +101,50 @@ typedef struct r3dh_maps_header {
 int r3dh_scatter_maps(const r3dh_model* m, uint32_t* min_count);
 int r3dh_write_maps_header(const r3dh_maps_header* h, const char* path);
 
+/* --lapse-windows[=V,T0,B1,E1,B2,E2] [--lapse-axes=X,Y,Z] [--lapse-geospread=G] [--lapse-ranges=R0,RA,RB]
+ * [--lapse-array=FIRST,LAST] in the model's arguments (the last four refused without the first, the first without
+ * --error-batches and with --job-error-batches): the lapse-time curves and coda ratios of vis/seisplot/lapsetimecurve.m
+ * with error bars from the batches (r3d.h r3d_run_batched_windows).
+ * r3dh_lapse_request: returns 1 and fills *rq when the windows were asked for, 0 otherwise; first .. last (inclusive) are
+ * the array's seismometers; -1 (r3dh_last_error) if --lapse-array's LAST is not a seismometer of the model.
+ * r3dh_lapse_plan: for the S = last - first + 1 receivers of the array, distances [S] -- range_km.m's: the x, y distance
+ * between the receiver's Location and EventLoc as seis_NNN.octv holds them (the output coordinate system's) --, bins
+ * [S][2][2] (window, then begin / end: r3d.h's bin rule with dt and n_bins the model's) and clipped [S][2].  0 ok.
+ * r3dh_write_lapse: lapse.octv-style GNU/Octave text at 17 digits to `path`, from the plan and a run's window sums
+ * (window_energy / window_se [S][2]: the sums of the weighted trace's BINS, not yet times dt; window_counts [S][2][2];
+ * batch_window_energy [B][S][2], B = n_batches >= 2).  Rows are the array's receivers in order, 0-based indices
+ * throughout:  LapseSeismometers [S] (the NNN of seis_NNN.octv), LapseBatches, LapseDistances [S], LapsePhaseEdge [2],
+ * LapseWindows [2][2], LapseAxes [3], LapseGeoSpread, LapseBins [S][4] (b1 e1 b2 e2), LapseTimes [S][4] (the same times
+ * dt), LapseClipped [S][2], LapseE / LapseE_se [S][2] (sum times dt: lapsetimecurve.m's EE1, EE2), LapseRE / LapseRE_se
+ * (times distance^G), LapseCounts [S][4] (P, S of window 1, then of window 2), LapseR1 [S] = log10(E1 / E2) where both are
+ * positive (NaN elsewhere) and LapseR1_se its jackknife (r3d.h r3d_window_log_ratio; NaN where a batch-deleted window is
+ * empty), LapseRanges [3], LapseRefIndex [3] (the first row nearest to each range, as Octave's min picks),
+ * LapseR2 = log10(RE1[iA] / RE1[iB]) and LapseR2_se.  Returns 0 ok.                                                   */
+typedef struct r3dh_lapse_opts {
+  uint32_t size;                 /* sizeof(r3dh_lapse_opts)                                   */
+  uint32_t first, last;          /* the array: seismometers first .. last                        */
+  uint32_t pad_;
+  double   phase_edge[2];        /* v, t0                                                         */
+  double   windows[4];           /* b1, e1, b2, e2: seconds behind the edge                      */
+  double   axes[3];              /* weights of the trace's X, Y, Z                               */
+  double   geospread;
+  double   ranges[3];            /* the reference's 8, 50, 150 km                                */
+} r3dh_lapse_opts;
+typedef struct r3dh_lapse_result {
+  uint32_t size;                 /* sizeof(r3dh_lapse_result)                                    */
+  uint32_t n_batches;
+  const double*   distances;             /* [S]          r3dh_lapse_plan's                      */
+  const uint32_t* bins;                  /* [S][2][2]                                            */
+  const int32_t*  clipped;               /* [S][2]                                               */
+  const double*   window_energy;         /* [S][2]                                               */
+  const double*   window_se;             /* [S][2]                                               */
+  const uint64_t* window_counts;         /* [S][2][2]                                            */
+  const double*   batch_window_energy;   /* [B][S][2]                                            */
+} r3dh_lapse_result;
+int r3dh_lapse_request(const r3dh_model* m, r3dh_lapse_opts* rq);
+int r3dh_lapse_plan(const r3dh_model* m, const r3dh_lapse_opts* rq, double* distances, uint32_t* bins, int32_t* clipped);
+int r3dh_write_lapse(const r3dh_model* m, const r3dh_lapse_opts* rq, const r3dh_lapse_result* res, const char* path);
+
 /* For a model built with --device-tables (scattering tables left to the engine):
  * record what r3d_engine_scatterer_stats() returned, so that the scatterer dump
  * and r3dh_scatterer_info show the engine's numbers.  Returns 0 ok.            */

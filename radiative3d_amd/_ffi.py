@@ -111,6 +111,26 @@ class VolumeMaps(C.Structure):
                 ("d_total", C.c_void_p)]
 
 
+class WindowSpec(C.Structure):
+    """include/r3d.h r3d_window_spec"""
+    _fields_ = [("size", C.c_uint32), ("n_seismometers", C.c_uint32), ("n_bins", C.c_uint32), ("n_windows", C.c_uint32),
+                ("d_bins", C.c_void_p), ("weight", C.c_double * R3D_N_ENERGY)]
+
+
+class LapseOpts(C.Structure):
+    """include/r3d_host.h r3dh_lapse_opts"""
+    _fields_ = [("size", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("pad_", C.c_uint32),
+                ("phase_edge", C.c_double * 2), ("windows", C.c_double * 4), ("axes", C.c_double * 3),
+                ("geospread", C.c_double), ("ranges", C.c_double * 3)]
+
+
+class LapseResult(C.Structure):
+    """include/r3d_host.h r3dh_lapse_result"""
+    _fields_ = [("size", C.c_uint32), ("n_batches", C.c_uint32), ("distances", C.c_void_p), ("bins", C.c_void_p),
+                ("clipped", C.c_void_p), ("window_energy", C.c_void_p), ("window_se", C.c_void_p),
+                ("window_counts", C.c_void_p), ("batch_window_energy", C.c_void_p)]
+
+
 class MapsHeader(C.Structure):
     """include/r3d_host.h r3dh_maps_header"""
     _fields_ = [("dims", C.c_uint32 * 3), ("frames", C.c_uint32), ("min_count", C.c_uint32), ("n_range", C.c_uint32),
@@ -215,6 +235,12 @@ def host_lib():
         L.r3dh_scatter_maps.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.r3dh_write_maps_header.restype = C.c_int
         L.r3dh_write_maps_header.argtypes = [C.POINTER(MapsHeader), C.c_char_p]
+        L.r3dh_lapse_request.restype = C.c_int
+        L.r3dh_lapse_request.argtypes = [C.c_void_p, C.POINTER(LapseOpts)]
+        L.r3dh_lapse_plan.restype = C.c_int
+        L.r3dh_lapse_plan.argtypes = [C.c_void_p, C.POINTER(LapseOpts), _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+        L.r3dh_write_lapse.restype = C.c_int
+        L.r3dh_write_lapse.argtypes = [C.c_void_p, C.POINTER(LapseOpts), C.POINTER(LapseResult), C.c_char_p]
         L.r3dh_seismometer_axes.restype = C.c_int
         L.r3dh_seismometer_axes.argtypes = [C.c_void_p, C.c_int]
         _host = L
@@ -389,6 +415,17 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_node_run_batched.restype = C.c_int
         L.r3d_node_run_batched.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
                                            _dp, _dp]
+        L.r3d_window_sums.restype = C.c_int
+        L.r3d_window_sums.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(WindowSpec), C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        L.r3d_window_bins.restype = C.c_int
+        L.r3d_window_bins.argtypes = [C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        L.r3d_window_log_ratio.restype = C.c_int
+        L.r3d_window_log_ratio.argtypes = [C.c_uint32, _dp, _dp, C.c_uint64, _dp, _dp]
+        L.r3d_run_batched_windows.restype = C.c_int
+        L.r3d_run_batched_windows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
+                                              _dp, _dp, C.POINTER(WindowSpec), _dp, C.POINTER(C.c_uint64), _dp, _dp]
         L.r3d_last_error.restype = C.c_char_p
         L.r3d_version.restype = C.c_char_p
         _hip[key] = L

@@ -157,6 +157,47 @@ int r3dh_write_maps_header(const r3dh_maps_header* h, const char* path) {
   return 0;
 }
 
+int r3dh_lapse_request(const r3dh_model* m, r3dh_lapse_opts* rq) {
+  if (!m || !m->mission.bLapse) return 0;
+  if (!rq) return 1;
+  try {
+    LapseRequest(*m->model, m->mission, rq);
+    return 1;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return -1;
+}
+
+int r3dh_lapse_plan(const r3dh_model* m, const r3dh_lapse_opts* rq, double* distances, uint32_t* bins, int32_t* clipped) {
+  if (!m || !rq || !distances || !bins || !clipped) return g_error = "r3dh_lapse_plan: null argument", 1;
+  try {
+    // (through the global coordinate system, which still holds this model's mapping only if no other model was built
+    //  since -- as for r3dh_grid_dump)
+    LapsePlan(*m->model, *rq, distances, bins, clipped);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
+int r3dh_write_lapse(const r3dh_model* m, const r3dh_lapse_opts* rq, const r3dh_lapse_result* res, const char* path) {
+  if (!m || !rq || !res || !path) return g_error = "r3dh_write_lapse: null argument", 1;
+  if (!res->distances || !res->bins || !res->clipped || !res->window_energy || !res->window_se || !res->window_counts ||
+      !res->batch_window_energy)
+    return g_error = "r3dh_write_lapse: null array in the result", 1;
+  try {
+    std::ofstream f(path);
+    OutputLapse(*m->model, *rq, *res, f);
+    if (!f) throw Runtime(std::string("cannot write ") + path);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
 int r3dh_model_set_scatterer_stats(r3dh_model* m, int s, const double mfp[2], const double dipole[2]) {
   if (!m || !mfp || !dipole || s < 0 || s >= (int)m->model->Scatterers().size()) return 1;
   m->model->SetScattererStats(s, mfp, dipole);

@@ -2,6 +2,7 @@
 #include "cmdline.hpp"
 
 #include <cctype>
+#include <cmath>
 #include <cstdlib>
 #include <deque>
 #include <iostream>
@@ -18,7 +19,8 @@ enum OptID {
   OPT_SEISARRAY, OPT_SEIS_P2P, OPT_SEIS_P2PW, OPTM_HELP, OPTM_DUMPGRID, OPTM_PARAMOUTFN,
   OPTM_RTTEST, OPTM_EVENTTEST, OPTM_RUNSIM, OPTX_SEED, OPTX_GPUS, OPTX_DEVTABLES, OPTX_HOSTTABLES,
   OPTX_DEVICES, OPTX_SCATGRID, OPTX_SCATGRID_FILE, OPTX_ERRBATCHES,
-  OPTX_SCATVIEWS, OPTX_SCATVIEW_AZI, OPTX_NO_SCATGRID_FILE, OPTX_SCATMAPS, OPTX_JOBERRBATCHES
+  OPTX_SCATVIEWS, OPTX_SCATVIEW_AZI, OPTX_NO_SCATGRID_FILE, OPTX_SCATMAPS, OPTX_JOBERRBATCHES,
+  OPTX_LAPSE, OPTX_LAPSE_AXES, OPTX_LAPSE_GEOSPREAD, OPTX_LAPSE_RANGES, OPTX_LAPSE_ARRAY
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -52,7 +54,9 @@ const std::map<std::string, OptID>& option_table() {
       {"--scatter-grid", OPTX_SCATGRID}, {"--scatter-grid-file", OPTX_SCATGRID_FILE},
       {"--error-batches", OPTX_ERRBATCHES}, {"--job-error-batches", OPTX_JOBERRBATCHES},
       {"--scatter-views", OPTX_SCATVIEWS}, {"--scatter-view-azimuth", OPTX_SCATVIEW_AZI},
-      {"--no-scatter-grid-file", OPTX_NO_SCATGRID_FILE}, {"--scatter-maps", OPTX_SCATMAPS}};
+      {"--no-scatter-grid-file", OPTX_NO_SCATGRID_FILE}, {"--scatter-maps", OPTX_SCATMAPS},
+      {"--lapse-windows", OPTX_LAPSE}, {"--lapse-axes", OPTX_LAPSE_AXES}, {"--lapse-geospread", OPTX_LAPSE_GEOSPREAD},
+      {"--lapse-ranges", OPTX_LAPSE_RANGES}, {"--lapse-array", OPTX_LAPSE_ARRAY}};
   return t;
 }
 
@@ -321,6 +325,43 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
         mission.MapMinCount = (unsigned)c;
         break;
       }
+      case OPTX_LAPSE: {
+        if (o.has()) {
+          for (int k = 0; k < 2; k++) mission.LapseEdge[k] = o.real();
+          for (int k = 0; k < 4; k++) mission.LapseWindows[k] = o.real();
+        }
+        const double* w = mission.LapseWindows;
+        if (!(mission.LapseEdge[0] > 0) || !std::isfinite(mission.LapseEdge[0]) || !std::isfinite(mission.LapseEdge[1]) ||
+            !(w[1] >= w[0]) || !(w[3] >= w[2]) || !std::isfinite(w[0] + w[1] + w[2] + w[3]))
+          throw Runtime("--lapse-windows[=V,T0,B1,E1,B2,E2]: the phase velocity V must be positive, each window's end not "
+                        "before its start, and every number finite.");
+        mission.bLapse = true;
+        break;
+      }
+      case OPTX_LAPSE_AXES:
+        for (int k = 0; k < 3; k++) mission.LapseAxes[k] = o.real();
+        if (!std::isfinite(mission.LapseAxes[0] + mission.LapseAxes[1] + mission.LapseAxes[2]))
+          throw Runtime("--lapse-axes=X,Y,Z: the weights must be finite.");
+        mission.LapseCompanion = "--lapse-axes";
+        break;
+      case OPTX_LAPSE_GEOSPREAD:
+        mission.LapseGeoSpread = o.real();
+        if (!std::isfinite(mission.LapseGeoSpread)) throw Runtime("--lapse-geospread=G: G must be finite.");
+        mission.LapseCompanion = "--lapse-geospread";
+        break;
+      case OPTX_LAPSE_RANGES:
+        for (int k = 0; k < 3; k++) mission.LapseRanges[k] = o.real();
+        if (!std::isfinite(mission.LapseRanges[0] + mission.LapseRanges[1] + mission.LapseRanges[2]))
+          throw Runtime("--lapse-ranges=R0,RA,RB: the distances must be finite.");
+        mission.LapseCompanion = "--lapse-ranges";
+        break;
+      case OPTX_LAPSE_ARRAY:
+        mission.LapseArray[0] = o.integer();
+        mission.LapseArray[1] = o.integer();
+        if (mission.LapseArray[0] < 0 || mission.LapseArray[1] < mission.LapseArray[0])
+          throw Runtime("--lapse-array=FIRST,LAST: seismometer indices with 0 <= FIRST <= LAST.");
+        mission.LapseCompanion = "--lapse-array";
+        break;
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }
@@ -340,6 +381,16 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
     if (N / shards < 2 || N / shards > 64)
       throw Runtime("--job-error-batches=N: every shard runs N / shards batches, which must be 2 .. 64 (got " + over + ").");
   }
+  // the lapse windows' errors come from one device's batches
+  if (mission.LapseCompanion && !mission.bLapse)
+    throw Runtime(std::string(mission.LapseCompanion) + " needs --lapse-windows: it only says how those windows are summed.");
+  if (mission.bLapse && mission.JobErrorBatches)
+    throw Runtime("--lapse-windows cannot be combined with --job-error-batches: the window sums are taken where ONE device's "
+                  "batch blocks lie (r3d_run_batched_windows); a job sharded over devices has no windows call.  Use "
+                  "--error-batches=B.");
+  if (mission.bLapse && !mission.ErrorBatches)
+    throw Runtime("--lapse-windows needs --error-batches=B: the windows' standard errors and the ratios' jackknife come from "
+                  "the B batches.");
   // the views and the maps are made from the grid: none of their options means anything without it
   if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile || mission.bScatterMaps))
     throw Runtime(std::string(mission.bScatterViews ? "--scatter-views" : mission.bViewAzimuth ? "--scatter-view-azimuth"

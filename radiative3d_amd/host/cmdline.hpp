@@ -6,7 +6,8 @@
 // aliases -F -N -T -A -E -L.  Integer values take K/M/B suffixes
 // (cmdline.cpp:343-390).  Engine-only additions: --seed, --gpus, --devices, --host-tables / --device-tables,
 // --scatter-grid / --scatter-grid-file (the scatter-event histogram of a video run, written as a file),
-// --error-batches / --job-error-batches (per-bin standard errors).
+// --error-batches / --job-error-batches (per-bin standard errors), --lapse-windows and its four companions (lapse-window
+// energies and coda ratios with batch errors).
 #ifndef R3DH_CMDLINE_HPP_
 #define R3DH_CMDLINE_HPP_
 
@@ -52,6 +53,17 @@ struct MissionParams {
   // frame with MINCOUNT events, the peak's frame and count, the total -- as scattermaps.octv and scattermaps_*.{u32,u64}
   bool bScatterMaps = false;
   unsigned MapMinCount = 1;
+  // --lapse-windows[=V,T0,B1,E1,B2,E2]: the two lapse-window energies of vis/seisplot/lapsetimecurve.m behind the phase edge
+  // (V km/s, T0 s) and the coda ratios R1, R2 made of them, with standard errors from the batches of --error-batches
+  // (include/r3d.h r3d_run_batched_windows), as lapse.octv; --lapse-axes=X,Y,Z the weights of the three trace axes,
+  // --lapse-geospread=G the exponent of distance in the range-corrected energies, --lapse-ranges=R0,RA,RB the distances (km)
+  // whose nearest receivers serve as the reference and as R1's / R2's stations, --lapse-array=FIRST,LAST the receivers
+  // (seismometer indices, inclusive) that form the array (default: all)
+  bool bLapse = false;
+  const char* LapseCompanion = nullptr;   // one of the four that was given (they are refused without --lapse-windows)
+  double LapseEdge[2] = {3.6, 0.0}, LapseWindows[4] = {5.0, 20.0, 45.0, 115.0}, LapseAxes[3] = {0.0, 0.0, 1.0};
+  double LapseGeoSpread = 2.0, LapseRanges[3] = {8.0, 50.0, 150.0};
+  long LapseArray[2] = {0, -1};           // LAST < 0: through the last receiver
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

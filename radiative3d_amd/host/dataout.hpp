@@ -43,6 +43,14 @@ void OutputSeismometerErrorsOctave(const Model& model, const double* energy_se, 
 void OutputSeismometerErrors(const Model& model, const double* energy_se, const double* counts_se, unsigned n_batches,
                              const std::string& outdir);
 
+// The lapse-window energies and coda ratios of --lapse-windows (include/r3d_host.h has the request, the plan, the file's
+// items): LapseRequest fills *rq from the mission (throws if --lapse-array names a receiver the model does not have),
+// LapsePlan the array's distances, bins and clipped flags, OutputLapse writes the file's text.
+struct MissionParams;
+void LapseRequest(const Model& model, const MissionParams& mission, r3dh_lapse_opts* rq);
+void LapsePlan(const Model& model, const r3dh_lapse_opts& rq, double* distances, uint32_t* bins, int32_t* clipped);
+void OutputLapse(const Model& model, const r3dh_lapse_opts& rq, const r3dh_lapse_result& res, std::ostream& out);
+
 // --reports keywords (reference main.cpp:223-258) -> R3D_RPT_* mask.  `csv` is the keyword
 // list as given ("ALL_ON", "GEN,SCT,REF", "SCATTERS", ...); empty = none.  ApplyReportKeyword: `mask` after ONE
 // keyword of the list; both throw the one sentence that names the valid keywords for any other word.

@@ -6,8 +6,8 @@
 // is one call into the engine's C-ABI.  What a run with --scatter-grid writes afterwards (the grid, its views, its maps)
 // is the output stage of scatter_out.cpp; this file builds its job, has it checked before the run and calls it once.
 //
-// Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B` and
-// `--job-error-batches=N` (error bars of a job on any number of shards) are accepted (the reference seeds from the clock,
+// Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B`,
+// `--job-error-batches=N` (error bars of a job on any number of shards) and `--lapse-windows` (lapse.octv) are accepted (the reference seeds from the clock,
 // is single-process, has no event histogram and no error bars); the `--reports` stream is written
 // after the run, grouped by history, where the reference writes its lines as they happen (the engine appends binary
 // records in HBM: include/r3d.h r3d_event); tables are built in HBM unless `--host-tables` is given.
@@ -127,6 +127,12 @@ struct SimulationOutput {
   std::vector<r3d_event> events;
   uint64_t events_dropped = 0;
   std::vector<double> energy_se, counts_se;
+  // --lapse-windows: the array's plan and its window sums (include/r3d_host.h r3dh_lapse_result), [S] receivers
+  r3dh_lapse_opts lapse{};
+  std::vector<double> lapse_distances, lapse_energy, lapse_se, lapse_batch_energy;
+  std::vector<uint32_t> lapse_bins;
+  std::vector<int32_t> lapse_clipped;
+  std::vector<uint64_t> lapse_counts;
 };
 
 // The report stream of the run, shard after shard (ids ascend across shards): at most caps[g] records of engine g,
@@ -172,8 +178,35 @@ SimulationOutput run_simulation(const Model& model, const MissionParams& mission
     // --error-batches: the one shard's ids as B batches, every bin's standard error from their spread
     // (include/r3d.h r3d_run_batched); the totals are those of the plain run up to summation order
     out.energy_se.assign(ne, 0.0), out.counts_se.assign(nc, 0.0);
-    if (r3d_run_batched(engines[0], n, 0, seed, mission.ErrorBatches, &out.total, out.energy_se.data(), out.counts_se.data()))
+    if (mission.bLapse) {
+      // --lapse-windows: the same run with its batch blocks kept on the device and the array's two windows per receiver
+      // summed there (include/r3d.h r3d_run_batched_windows); receivers outside the array get empty windows
+      LapseRequest(model, mission, &out.lapse);
+      const size_t S = (size_t)out.lapse.last - out.lapse.first + 1, all = (size_t)d.n_seismometers, B = mission.ErrorBatches;
+      out.lapse_distances.assign(S, 0.0), out.lapse_bins.assign(4 * S, 0), out.lapse_clipped.assign(2 * S, 0);
+      LapsePlan(model, out.lapse, out.lapse_distances.data(), out.lapse_bins.data(), out.lapse_clipped.data());
+      std::vector<uint32_t> bins(4 * all, 0);
+      std::copy(out.lapse_bins.begin(), out.lapse_bins.end(), bins.begin() + 4 * out.lapse.first);
+      r3d_window_spec spec{};
+      spec.size = sizeof spec, spec.n_seismometers = (uint32_t)all, spec.n_bins = d.params.n_bins, spec.n_windows = 2;
+      spec.d_bins = bins.data();   // (for this call: on the host)
+      for (int k = 0; k < 3; k++) spec.weight[k] = out.lapse.axes[k];
+      std::vector<double> we(2 * all, 0.0), wse(2 * all, 0.0), bwe(B * 2 * all, 0.0);
+      std::vector<uint64_t> wc(4 * all, 0);
+      if (r3d_run_batched_windows(engines[0], n, 0, seed, mission.ErrorBatches, &out.total, out.energy_se.data(),
+                                  out.counts_se.data(), &spec, we.data(), wc.data(), wse.data(), bwe.data()))
+        throw Runtime(r3d_last_error());
+      const size_t lo = out.lapse.first;
+      out.lapse_energy.assign(we.begin() + 2 * lo, we.begin() + 2 * (lo + S));
+      out.lapse_se.assign(wse.begin() + 2 * lo, wse.begin() + 2 * (lo + S));
+      out.lapse_counts.assign(wc.begin() + 4 * lo, wc.begin() + 4 * (lo + S));
+      for (size_t j = 0; j < B; j++)
+        out.lapse_batch_energy.insert(out.lapse_batch_energy.end(), bwe.begin() + 2 * (j * all + lo),
+                                      bwe.begin() + 2 * (j * all + lo + S));
+    } else if (r3d_run_batched(engines[0], n, 0, seed, mission.ErrorBatches, &out.total, out.energy_se.data(),
+                               out.counts_se.data())) {
       throw Runtime(r3d_last_error());
+    }
     std::cout << "|  Batches: " << mission.ErrorBatches << " (standard errors from batch means)\n";
   } else if (mission.JobErrorBatches) {
     // --job-error-batches: the whole job as N batches dealt to the shards, every shard's moments taken on its device
@@ -234,7 +267,11 @@ int main(int argc, char* argv[]) {
               << "--error-batches=B (2..64, one device): the histories run as B id-partitioned batches and every bin's\n"
               << "standard error is written to seis_NNN_err.octv beside seis_NNN.octv\n"
               << "--job-error-batches=N: the same for a job on any number of shards (--gpus / --devices) -- the whole job is cut\n"
-              << "into N batches, N / shards (2..64) on every shard, and the shards' moments are merged on the GPU\n\n";
+              << "into N batches, N / shards (2..64) on every shard, and the shards' moments are merged on the GPU\n"
+              << "--lapse-windows[=V,T0,B1,E1,B2,E2] (with --error-batches; default 3.6,0,5,20,45,115): the energy in two lapse windows\n"
+              << "behind the phase edge (V km/s, T0 s) per receiver and the coda ratios R1, R2 of them, summed on the GPU over every\n"
+              << "batch, with standard errors, as lapse.octv; --lapse-axes=X,Y,Z (default 0,0,1)  --lapse-geospread=G (default 2)\n"
+              << "--lapse-ranges=R0,RA,RB (default 8,50,150 km)  --lapse-array=FIRST,LAST (seismometer indices; default all)\n\n";
     return 0;
   }
   // A simulation run makes its tables where it uses them (seconds of host work and GBs of upload
@@ -321,6 +358,17 @@ int main(int argc, char* argv[]) {
         if (mission.ErrorBatches || mission.JobErrorBatches)
           OutputSeismometerErrors(model, run.energy_se.data(), run.counts_se.data(),
                                   mission.ErrorBatches ? mission.ErrorBatches : mission.JobErrorBatches, mission.OutputDir);
+        if (mission.bLapse) {
+          r3dh_lapse_result res{};
+          res.size = sizeof res, res.n_batches = mission.ErrorBatches;
+          res.distances = run.lapse_distances.data(), res.bins = run.lapse_bins.data(), res.clipped = run.lapse_clipped.data();
+          res.window_energy = run.lapse_energy.data(), res.window_se = run.lapse_se.data();
+          res.window_counts = run.lapse_counts.data(), res.batch_window_energy = run.lapse_batch_energy.data();
+          const std::string fn = (mission.OutputDir.empty() ? std::string() : mission.OutputDir + "/") + "lapse.octv";
+          std::ofstream f(fn.c_str());
+          OutputLapse(model, run.lapse, res, f);
+          if (!f) throw Runtime("cannot write " + fn);
+        }
       }
     }
   } catch (std::exception& e) {

@@ -244,6 +244,72 @@ class Model:
             return None
         return int(min_count.value)
 
+    @property
+    def lapse_request(self):
+        """What --lapse-windows[=V,T0,B1,E1,B2,E2] and its companions (--lapse-axes, --lapse-geospread, --lapse-ranges,
+        --lapse-array) asked for: None, or dict(first, last, phase_edge, windows, axes, geospread, ranges) -- the array's
+        seismometers first .. last inclusive (include/r3d_host.h r3dh_lapse_opts)."""
+        rq = _ffi.LapseOpts()
+        rc = self._lib.r3dh_lapse_request(self._h, C.byref(rq))
+        if rc < 0:
+            raise RuntimeError("lapse_request failed: " + self._lib.r3dh_last_error().decode())
+        if rc == 0:
+            return None
+        return dict(first=int(rq.first), last=int(rq.last), phase_edge=tuple(rq.phase_edge), windows=tuple(rq.windows),
+                    axes=tuple(rq.axes), geospread=rq.geospread, ranges=tuple(rq.ranges))
+
+    @staticmethod
+    def _lapse_opts(request):
+        rq = _ffi.LapseOpts(size=C.sizeof(_ffi.LapseOpts), first=int(request["first"]), last=int(request["last"]),
+                            geospread=float(request["geospread"]))
+        for name in ("phase_edge", "windows", "axes", "ranges"):
+            field = getattr(rq, name)
+            if len(request[name]) != len(field):
+                raise ValueError(f"lapse request: {name} needs {len(field)} numbers")
+            for k, v in enumerate(request[name]):
+                field[k] = float(v)
+        return rq
+
+    def lapse_plan(self, request=None):
+        """(distances [S], bins [S, 2, 2], clipped [S, 2]) of the lapse array (`request`: a dict as lapse_request gives;
+        None: the model's own): every receiver's epicentral distance as vis/seisplot/range_km.m takes it from
+        seis_NNN.octv, and the begin, end bins of its two lapse windows (include/r3d.h r3d_window_bins)."""
+        request = request if request is not None else self.lapse_request
+        if request is None:
+            raise RuntimeError("the model's arguments hold no --lapse-windows")
+        rq = self._lapse_opts(request)
+        S = int(rq.last) - int(rq.first) + 1
+        if S < 1:
+            raise ValueError("lapse request: first > last")
+        dist, bins, clipped = np.zeros(S), np.zeros((S, 2, 2), dtype=np.uint32), np.zeros((S, 2), dtype=np.int32)
+        if self._lib.r3dh_lapse_plan(self._h, C.byref(rq), dist.ctypes.data_as(_ffi._dp),
+                                     bins.ctypes.data_as(C.POINTER(C.c_uint32)), clipped.ctypes.data_as(C.POINTER(C.c_int32))):
+            raise RuntimeError("lapse_plan failed: " + self._lib.r3dh_last_error().decode())
+        return dist, bins, clipped.astype(bool)
+
+    def write_lapse(self, path, plan, window_energy, window_se, window_counts, batch_window_energy, request=None):
+        """Write lapse.octv (include/r3d_host.h r3dh_write_lapse) to `path`: plan = lapse_plan(request); window_energy /
+        window_se [S, 2], window_counts [S, 2, 2] and batch_window_energy [B, S, 2] the ARRAY's rows of what
+        Engine.run_batched_windows returned for the plan's bins."""
+        request = request if request is not None else self.lapse_request
+        if request is None:
+            raise RuntimeError("the model's arguments hold no --lapse-windows")
+        rq = self._lapse_opts(request)
+        S = int(rq.last) - int(rq.first) + 1
+        dist = np.ascontiguousarray(plan[0], dtype=np.float64).reshape(S)
+        bins = np.ascontiguousarray(plan[1], dtype=np.uint32).reshape(S, 2, 2)
+        clipped = np.ascontiguousarray(plan[2], dtype=np.int32).reshape(S, 2)
+        we = np.ascontiguousarray(window_energy, dtype=np.float64).reshape(S, 2)
+        wse = np.ascontiguousarray(window_se, dtype=np.float64).reshape(S, 2)
+        wc = np.ascontiguousarray(window_counts, dtype=np.uint64).reshape(S, 2, 2)
+        bwe = np.ascontiguousarray(batch_window_energy, dtype=np.float64)
+        B = bwe.shape[0]
+        bwe = bwe.reshape(B, S, 2)
+        res = _ffi.LapseResult(C.sizeof(_ffi.LapseResult), B, dist.ctypes.data, bins.ctypes.data, clipped.ctypes.data,
+                               we.ctypes.data, wse.ctypes.data, wc.ctypes.data, bwe.ctypes.data)
+        if self._lib.r3dh_write_lapse(self._h, C.byref(rq), C.byref(res), str(path).encode()):
+            raise RuntimeError("write_lapse failed: " + self._lib.r3dh_last_error().decode())
+
     def new_result(self):
         return Result(self.n_seismometers, self.n_bins)
 
@@ -287,6 +353,91 @@ def batch_moments(batch_energy, batch_counts, batch_scalars=None, energy=None, c
     if rc:
         raise RuntimeError("r3d_batch_moments failed: " + lib.r3d_last_error().decode())
     return energy, counts, scalars, energy_se, counts_se
+
+
+def window_spec(n_seismometers, n_bins, n_windows, bins_ptr, weights):
+    """An r3d_window_spec (include/r3d.h): bins_ptr the address of the uint32 [n_seis][n_windows][2] begin, end pairs --
+    on the device for window_sums, on the host for Engine.run_batched_windows."""
+    w = [float(v) for v in weights]
+    if len(w) != _ffi.R3D_N_ENERGY:
+        raise ValueError("five component weights (X, Y, Z, P, S) are needed")
+    return _ffi.WindowSpec(C.sizeof(_ffi.WindowSpec), int(n_seismometers), int(n_bins), int(n_windows), bins_ptr,
+                           (C.c_double * _ffi.R3D_N_ENERGY)(*w))
+
+
+def window_bins(dt, n_bins, r, v, t0, o, e):
+    """r3d_window_bins: (begin, end, clipped) -- the 0-based half-open bins of the window that runs from o to e seconds
+    behind the phase edge (v, t0) at epicentral distance r, bins of dt seconds (vis/seisplot/lapsetimecurve.m's rule;
+    include/r3d.h).  clipped: the rule's bins did not fit [0, n_bins) and were cut.  Needs no GPU."""
+    lib = _ffi.hip_lib()
+    out, clipped = (C.c_uint32 * 2)(), C.c_int(0)
+    if lib.r3d_window_bins(float(dt), int(n_bins), float(r), float(v), float(t0), float(o), float(e), out, C.byref(clipped)):
+        raise RuntimeError("r3d_window_bins failed: " + lib.r3d_last_error().decode())
+    return int(out[0]), int(out[1]), bool(clipped.value)
+
+
+def window_log_ratio(a, b):
+    """r3d_window_log_ratio: (theta, se) -- log10(sum a / sum b) of N batch values each and its jackknife standard
+    error; both NaN where a full or a leave-one-out sum is not positive (include/r3d.h).  Needs no GPU."""
+    lib = _ffi.hip_lib()
+    a, b = np.ascontiguousarray(a, dtype=np.float64).reshape(-1), np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+    if a.size != b.size:
+        raise ValueError("a and b must hold one value per batch each")
+    theta, se = C.c_double(), C.c_double()
+    if lib.r3d_window_log_ratio(a.size, a.ctypes.data_as(_ffi._dp), b.ctypes.data_as(_ffi._dp), 1, C.byref(theta),
+                                C.byref(se)):
+        raise RuntimeError("r3d_window_log_ratio failed: " + lib.r3d_last_error().decode())
+    return theta.value, se.value
+
+
+def window_sums(batch_energy, bins, weights, batch_counts=None, window_energy=None, window_counts=None, count_bad=False,
+                stream=None):
+    """r3d_window_sums on torch tensors of one device: batch_energy [B, S, n_bins, 5] float64 (and batch_counts
+    [B, S, n_bins, 2] of a 64-bit integer type, optional) are B batch blocks, bins [S, W, 2] int32 the begin, end pairs
+    of W windows per seismometer, weights the five component weights.  Returns (window_energy [B, S, W], window_counts
+    [B, S, W, 2] or None, bad): every block's weighted sum over every window, WRITTEN (into the tensors given, or new
+    ones); bad is a one-element tensor with the number of pairs that are not begin <= end <= n_bins (count_bad), else
+    None.  The result is one more batch-major block: batch_moments turns it into totals and standard errors.
+    Asynchronous on `stream` (a raw hipStream_t; None: torch's current one)."""
+    import torch
+    lib = _ffi.hip_lib()
+    if batch_energy.dim() != 4 or batch_energy.shape[3] != _ffi.R3D_N_ENERGY or batch_energy.dtype != torch.float64:
+        raise ValueError("batch_energy must be float64 [B, S, n_bins, 5]")
+    B, S, n_bins = (int(v) for v in batch_energy.shape[:3])
+    dev = batch_energy.device
+    if bins.dim() != 3 or bins.shape[0] != S or bins.shape[2] != 2 or bins.element_size() != 4 or bins.dtype.is_floating_point:
+        raise ValueError("bins must be a 32-bit integer tensor [S, W, 2]")
+    W = int(bins.shape[1])
+    tensors = [batch_energy, bins]
+    if batch_counts is not None:
+        if tuple(batch_counts.shape) != (B, S, n_bins, _ffi.R3D_N_COUNT) or batch_counts.element_size() != 8 \
+                or batch_counts.dtype.is_floating_point:
+            raise ValueError("batch_counts must be a 64-bit integer tensor [B, S, n_bins, 2]")
+        tensors.append(batch_counts)
+        if window_counts is None:
+            window_counts = torch.empty((B, S, W, _ffi.R3D_N_COUNT), dtype=batch_counts.dtype, device=dev)
+        tensors.append(window_counts)
+    if window_energy is None:
+        window_energy = torch.empty((B, S, W), dtype=torch.float64, device=dev)
+    tensors.append(window_energy)
+    for t in tensors:
+        if not t.is_cuda or not t.is_contiguous() or t.device != dev:
+            raise ValueError("blocks, bins and outputs must be contiguous tensors on one GPU")
+    if window_energy.numel() != B * S * W or window_energy.dtype != torch.float64:
+        raise ValueError("window_energy must be float64 [B, S, W]")
+    if window_counts is not None and (window_counts.numel() != 2 * B * S * W or window_counts.element_size() != 8):
+        raise ValueError("window_counts must be a 64-bit integer tensor [B, S, W, 2]")
+    bad = torch.zeros(1, dtype=torch.int64, device=dev) if count_bad else None
+    spec = window_spec(S, n_bins, W, bins.data_ptr(), weights)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.r3d_window_sums(dev.index or 0, B, batch_energy.data_ptr(),
+                             batch_counts.data_ptr() if batch_counts is not None else None, C.byref(spec),
+                             window_energy.data_ptr(), window_counts.data_ptr() if window_counts is not None else None,
+                             bad.data_ptr() if bad is not None else None, stream)
+    if rc:
+        raise RuntimeError("r3d_window_sums failed: " + lib.r3d_last_error().decode())
+    return window_energy, window_counts, bad
 
 
 def _check_blocks(blocks, lead, what):
@@ -694,6 +845,32 @@ class Engine:
         res.counts[:] = counts.cpu().numpy().view(np.uint64)
         res.set_scalars(scalars.cpu().numpy().view(np.uint64))
         return res, ese.cpu().numpy(), cse.cpu().numpy(), be.cpu().numpy(), bc.cpu().numpy().view(np.uint64)
+
+    def run_batched_windows(self, n, n_batches, bins, weights, first_id=0, seed=0x5EED, keep_batch_windows=False):
+        """run_batched that also sums lapse windows where the batch blocks lie (include/r3d.h r3d_run_batched_windows):
+        bins [S, W, 2] begin, end pairs (host; anything numpy makes uint32 of), weights the five component weights.
+        Returns (Result, energy_se, counts_se, window_energy [S, W], window_counts [S, W, 2], window_se [S, W]) and,
+        with keep_batch_windows, the batches' own window sums [B, S, W] behind them (window_log_ratio's input)."""
+        m = self.model
+        res = m.new_result()
+        shape = (m.n_seismometers, m.n_bins)
+        b = np.ascontiguousarray(bins, dtype=np.uint32)
+        if b.ndim != 3 or b.shape[0] != m.n_seismometers or b.shape[2] != 2:
+            raise ValueError("bins must be [n_seismometers, W, 2]")
+        W = b.shape[1]
+        spec = window_spec(m.n_seismometers, m.n_bins, W, b.ctypes.data, weights)
+        ese, cse = np.zeros(shape + (_ffi.R3D_N_ENERGY,)), np.zeros(shape + (_ffi.R3D_N_COUNT,))
+        we, wse = np.zeros((m.n_seismometers, W)), np.zeros((m.n_seismometers, W))
+        wc = np.zeros((m.n_seismometers, W, _ffi.R3D_N_COUNT), dtype=np.uint64)
+        bwe = np.zeros((max(int(n_batches), 0), m.n_seismometers, W)) if keep_batch_windows else None
+        c = res._as_c()
+        if self._lib.r3d_run_batched_windows(self._e, n, first_id, seed, n_batches, C.byref(c), ese.ctypes.data_as(_ffi._dp),
+                                             cse.ctypes.data_as(_ffi._dp), C.byref(spec), we.ctypes.data_as(_ffi._dp),
+                                             wc.ctypes.data_as(C.POINTER(C.c_uint64)), wse.ctypes.data_as(_ffi._dp),
+                                             bwe.ctypes.data_as(_ffi._dp) if bwe is not None else None):
+            raise RuntimeError("r3d_run_batched_windows failed: " + self._lib.r3d_last_error().decode())
+        res._from_c(c)
+        return (res, ese, cse, we, wc, wse) + ((bwe,) if keep_batch_windows else ())
 
     def run_device(self, n, first_id, seed, d_energy, d_counts, d_scalars, stream=None, carry=None):
         """Asynchronous, device-resident accumulate (pointers are raw device

@@ -1,6 +1,7 @@
 // r3d_batch_stats.hip -- per-bin standard errors from id-partitioned batches (include/r3d.h r3d_batch_moments,
 // r3d_run_device_batched, r3d_run_batched; for a job sharded over several devices r3d_batch_partial, r3d_batch_merge,
-// r3d_node_run_batched).
+// r3d_node_run_batched), and lapse-window sums of such batch blocks (r3d_window_sums, r3d_run_batched_windows; host only:
+// r3d_window_bins, r3d_window_log_ratio).
 //
 // A run of ids [first_id, first_id + n) is cut into B contiguous batches; each is one self-contained
 // r3d_run_device launch into its own zeroed block.  Histories are keyed by id, so the blocks are independent
@@ -14,6 +15,7 @@
 // events it overlaps the batches with; nothing in csrc/ knows about it.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <mutex>
 #include <string>
@@ -21,6 +23,7 @@
 
 #include "../common/r3d_entry.h"
 #include "r3d_batch_moments.h"
+#include "r3d_window_sums.h"
 
 namespace r3d {
 namespace {
@@ -124,6 +127,117 @@ __global__ __launch_bounds__(kMomentsBlock) void batch_merge_u64_kernel(const ui
     }
     total_out[i] += total;
   }
+}
+
+// ---- lapse-window sums (r3d_window_sums.h has the arithmetic and why the geometry G does not show in the bits) ----
+constexpr int kWindowBlock = 256;
+
+struct WindowArgs {
+  const double* x;        // [B][n_seis][n_bins][5]
+  const uint64_t* c;      // [B][n_seis][n_bins][2], or null
+  const uint32_t* bins;   // [n_seis][n_windows][2]
+  double* y;              // [B][n_seis][n_windows]
+  uint64_t* yc;           // [B][n_seis][n_windows][2], or null
+  uint64_t n_sw;          // n_seis * n_windows
+  uint64_t n_total;       // B * n_sw
+  uint32_t n_seis, n_bins, n_windows;
+  double w[kWindowComponents];
+};
+
+// G work-items per window, 256 / G windows per workgroup, grid-stride over the B * n_seis * n_windows windows (the trip
+// count is the same for the G work-items of a window, so the shuffles below always find their partners).  Work-item g
+// reads the bins begin + g, begin + g + G, ...: the G of a window read G * 40 contiguous bytes per step -- a wave
+// walking one long window 2560 --, and neighbouring short windows of one trace (decimation) make one contiguous stretch
+// of their wave's reads.  A pair that is not begin <= end <= n_bins is served as the empty window: nothing is read.
+template <int G>
+__global__ __launch_bounds__(kWindowBlock) void window_sums_kernel(const WindowArgs a) {
+  const uint32_t g = threadIdx.x % G;
+  const uint64_t per_grid = (uint64_t)gridDim.x * (kWindowBlock / G);
+  for (uint64_t wi = (uint64_t)blockIdx.x * (kWindowBlock / G) + threadIdx.x / G; wi < a.n_total; wi += per_grid) {
+    const uint64_t batch = wi / a.n_sw, sw = wi - batch * a.n_sw;
+    const uint64_t row = (batch * a.n_seis + sw / a.n_windows) * a.n_bins;
+    uint32_t begin = a.bins[2 * sw], end = a.bins[2 * sw + 1];
+    if (begin > end || end > a.n_bins) begin = end = 0;
+    double p[kWindowStrands / G];
+    window_strands<G>(a.x + row * kWindowComponents, begin, end, a.w, g, p);
+    window_fold<G>(p);
+    double v = p[0];
+#pragma unroll
+    for (int h = G / 2; h >= 1; h /= 2) v = v + __shfl_down(v, h, G);   // (a plain add: nothing here to contract)
+    if (g == 0) a.y[wi] = v;
+    if (a.yc) {
+      uint64_t n[2];
+      window_counts_part<G>(a.c + row * 2, begin, end, g, n);
+#pragma unroll
+      for (int h = G / 2; h >= 1; h /= 2) {
+        n[0] += __shfl_down((unsigned long long)n[0], h, G);
+        n[1] += __shfl_down((unsigned long long)n[1], h, G);
+      }
+      if (g == 0) a.yc[2 * wi] = n[0], a.yc[2 * wi + 1] = n[1];
+    }
+  }
+}
+
+// The pairs of the spec that are not begin <= end <= n_bins, counted by ONE workgroup and written by one work-item.
+__global__ __launch_bounds__(kWindowBlock) void window_bad_kernel(const uint32_t* __restrict__ bins, uint64_t n_sw,
+                                                                 uint32_t n_bins, uint64_t* __restrict__ bad) {
+  __shared__ unsigned long long part[kWindowBlock / 64];
+  unsigned long long n = 0;
+  for (uint64_t i = threadIdx.x; i < n_sw; i += kWindowBlock) n += bins[2 * i] > bins[2 * i + 1] || bins[2 * i + 1] > n_bins;
+#pragma unroll
+  for (int h = 32; h >= 1; h /= 2) n += __shfl_down(n, h, 64);
+  if (threadIdx.x % 64 == 0) part[threadIdx.x / 64] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long total = 0;
+    for (int k = 0; k < kWindowBlock / 64; k++) total += part[k];
+    *bad = total;
+  }
+}
+
+// The work-items per window, from the shape alone (the bins are on the device): n_bins / n_windows is the length of a
+// window when the windows tile a trace, as decimation's do; two long lapse windows get a wave each.
+int window_geometry(uint32_t n_bins, uint32_t n_windows) {
+  const uint32_t per = n_bins / n_windows;
+  return per <= 4 ? 4 : per <= 16 ? 16 : 64;
+}
+
+template <int G>
+void launch_window_sums(const WindowArgs& a, hipStream_t s) {
+  const uint64_t per_block = kWindowBlock / G, blocks = (a.n_total + per_block - 1) / per_block;
+  window_sums_kernel<G><<<dim3((unsigned)(blocks < (1u << 19) ? blocks : (1u << 19))), dim3(kWindowBlock), 0, s>>>(a);
+}
+
+int enqueue_window_sums(uint32_t n_batches, const double* d_batch_energy, const uint64_t* d_batch_counts,
+                        const r3d_window_spec* w, const uint32_t* d_bins, double* d_window_energy,
+                        uint64_t* d_window_counts, uint64_t* d_bad, hipStream_t s) {
+  WindowArgs a;
+  a.x = d_batch_energy, a.c = d_batch_counts, a.bins = d_bins, a.y = d_window_energy, a.yc = d_window_counts;
+  a.n_sw = (uint64_t)w->n_seismometers * w->n_windows, a.n_total = a.n_sw * n_batches;
+  a.n_seis = w->n_seismometers, a.n_bins = w->n_bins, a.n_windows = w->n_windows;
+  for (int k = 0; k < kWindowComponents; k++) a.w[k] = w->weight[k];
+  switch (window_geometry(w->n_bins, w->n_windows)) {
+    case 4: launch_window_sums<4>(a, s); break;
+    case 16: launch_window_sums<16>(a, s); break;
+    default: launch_window_sums<64>(a, s); break;
+  }
+  if (d_bad) window_bad_kernel<<<dim3(1), dim3(kWindowBlock), 0, s>>>(d_bins, a.n_sw, w->n_bins, d_bad);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : refuse("r3d_window_sums", err);
+}
+
+// What r3d_window_sums and r3d_run_batched_windows refuse on the spec alone (0: nothing; else the message is set).
+int check_window_spec(const char* who, const r3d_window_spec* w) {
+  if (!w) return refuse(who, "null window spec");
+  if (w->size != sizeof(r3d_window_spec))
+    return refuse(who, "r3d_window_spec.size is " + std::to_string(w->size) + ", this library's is " +
+                           std::to_string(sizeof(r3d_window_spec)));
+  if (w->n_seismometers == 0 || w->n_bins == 0 || w->n_windows == 0)
+    return refuse(who, "n_seismometers, n_bins and n_windows must all be at least 1");
+  if (!w->d_bins) return refuse(who, "null window bins");
+  for (int k = 0; k < R3D_N_ENERGY; k++)
+    if (!std::isfinite(w->weight[k])) return refuse(who, "weight " + std::to_string(k) + " is not finite");
+  return 0;
 }
 
 unsigned moments_grid(uint64_t len) {
@@ -295,6 +409,84 @@ int engine_device(r3d_engine* e, const char* who) {
   return device;
 }
 
+// r3d_run_batched, and with a window spec (bins on the HOST, checked by the caller) r3d_run_batched_windows: the batches
+// then run into blocks of this call's own, which stay on the device for the window kernel and the moments of its sums.
+int run_batched_to_host(const char* who, r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                        r3d_result* out, double* energy_se, double* counts_se, const r3d_window_spec* w,
+                        double* window_energy, uint64_t* window_counts, double* window_se, double* batch_window_energy) {
+  if (!e) return g_error = "null engine", 1;
+  if (!out || !out->energy || !out->counts) return g_error = "null result", 1;
+  if (check_batches(who, n, n_batches)) return 1;
+  if (refuse_engine_state(e, who)) return 1;
+  const int device = engine_device(e, who);
+  if (device < 0) return 1;
+  OnDevice on(device);
+  if (on.status != hipSuccess) return refuse(who, on.status);
+  const size_t ne = r3d_energy_len(e), nc = r3d_counts_len(e), ns = R3D_N_SCALARS;
+  const size_t B = n_batches, sw = w ? (size_t)w->n_seismometers * w->n_windows : 0;
+  // one block: totals (energy, counts, scalars), then the two se arrays; with windows, behind them what the host reads
+  // of those (sums [sw], counts [sw][2], se [sw], the batches' sums [B][sw]) and what it does not (the batches' window
+  // counts [B][sw][2], the bins, the batch blocks)
+  DeviceBuffer block;
+  const size_t words = 2 * ne + 2 * nc + ns, win_words = (4 + B) * sw;
+  const size_t rest_words = w ? 2 * B * sw + sw + B * (ne + nc) : 0;
+  if (hipError_t err = block.alloc((words + win_words + rest_words) * 8); err != hipSuccess) return refuse(who, err);
+  double* const d_e = block.as<double>();
+  uint64_t* const d_c = reinterpret_cast<uint64_t*>(d_e + ne);
+  uint64_t* const d_s = d_c + nc;
+  double* const d_ese = reinterpret_cast<double*>(d_s + ns);
+  double* const d_cse = d_ese + ne;
+  double* const d_we = d_cse + nc;
+  uint64_t* const d_wc = reinterpret_cast<uint64_t*>(d_we + sw);
+  double* const d_wse = reinterpret_cast<double*>(d_wc + 2 * sw);
+  double* const d_bwe = d_wse + sw;
+  uint64_t* const d_bwc = reinterpret_cast<uint64_t*>(d_bwe + B * sw);
+  uint32_t* const d_bins = reinterpret_cast<uint32_t*>(d_bwc + 2 * B * sw);
+  double* const d_be = w ? reinterpret_cast<double*>(d_bwc + 2 * B * sw + sw) : nullptr;
+  uint64_t* const d_bc = w ? reinterpret_cast<uint64_t*>(d_be + B * ne) : nullptr;
+  std::vector<uint64_t> host(words + win_words);
+  hipStream_t s = nullptr;
+  hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  if (err == hipSuccess) err = hipMemsetAsync(block.p, 0, (words + 3 * sw) * 8, s);
+  if (err == hipSuccess && w) err = hipMemcpyAsync(d_bins, w->d_bins, sw * 8, hipMemcpyHostToDevice, s);
+  int rc = err == hipSuccess ? 0 : refuse(who, err);
+  if (rc == 0) rc = r3d_run_device_batched(e, n, first_id, seed, n_batches, d_e, d_c, d_s, d_ese, d_cse, d_be, d_bc, s);
+  if (rc == 0 && w) rc = enqueue_window_sums(n_batches, d_be, d_bc, w, d_bins, d_bwe, d_bwc, nullptr, s);
+  if (rc == 0 && w)
+    rc = enqueue_moments(n_batches, d_bwe, sw, d_bwc, 2 * sw, nullptr, 0, d_we, d_wc, nullptr, d_wse, nullptr, s);
+  if (s) {   // (also after a refusal: what was enqueued reads the block)
+    err = hipStreamSynchronize(s);
+    if (err == hipSuccess && rc == 0) err = hipMemcpy(host.data(), block.p, host.size() * 8, hipMemcpyDeviceToHost);
+    if (err != hipSuccess && rc == 0) rc = refuse(who, err);
+    (void)hipStreamDestroy(s);
+  }
+  if (rc) return rc;
+  const double* const he = reinterpret_cast<const double*>(host.data());
+  const uint64_t* const hc = host.data() + ne;
+  const uint64_t* const hs = hc + nc;
+  const double* const hese = reinterpret_cast<const double*>(hs + ns);
+  for (size_t i = 0; i < ne; i++) out->energy[i] += he[i];
+  for (size_t i = 0; i < nc; i++) out->counts[i] += hc[i];
+  out->n_lost += hs[0], out->n_timeout += hs[1], out->n_invalid += hs[2];
+  for (int r = 0; r < R3D_INV_NUM; r++) out->invalid_reasons[r] += hs[3 + r];
+  for (int k = 0; k < R3D_EV_NUM; k++) out->events[k] += hs[3 + R3D_INV_NUM + k];
+  if (energy_se)
+    for (size_t i = 0; i < ne; i++) energy_se[i] = hese[i];
+  if (counts_se)
+    for (size_t i = 0; i < nc; i++) counts_se[i] = hese[ne + i];
+  if (w) {
+    const double* const hwe = hese + ne + nc;
+    const uint64_t* const hwc = reinterpret_cast<const uint64_t*>(hwe + sw);
+    const double* const hwse = reinterpret_cast<const double*>(hwc + 2 * sw);
+    for (size_t i = 0; i < sw; i++) window_energy[i] += hwe[i], window_se[i] = hwse[i];
+    if (window_counts)
+      for (size_t i = 0; i < 2 * sw; i++) window_counts[i] += hwc[i];
+    if (batch_window_energy)
+      for (size_t i = 0; i < B * sw; i++) batch_window_energy[i] = hwse[sw + i];
+  }
+  return 0;
+}
+
 }  // namespace
 }  // namespace r3d
 
@@ -358,52 +550,56 @@ int r3d_run_device_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_
 
 int r3d_run_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches, r3d_result* out,
                     double* energy_se, double* counts_se) {
-  const char* const who = "r3d_run_batched";
-  if (!e) return g_error = "null engine", 1;
-  if (!out || !out->energy || !out->counts) return g_error = "null result", 1;
-  if (check_batches(who, n, n_batches)) return 1;
-  if (refuse_engine_state(e, who)) return 1;
-  const int device = engine_device(e, who);
-  if (device < 0) return 1;
+  return run_batched_to_host("r3d_run_batched", e, n, first_id, seed, n_batches, out, energy_se, counts_se, nullptr, nullptr,
+                             nullptr, nullptr, nullptr);
+}
+
+int r3d_window_sums(int device, uint32_t n_batches, const double* d_batch_energy, const uint64_t* d_batch_counts,
+                    const r3d_window_spec* w, double* d_window_energy, uint64_t* d_window_counts, uint64_t* d_bad,
+                    void* stream) {
+  const char* const who = "r3d_window_sums";
+  if (n_batches == 0) return refuse(who, "no batch block (n_batches == 0); one plain result block is n_batches = 1");
+  if (!d_batch_energy || !d_window_energy) return refuse(who, "null argument");
+  if (check_window_spec(who, w)) return 1;
+  if (d_window_counts && !d_batch_counts) return refuse(who, "window counts are asked for without the batches' count blocks");
   OnDevice on(device);
-  if (on.status != hipSuccess) return refuse(who, on.status);
-  const size_t ne = r3d_energy_len(e), nc = r3d_counts_len(e), ns = R3D_N_SCALARS;
-  // one block: totals (energy, counts, scalars), then the two se arrays
-  DeviceBuffer block;
-  const size_t words = 2 * ne + 2 * nc + ns;
-  if (hipError_t err = block.alloc(words * 8); err != hipSuccess) return refuse(who, err);
-  double* const d_e = block.as<double>();
-  uint64_t* const d_c = reinterpret_cast<uint64_t*>(d_e + ne);
-  uint64_t* const d_s = d_c + nc;
-  double* const d_ese = reinterpret_cast<double*>(d_s + ns);
-  double* const d_cse = d_ese + ne;
-  std::vector<uint64_t> host(words);
-  hipStream_t s = nullptr;
-  hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-  if (err == hipSuccess) err = hipMemsetAsync(block.p, 0, words * 8, s);
-  int rc = err == hipSuccess ? 0 : refuse(who, err);
-  if (rc == 0) rc = r3d_run_device_batched(e, n, first_id, seed, n_batches, d_e, d_c, d_s, d_ese, d_cse, nullptr, nullptr, s);
-  if (s) {   // (also after a refusal: what was enqueued reads the block)
-    err = hipStreamSynchronize(s);
-    if (err == hipSuccess && rc == 0) err = hipMemcpy(host.data(), block.p, words * 8, hipMemcpyDeviceToHost);
-    if (err != hipSuccess && rc == 0) rc = refuse(who, err);
-    (void)hipStreamDestroy(s);
-  }
-  if (rc) return rc;
-  const double* const he = reinterpret_cast<const double*>(host.data());
-  const uint64_t* const hc = host.data() + ne;
-  const uint64_t* const hs = hc + nc;
-  const double* const hese = reinterpret_cast<const double*>(hs + ns);
-  for (size_t i = 0; i < ne; i++) out->energy[i] += he[i];
-  for (size_t i = 0; i < nc; i++) out->counts[i] += hc[i];
-  out->n_lost += hs[0], out->n_timeout += hs[1], out->n_invalid += hs[2];
-  for (int r = 0; r < R3D_INV_NUM; r++) out->invalid_reasons[r] += hs[3 + r];
-  for (int k = 0; k < R3D_EV_NUM; k++) out->events[k] += hs[3 + R3D_INV_NUM + k];
-  if (energy_se)
-    for (size_t i = 0; i < ne; i++) energy_se[i] = hese[i];
-  if (counts_se)
-    for (size_t i = 0; i < nc; i++) counts_se[i] = hese[ne + i];
+  if (on.status != hipSuccess) return refuse(who, "no HIP device (or a bad device index)");
+  return enqueue_window_sums(n_batches, d_batch_energy, d_window_counts ? d_batch_counts : nullptr, w, w->d_bins,
+                             d_window_energy, d_window_counts, d_bad, reinterpret_cast<hipStream_t>(stream));
+}
+
+int r3d_window_bins(double dt, uint32_t n_bins, double r, double v, double t0, double o, double e, uint32_t out[2],
+                    int* clipped) {
+  if (!out) return refuse("r3d_window_bins", "null argument");
+  if (window_bins(dt, n_bins, r, v, t0, o, e, out, clipped))
+    return refuse("r3d_window_bins", "dt and v must be positive, the window's end not before its start, n_bins at least 1 "
+                                     "and every number finite");
   return 0;
+}
+
+int r3d_window_log_ratio(uint32_t n, const double* a, const double* b, uint64_t stride, double* theta, double* se) {
+  if (!a || !b || !theta || !se) return refuse("r3d_window_log_ratio", "null argument");
+  if (n == 0 || stride == 0) return refuse("r3d_window_log_ratio", "at least one batch value, values at least 1 apart");
+  window_log_ratio(n, a, b, stride, theta, se);
+  return 0;
+}
+
+int r3d_run_batched_windows(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches, r3d_result* out,
+                            double* energy_se, double* counts_se, const r3d_window_spec* w, double* window_energy,
+                            uint64_t* window_counts, double* window_se, double* batch_window_energy) {
+  const char* const who = "r3d_run_batched_windows";
+  if (!e) return g_error = "null engine", 1;
+  if (check_window_spec(who, w)) return 1;
+  if (!window_energy || !window_se) return refuse(who, "null window_energy or window_se");
+  if ((uint64_t)w->n_seismometers * w->n_bins * R3D_N_ENERGY != r3d_energy_len(e))
+    return refuse(who, "the window spec's n_seismometers x n_bins is not the model's");
+  const uint64_t n_sw = (uint64_t)w->n_seismometers * w->n_windows;
+  for (uint64_t i = 0; i < n_sw; i++)
+    if (w->d_bins[2 * i] > w->d_bins[2 * i + 1] || w->d_bins[2 * i + 1] > w->n_bins)
+      return refuse(who, "window " + std::to_string(i % w->n_windows) + " of seismometer " +
+                             std::to_string(i / w->n_windows) + " is not begin <= end <= n_bins");
+  return run_batched_to_host(who, e, n, first_id, seed, n_batches, out, energy_se, counts_se, w, window_energy, window_counts,
+                             window_se, batch_window_energy);
 }
 
 int r3d_batch_partial(int device, uint32_t n_batches, const double* d_batch_energy, uint64_t n_energy,
