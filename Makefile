@@ -44,9 +44,11 @@ ENGINE_HDR := $(wildcard $(CSRC)/*.h) include/r3d.h
 #   stats  per-bin standard errors from batches (r3d_batch_moments, r3d_run_device_batched), lapse-window sums (r3d_window_sums)
 #   views  the two video views of the scatter-event grid (r3d_volume_project, r3d_volume_range_bins)
 #   maps   the grid reduced along its frame axis: arrival-time, peak and total maps (r3d_volume_time_maps)
-ADDONS := stats views maps
+#   arrays the travel-time image of a receiver array with jackknife errors (r3d_array_image, r3d_run_batched_array_image)
+ADDONS := stats views maps arrays
 addon_src = $(wildcard radiative3d_amd/$(1)/*.hip)
-addon_hdr = $(wildcard radiative3d_amd/$(1)/*.h) $(COMMON)/r3d_entry.h include/r3d.h
+# (arrays/ takes the bin energy and the strand constants from stats/r3d_window_sums.h)
+addon_hdr = $(wildcard radiative3d_amd/$(1)/*.h) $(COMMON)/r3d_entry.h include/r3d.h $(if $(filter arrays,$(1)),radiative3d_amd/stats/r3d_window_sums.h)
 OBJDIR   := build/obj
 
 # (the default goal is the first target of the file: it has to come before the generated object rules)

@@ -784,6 +784,105 @@ int r3d_run_batched_windows(r3d_engine* e, uint64_t n, uint64_t first_id, uint64
                             double* window_energy, uint64_t* window_counts, double* window_se,
                             double* batch_window_energy);
 
+/* ---- the travel-time image of a receiver array with jackknife errors -----------------
+ * What vis/seisplot/array.m -> arraymatrix.m -> arrayimage.m and normcurve_fitpowerlaw.m make of a run's seismometer files
+ * -- every receiver's weighted trace as one row of an image, gamma-scaled and normalised per row, and the power law
+ * Sum(E dt) = c X^q along the array -- with error bars.  A pixel is a nonlinear function of its whole row (divided by the
+ * row's sum and peak after the gamma root) and the fit one of all rows, so neither error follows from the per-bin errors:
+ * both are jackknives over the batch blocks where they lie.  radiative3d_amd/arrays/r3d_array_image.h has the arithmetic:
+ *     PER BIN, e_j the weighted energy of batch j (the window sum's e_b; weights finite and >= 0): the total t = the sum
+ *       in the order j and, for B >= 2, t_(j) = (L_j + R_j) B/(B-1) from the prefix sums L and the suffix sums R of the
+ *       e_j -- never t - e_j; g = t^(1/gamma), gamma = 2^gamma_log2 in {1, 2, 4}: sqrt applied gamma_log2 times, no pow.
+ *     ROW REDUCTIONS: rowsum by the window sum's 64 strands and tree, rowmax, rowarg = the first bin that holds rowmax.
+ *     LEGACY pixel (arrayimage.m:65-81): (1 - rho) g / rowsum(g) + rho g / rowmax(g); a row with rowmax == 0 is dead:
+ *       +0.0 in every pixel (Octave: NaN) and lit = 0.  CURVE pixel (:54-59): (t / (c_s / Tw))^(1/gamma) with a curve value
+ *       c_s per receiver and Tw = n_bins dt; a c_s that is not finite and > 0 makes the row dead and is counted as bad.
+ *     A PIXEL'S se, B >= 2: img_(j) = the pixel of the row t_(j) with that row's own sum and maximum (dead: +0.0),
+ *       se = sqrt((B-1)/B sum_j (img_(j) - mean)^2), two passes in the order j on img_(j) - img_(0).
+ *     peak = rowmax(t), peak_bin = rowarg(t) (NS.PeakEnergy, before gamma); row sums y_j = r3d_window_sums' full window.
+ *     THE FIT (host only; normcurve_fitpowerlaw.m:44-51) of Y_i against X_i = r_first + i (r_last - r_first) / (A - 1) over
+ *       the 1-based inclusive points ibegin .. iend: least squares of log Y on log X about their means; fit = (ln c, q),
+ *       NaN if a Y of the range is not positive.  Its jackknife: Y and Y_(j) from the batches' values by the L, R scans,
+ *       se = (se(ln c), se(q)) by the pixel's formula, NaN for B < 2 or where a leave-one-out Y is not positive.
+ *     The same bits on every run, machine and launch geometry.  With u = 2^-53, relative to the exact pixel:
+ *       |img - exact| <= eps exact, eps = d u / (1 - 2 d u), d = 2 (B + 7 + gamma_log2) + ceil(n_bins / 64) + 10 (LEGACY),
+ *       d = B + 9 + gamma_log2 (CURVE);  |se - se_exact| <= 2 B^1.5 eps max_j img_(j) + (B + 4) eps se_exact.
+ *
+ * r3d_array_image: device level, like r3d_window_sums -- B >= 1 batch-major blocks d_batch_energy [B][n_seis][n_bins][5]
+ * on `device`, only read; the array is the receivers first .. last, A of them.  WRITTEN, every entry by one work-item:
+ * d_image [A][n_bins]; d_image_se [A][n_bins] (may be NULL; needs B >= 2); d_row_sum [B][A], d_peak [A], d_peak_bin [A],
+ * d_lit [A] (u32; 1 where the row is alive) and d_bad (one uint64: the bad curve values, 0 in LEGACY), each of which may
+ * be NULL.  One workgroup per receiver, no atomics, fixed order, 64-bit offsets.  Asynchronous on `stream`.  The spec's
+ * range, fit_* and curve_c / curve_q are not read.  REFUSED (non-zero, r3d_last_error, nothing enqueued, no buffer
+ * touched; all checked before any HIP call): a null blocks, spec or image pointer, a size mismatch, n_batches == 0,
+ * B > 64, n_bins == 0, last < first, last >= n_seismometers, a weight that is negative or not finite, gamma_log2 > 2, a
+ * mode that is neither, LEGACY with rho outside [0, 1] or not finite, CURVE without d_curve or with a window_length that
+ * is not finite and > 0, d_image_se with B < 2.
+ * r3d_array_powerlaw / r3d_array_powerlaw_jackknife: the fit of y[i * stride], and the fit of the batches' totals with
+ * its jackknife from y[j * batch_stride + i] (`total` [A], may be NULL, receives the totals).  Refused: a null argument,
+ * A < 2, fewer than 2 points, a range outside 1 .. A, no batch.
+ *
+ * r3d_run_batched_array_image: r3d_run_batched (same arguments, refusals, out / energy_se / counts_se) that keeps its batch
+ * blocks on the device and makes there (1) the row sums and r3d_batch_moments of them: res->summed [A] ADDED into,
+ * summed_se [A] WRITTEN -- raw sums of bins, the caller multiplies by dt --; (2) the LEGACY image and its se, lit, peak,
+ * peak_bin; (3) if spec->fit_begin, fit_end are not 0, 0: the [B][A] row sums come down, are multiplied by dt =
+ * window_length / n_bins and fitted with their jackknife on the host over X between spec->range[0] and range[1] (the
+ * distances of the array's end receivers): res->fit = (c, q), fit_se = (se(ln c), se(q)); the curve c X^q goes up and the
+ * CURVE image and its se are made: res->curve [A], image_curve, image_curve_se.  (4) A curve given outright (spec->curve_c,
+ * curve_q; NaN, NaN = none; needs the fit's range) takes the fitted one's place for the image -- the reference's common
+ * normalisation between runs; the fit is still reported.  The curve is made and checked on the host: a given curve with
+ * a value that is not finite and > 0 is REFUSED before anything runs.  A fit that has no answer (a receiver of its range
+ * without energy: fit = NaN) makes no curve: curve_made = 0 and res->curve, image_curve, image_curve_se are NaN.  Only the
+ * small arrays come back; a refusal touches nothing.  spec->mode and d_curve are not read; rho is.  Further refusals: a
+ * null res or one of its image, image_se, summed, summed_se; with a fit a null curve, image_curve or image_curve_se; a
+ * spec whose n_seismometers / n_bins are not the model's; a given curve without a fit.  A job sharded over several
+ * devices (r3d_node_run_batched) has no image call, and the image cannot be combined with r3d_run_batched_windows in one
+ * run: both out of scope.                                                                                              */
+#define R3D_ARRAY_LEGACY 0
+#define R3D_ARRAY_CURVE  1
+typedef struct r3d_array_image_spec {
+  uint32_t size;                    /* sizeof(r3d_array_image_spec): a mismatch is refused     */
+  uint32_t n_seismometers, n_bins;
+  uint32_t first, last;             /* the array: seismometers first .. last                   */
+  uint32_t gamma_log2;              /* gamma = 2^gamma_log2: 0, 1 or 2                          */
+  int32_t  mode;                    /* R3D_ARRAY_LEGACY / R3D_ARRAY_CURVE                       */
+  uint32_t fit_begin, fit_end;      /* 1-based inclusive points of the fit; 0, 0 = none  (run) */
+  uint32_t pad_;
+  double   weight[R3D_N_ENERGY];
+  double   rho;                     /* LEGACY: the norm ratio, 0 = by area .. 1 = by peak      */
+  const double* d_curve;            /* CURVE: [A] curve values; device                          */
+  double   window_length;           /* Tw = n_bins * dt                                         */
+  double   range[2];                /* distances of receivers first and last            (run) */
+  double   curve_c, curve_q;        /* a curve given outright; NaN, NaN = none           (run) */
+} r3d_array_image_spec;
+typedef struct r3d_array_image_result {
+  uint32_t size;                    /* sizeof(r3d_array_image_result)                          */
+  uint32_t curve_made;              /* WRITTEN with a fit: 1 if the CURVE image was made       */
+  double*   image;                  /* [A][n_bins]                                             */
+  double*   image_se;               /* [A][n_bins]                                             */
+  double*   summed;                 /* [A]  ADDED into                                         */
+  double*   summed_se;              /* [A]                                                     */
+  double*   peak;                   /* [A]       may be NULL                                   */
+  uint32_t* peak_bin;               /* [A]       may be NULL                                   */
+  uint32_t* lit;                    /* [A]       may be NULL                                   */
+  double*   batch_row_sum;          /* [B][A]    may be NULL                                   */
+  double    fit[2], fit_se[2];      /* with a fit: c, q and se(ln c), se(q)                    */
+  double*   curve;                  /* [A]            with a fit                               */
+  double*   image_curve;            /* [A][n_bins]    with a fit                               */
+  double*   image_curve_se;         /* [A][n_bins]    with a fit                               */
+} r3d_array_image_result;
+int r3d_array_image(int device, uint32_t n_batches, const double* d_batch_energy, const r3d_array_image_spec* spec,
+                    double* d_image, double* d_image_se, double* d_row_sum, double* d_peak, uint32_t* d_peak_bin,
+                    uint32_t* d_lit, uint64_t* d_bad, void* stream);
+int r3d_array_powerlaw(uint32_t n_array, double r_first, double r_last, const double* y, uint64_t stride, uint32_t ibegin,
+                       uint32_t iend, double fit[2]);
+int r3d_array_powerlaw_jackknife(uint32_t n_array, double r_first, double r_last, uint32_t n_batches, const double* y,
+                                 uint64_t batch_stride, uint32_t ibegin, uint32_t iend, double fit[2], double se[2],
+                                 double* total);
+int r3d_run_batched_array_image(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                                r3d_result* out, double* energy_se, double* counts_se, const r3d_array_image_spec* spec,
+                                r3d_array_image_result* res);
+
 /* Self-test hook: evaluates one of the kernel's own elementary functions
  * (radiative3d_amd/csrc/r3d_math.h -- the traversal uses these instead of the
  * device library's exp / log / atanh / asin / atan2 / sincos) on the device,

@@ -145,6 +145,53 @@ int r3dh_lapse_request(const r3dh_model* m, r3dh_lapse_opts* rq);
 int r3dh_lapse_plan(const r3dh_model* m, const r3dh_lapse_opts* rq, double* distances, uint32_t* bins, int32_t* clipped);
 int r3dh_write_lapse(const r3dh_model* m, const r3dh_lapse_opts* rq, const r3dh_lapse_result* res, const char* path);
 
+/* --ttimage[=GAMMA,NORM] [--ttimage-array=FIRST,LAST] [--ttimage-axes=X,Y,Z] [--ttimage-fit=IBEGIN,IEND]
+ * [--ttimage-normcurve=C,Q] in the model's arguments (the last four refused without the first, the first without
+ * --error-batches, with --job-error-batches and with --lapse-windows, --ttimage-normcurve without --ttimage-fit): the
+ * travel-time image of a receiver array, vis/seisplot/array.m -> arrayimage.m with normcurve_fitpowerlaw.m, with jackknife
+ * errors from the batches (r3d.h r3d_run_batched_array_image).
+ * r3dh_ttimage_request: returns 1 and fills *rq when the image was asked for, 0 otherwise; -1 (r3dh_last_error) if
+ * --ttimage-array's LAST is not a seismometer of the model or --ttimage-fit's IEND not a point of the array.
+ * r3dh_ttimage_plan: for the A = last - first + 1 receivers of the array, distances [A] as r3dh_lapse_plan gives them
+ * (range_km.m) and azimuths [A] (azimuth_deg.m: degrees east of north from EventLoc to Location, in [0, 360)).  0 ok.
+ * r3dh_write_ttimage: ttimage.octv-style GNU/Octave text at 17 digits to `path`, rows the array's receivers in order,
+ * 0-based indices:  TTSeismometers [A], TTBatches, TTDistances / TTAzimuths [A], TTTimeWindow [2], TTNumBins, TTAxes [3],
+ * TTGamma, TTNorm, TTImage / TTImage_se [A][n_bins] (arrayimage.m's legacy normalisation), TTLit [A] (0: a row without
+ * energy, all +0.0), TTSummedEnergy / TTSummedEnergy_se [A] (summed / summed_se times dt: NS.SummedEnergy), TTPeakEnergy
+ * / TTPeakBin [A]; and with has_fit TTFitRange [2] (IBEGIN, IEND as given, 1-based), TTPLCQ_Summed [2] (c, q),
+ * TTPLCQ_Summed_se [2] (se of ln c, se of q), TTNormCurve [A], TTImageCurve / TTImageCurve_se [A][n_bins] (NaN where the
+ * fit had no answer and no curve was given).  Returns 0 ok.                                                            */
+typedef struct r3dh_ttimage_opts {
+  uint32_t size;                 /* sizeof(r3dh_ttimage_opts)                                    */
+  uint32_t first, last;          /* the array: seismometers first .. last                        */
+  uint32_t gamma_log2;           /* GAMMA = 2^gamma_log2                                         */
+  uint32_t fit_begin, fit_end;   /* --ttimage-fit, 1-based inclusive; 0, 0 = none                */
+  double   norm;                 /* NORM: the norm ratio                                         */
+  double   axes[3];              /* weights of the trace's X, Y, Z                               */
+  double   curve_c, curve_q;     /* --ttimage-normcurve; NaN, NaN = none                         */
+} r3dh_ttimage_opts;
+typedef struct r3dh_ttimage_result {
+  uint32_t size;                 /* sizeof(r3dh_ttimage_result)                                  */
+  uint32_t n_batches;
+  uint32_t has_fit, curve_made;
+  const double*   distances;     /* [A]  r3dh_ttimage_plan's                                     */
+  const double*   azimuths;      /* [A]                                                          */
+  const double*   image;         /* [A][n_bins]                                                  */
+  const double*   image_se;      /* [A][n_bins]                                                  */
+  const uint32_t* lit;           /* [A]                                                          */
+  const double*   summed;        /* [A]  raw sums of bins                                        */
+  const double*   summed_se;     /* [A]                                                          */
+  const double*   peak;          /* [A]                                                          */
+  const uint32_t* peak_bin;      /* [A]                                                          */
+  double fit[2], fit_se[2];      /* has_fit: c, q; se(ln c), se(q)                               */
+  const double*   curve;         /* [A]          has_fit                                         */
+  const double*   image_curve;   /* [A][n_bins]  has_fit                                         */
+  const double*   image_curve_se;
+} r3dh_ttimage_result;
+int r3dh_ttimage_request(const r3dh_model* m, r3dh_ttimage_opts* rq);
+int r3dh_ttimage_plan(const r3dh_model* m, const r3dh_ttimage_opts* rq, double* distances, double* azimuths);
+int r3dh_write_ttimage(const r3dh_model* m, const r3dh_ttimage_opts* rq, const r3dh_ttimage_result* res, const char* path);
+
 /* For a model built with --device-tables (scattering tables left to the engine):
  * record what r3d_engine_scatterer_stats() returned, so that the scatterer dump
  * and r3dh_scatterer_info show the engine's numbers.  Returns 0 ok.            */

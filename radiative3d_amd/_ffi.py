@@ -18,6 +18,7 @@ R3D_EV_NAMES = ("generated", "iterations", "scatter", "collect", "catch", "refle
                 "transfer", "rtsolve", "volume_out")
 R3D_EV_NUM = len(R3D_EV_NAMES)
 R3D_N_ENERGY, R3D_N_COUNT = 5, 2
+R3D_ARRAY_LEGACY, R3D_ARRAY_CURVE = 0, 1   # include/r3d.h r3d_array_image_spec.mode
 R3D_N_SCALARS = 3 + R3D_INV_NUM + R3D_EV_NUM
 
 _dp = C.POINTER(C.c_double)
@@ -115,6 +116,39 @@ class WindowSpec(C.Structure):
     """include/r3d.h r3d_window_spec"""
     _fields_ = [("size", C.c_uint32), ("n_seismometers", C.c_uint32), ("n_bins", C.c_uint32), ("n_windows", C.c_uint32),
                 ("d_bins", C.c_void_p), ("weight", C.c_double * R3D_N_ENERGY)]
+
+
+class ArrayImageSpec(C.Structure):
+    """include/r3d.h r3d_array_image_spec"""
+    _fields_ = [("size", C.c_uint32), ("n_seismometers", C.c_uint32), ("n_bins", C.c_uint32), ("first", C.c_uint32),
+                ("last", C.c_uint32), ("gamma_log2", C.c_uint32), ("mode", C.c_int32), ("fit_begin", C.c_uint32),
+                ("fit_end", C.c_uint32), ("pad_", C.c_uint32), ("weight", C.c_double * R3D_N_ENERGY), ("rho", C.c_double),
+                ("d_curve", C.c_void_p), ("window_length", C.c_double), ("range", C.c_double * 2), ("curve_c", C.c_double),
+                ("curve_q", C.c_double)]
+
+
+class ArrayImageResult(C.Structure):
+    """include/r3d.h r3d_array_image_result"""
+    _fields_ = [("size", C.c_uint32), ("curve_made", C.c_uint32), ("image", C.c_void_p), ("image_se", C.c_void_p),
+                ("summed", C.c_void_p), ("summed_se", C.c_void_p), ("peak", C.c_void_p), ("peak_bin", C.c_void_p),
+                ("lit", C.c_void_p), ("batch_row_sum", C.c_void_p), ("fit", C.c_double * 2), ("fit_se", C.c_double * 2),
+                ("curve", C.c_void_p), ("image_curve", C.c_void_p), ("image_curve_se", C.c_void_p)]
+
+
+class TTImageOpts(C.Structure):
+    """include/r3d_host.h r3dh_ttimage_opts"""
+    _fields_ = [("size", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("gamma_log2", C.c_uint32),
+                ("fit_begin", C.c_uint32), ("fit_end", C.c_uint32), ("norm", C.c_double), ("axes", C.c_double * 3),
+                ("curve_c", C.c_double), ("curve_q", C.c_double)]
+
+
+class TTImageResult(C.Structure):
+    """include/r3d_host.h r3dh_ttimage_result"""
+    _fields_ = [("size", C.c_uint32), ("n_batches", C.c_uint32), ("has_fit", C.c_uint32), ("curve_made", C.c_uint32),
+                ("distances", C.c_void_p), ("azimuths", C.c_void_p), ("image", C.c_void_p), ("image_se", C.c_void_p),
+                ("lit", C.c_void_p), ("summed", C.c_void_p), ("summed_se", C.c_void_p), ("peak", C.c_void_p),
+                ("peak_bin", C.c_void_p), ("fit", C.c_double * 2), ("fit_se", C.c_double * 2), ("curve", C.c_void_p),
+                ("image_curve", C.c_void_p), ("image_curve_se", C.c_void_p)]
 
 
 class LapseOpts(C.Structure):
@@ -241,6 +275,12 @@ def host_lib():
         L.r3dh_lapse_plan.argtypes = [C.c_void_p, C.POINTER(LapseOpts), _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
         L.r3dh_write_lapse.restype = C.c_int
         L.r3dh_write_lapse.argtypes = [C.c_void_p, C.POINTER(LapseOpts), C.POINTER(LapseResult), C.c_char_p]
+        L.r3dh_ttimage_request.restype = C.c_int
+        L.r3dh_ttimage_request.argtypes = [C.c_void_p, C.POINTER(TTImageOpts)]
+        L.r3dh_ttimage_plan.restype = C.c_int
+        L.r3dh_ttimage_plan.argtypes = [C.c_void_p, C.POINTER(TTImageOpts), _dp, _dp]
+        L.r3dh_write_ttimage.restype = C.c_int
+        L.r3dh_write_ttimage.argtypes = [C.c_void_p, C.POINTER(TTImageOpts), C.POINTER(TTImageResult), C.c_char_p]
         L.r3dh_seismometer_axes.restype = C.c_int
         L.r3dh_seismometer_axes.argtypes = [C.c_void_p, C.c_int]
         _host = L
@@ -423,6 +463,16 @@ def hip_lib(reproducible=False, path=None):
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         L.r3d_window_log_ratio.restype = C.c_int
         L.r3d_window_log_ratio.argtypes = [C.c_uint32, _dp, _dp, C.c_uint64, _dp, _dp]
+        L.r3d_array_image.restype = C.c_int
+        L.r3d_array_image.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.POINTER(ArrayImageSpec)] + [C.c_void_p] * 8
+        L.r3d_array_powerlaw.restype = C.c_int
+        L.r3d_array_powerlaw.argtypes = [C.c_uint32, C.c_double, C.c_double, _dp, C.c_uint64, C.c_uint32, C.c_uint32, _dp]
+        L.r3d_array_powerlaw_jackknife.restype = C.c_int
+        L.r3d_array_powerlaw_jackknife.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_uint32, _dp, C.c_uint64, C.c_uint32,
+                                                   C.c_uint32, _dp, _dp, _dp]
+        L.r3d_run_batched_array_image.restype = C.c_int
+        L.r3d_run_batched_array_image.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
+                                                  _dp, _dp, C.POINTER(ArrayImageSpec), C.POINTER(ArrayImageResult)]
         L.r3d_run_batched_windows.restype = C.c_int
         L.r3d_run_batched_windows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
                                               _dp, _dp, C.POINTER(WindowSpec), _dp, C.POINTER(C.c_uint64), _dp, _dp]

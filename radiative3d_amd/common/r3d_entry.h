@@ -1,7 +1,8 @@
 // r3d_entry.h -- what an entry point of the C-ABI that lives OUTSIDE the engine needs around its launch: the engine's
-// error text, the caller's device kept across the call, device scratch that frees itself, and the refusals the calls
-// on the event grid share.  Host code only, all inline.  An add-on (stats/, views/, maps/) includes this and
-// include/r3d.h and nothing from csrc/; csrc/r3d_volume.hip, whose entry points are of the same kind, uses it too.
+// error text, the caller's device kept across the call, device scratch that frees itself, the refusals the calls on
+// the event grid share, and those of the batched runs with the way they learn their engine's device.  Host code only,
+// all inline.  An add-on (stats/, views/, maps/, arrays/) includes this and include/r3d.h and nothing from csrc/;
+// csrc/r3d_volume.hip, whose entry points are of the same kind, uses it too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -70,6 +71,59 @@ inline const char* bad_frame_range(const r3d_volume_desc* v, uint32_t frame_begi
   if (frame_begin > frame_end) return "frame_end before frame_begin";
   if (frame_end > v->n_frames) return "frame_end beyond the grid's frames";
   return nullptr;
+}
+
+// ---- what the batched runs share (stats/ r3d_run_batched and its kin, arrays/ r3d_run_batched_array_image) ----
+constexpr uint32_t kMaxBatches = 64;   // launches of one engine in flight (include/r3d.h r3d_run_device)
+
+// The device a pointer of the caller's lives on (-1: not device memory).
+inline int device_of(const void* p) {
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  if (attr.type != hipMemoryTypeDevice) return -1;
+  return attr.device;
+}
+
+// What a batched run cannot be combined with, asked of the engine through its public calls.
+inline int refuse_engine_state(r3d_engine* e, const char* who) {
+  if (r3d_engine_carry_pending(e))
+    return refuse(who, "histories carried over by r3d_run_device_carry await their flush; a batch must be a self-contained launch");
+  if (r3d_event_log_read(e, nullptr, 0, 0) != ~uint64_t(0))
+    return refuse(who, "an event log is attached (its launches run the diagnostic kernel, one at a time); detach it first");
+  if (r3d_production_finals_read(e, nullptr, 0, 0) == 0)
+    return refuse(who, "a production-finals buffer is attached; detach it first");
+  return 0;
+}
+
+inline int check_batches(const char* who, uint64_t n, uint32_t n_batches) {
+  if (n_batches < 2)
+    return refuse(who, "at least 2 batches are needed for a variance (got " + std::to_string(n_batches) + ")");
+  if (n_batches > kMaxBatches)
+    return refuse(who, "at most 64 batches (the engine's launches in flight), got " + std::to_string(n_batches));
+  if (n < n_batches)
+    return refuse(who, "fewer histories (" + std::to_string(n) + ") than batches (" + std::to_string(n_batches) + ")");
+  return 0;
+}
+
+// The engine's device, learned from an address it owns: the only one the interface hands out is its event grid's,
+// so an engine without a grid gets one of a single cell for the length of the question.  -1 with the message set.
+inline int engine_device(r3d_engine* e, const char* who) {
+  int device = -1;
+  if (r3d_volume_len(e)) {
+    device = device_of(r3d_volume_device_ptr(e));
+  } else {
+    r3d_volume_desc one{};
+    one.cell_size[0] = one.cell_size[1] = one.cell_size[2] = 1.0, one.dims[0] = one.dims[1] = one.dims[2] = 1;
+    one.n_frames = 1, one.frame_dt = 1.0;
+    if (r3d_engine_set_volume(e, &one)) return -1;
+    device = device_of(r3d_volume_device_ptr(e));
+    if (r3d_engine_set_volume(e, nullptr)) return -1;
+  }
+  if (device < 0) refuse(who, "the engine's device could not be determined");
+  return device;
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

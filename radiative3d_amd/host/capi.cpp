@@ -198,6 +198,46 @@ int r3dh_write_lapse(const r3dh_model* m, const r3dh_lapse_opts* rq, const r3dh_
   return 1;
 }
 
+int r3dh_ttimage_request(const r3dh_model* m, r3dh_ttimage_opts* rq) {
+  if (!m || !m->mission.bTTImage) return 0;
+  if (!rq) return 1;
+  try {
+    TTImageRequest(*m->model, m->mission, rq);
+    return 1;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return -1;
+}
+
+int r3dh_ttimage_plan(const r3dh_model* m, const r3dh_ttimage_opts* rq, double* distances, double* azimuths) {
+  if (!m || !rq || !distances || !azimuths) return g_error = "r3dh_ttimage_plan: null argument", 1;
+  try {
+    // (through the global coordinate system, as r3dh_lapse_plan)
+    TTImagePlan(*m->model, *rq, distances, azimuths);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
+int r3dh_write_ttimage(const r3dh_model* m, const r3dh_ttimage_opts* rq, const r3dh_ttimage_result* res, const char* path) {
+  if (!m || !rq || !res || !path) return g_error = "r3dh_write_ttimage: null argument", 1;
+  if (!res->distances || !res->azimuths || !res->image || !res->image_se || !res->lit || !res->summed || !res->summed_se ||
+      !res->peak || !res->peak_bin || (res->has_fit && (!res->curve || !res->image_curve || !res->image_curve_se)))
+    return g_error = "r3dh_write_ttimage: null array in the result", 1;
+  try {
+    std::ofstream f(path);
+    OutputTTImage(*m->model, *rq, *res, f);
+    if (!f) throw Runtime(std::string("cannot write ") + path);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
 int r3dh_model_set_scatterer_stats(r3dh_model* m, int s, const double mfp[2], const double dipole[2]) {
   if (!m || !mfp || !dipole || s < 0 || s >= (int)m->model->Scatterers().size()) return 1;
   m->model->SetScattererStats(s, mfp, dipole);

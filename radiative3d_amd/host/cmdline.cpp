@@ -20,7 +20,8 @@ enum OptID {
   OPTM_RTTEST, OPTM_EVENTTEST, OPTM_RUNSIM, OPTX_SEED, OPTX_GPUS, OPTX_DEVTABLES, OPTX_HOSTTABLES,
   OPTX_DEVICES, OPTX_SCATGRID, OPTX_SCATGRID_FILE, OPTX_ERRBATCHES,
   OPTX_SCATVIEWS, OPTX_SCATVIEW_AZI, OPTX_NO_SCATGRID_FILE, OPTX_SCATMAPS, OPTX_JOBERRBATCHES,
-  OPTX_LAPSE, OPTX_LAPSE_AXES, OPTX_LAPSE_GEOSPREAD, OPTX_LAPSE_RANGES, OPTX_LAPSE_ARRAY
+  OPTX_LAPSE, OPTX_LAPSE_AXES, OPTX_LAPSE_GEOSPREAD, OPTX_LAPSE_RANGES, OPTX_LAPSE_ARRAY,
+  OPTX_TTIMAGE, OPTX_TTIMAGE_ARRAY, OPTX_TTIMAGE_AXES, OPTX_TTIMAGE_FIT, OPTX_TTIMAGE_NORMCURVE
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -56,7 +57,9 @@ const std::map<std::string, OptID>& option_table() {
       {"--scatter-views", OPTX_SCATVIEWS}, {"--scatter-view-azimuth", OPTX_SCATVIEW_AZI},
       {"--no-scatter-grid-file", OPTX_NO_SCATGRID_FILE}, {"--scatter-maps", OPTX_SCATMAPS},
       {"--lapse-windows", OPTX_LAPSE}, {"--lapse-axes", OPTX_LAPSE_AXES}, {"--lapse-geospread", OPTX_LAPSE_GEOSPREAD},
-      {"--lapse-ranges", OPTX_LAPSE_RANGES}, {"--lapse-array", OPTX_LAPSE_ARRAY}};
+      {"--lapse-ranges", OPTX_LAPSE_RANGES}, {"--lapse-array", OPTX_LAPSE_ARRAY},
+      {"--ttimage", OPTX_TTIMAGE}, {"--ttimage-array", OPTX_TTIMAGE_ARRAY}, {"--ttimage-axes", OPTX_TTIMAGE_AXES},
+      {"--ttimage-fit", OPTX_TTIMAGE_FIT}, {"--ttimage-normcurve", OPTX_TTIMAGE_NORMCURVE}};
   return t;
 }
 
@@ -362,6 +365,48 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
           throw Runtime("--lapse-array=FIRST,LAST: seismometer indices with 0 <= FIRST <= LAST.");
         mission.LapseCompanion = "--lapse-array";
         break;
+      case OPTX_TTIMAGE: {
+        if (o.has()) {
+          mission.TTGamma = o.real();
+          mission.TTNorm = o.real();
+        }
+        if (mission.TTGamma != 1.0 && mission.TTGamma != 2.0 && mission.TTGamma != 4.0)
+          throw Runtime("--ttimage[=GAMMA,NORM]: GAMMA must be 1, 2 or 4 (the gamma root is taken as repeated square roots).");
+        if (!(mission.TTNorm >= 0.0 && mission.TTNorm <= 1.0))
+          throw Runtime("--ttimage[=GAMMA,NORM]: the norm ratio NORM must lie in [0, 1] (0: by area, 1: by peak).");
+        mission.bTTImage = true;
+        break;
+      }
+      case OPTX_TTIMAGE_ARRAY:
+        mission.TTArray[0] = o.integer();
+        mission.TTArray[1] = o.integer();
+        if (mission.TTArray[0] < 0 || mission.TTArray[1] < mission.TTArray[0])
+          throw Runtime("--ttimage-array=FIRST,LAST: seismometer indices with 0 <= FIRST <= LAST.");
+        mission.TTCompanion = "--ttimage-array";
+        break;
+      case OPTX_TTIMAGE_AXES:
+        for (int k = 0; k < 3; k++) mission.TTAxes[k] = o.real();
+        for (int k = 0; k < 3; k++)
+          if (!std::isfinite(mission.TTAxes[k]) || mission.TTAxes[k] < 0)
+            throw Runtime("--ttimage-axes=X,Y,Z: the weights must be finite and not negative (roots are taken of the weighted energy).");
+        mission.TTCompanion = "--ttimage-axes";
+        break;
+      case OPTX_TTIMAGE_FIT:
+        mission.TTFit[0] = o.integer();
+        mission.TTFit[1] = o.integer();
+        if (mission.TTFit[0] < 1 || mission.TTFit[1] <= mission.TTFit[0])
+          throw Runtime("--ttimage-fit=IBEGIN,IEND: the 1-based inclusive points of the array the power law is fitted over, "
+                        "1 <= IBEGIN < IEND.");
+        mission.TTCompanion = "--ttimage-fit";
+        break;
+      case OPTX_TTIMAGE_NORMCURVE:
+        mission.TTNormCurve[0] = o.real();
+        mission.TTNormCurve[1] = o.real();
+        if (!(mission.TTNormCurve[0] > 0) || !std::isfinite(mission.TTNormCurve[0]) || !std::isfinite(mission.TTNormCurve[1]))
+          throw Runtime("--ttimage-normcurve=C,Q: the curve C X^Q needs C > 0 and both numbers finite.");
+        mission.bTTNormCurve = true;
+        mission.TTCompanion = "--ttimage-normcurve";
+        break;
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }
@@ -391,6 +436,19 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
   if (mission.bLapse && !mission.ErrorBatches)
     throw Runtime("--lapse-windows needs --error-batches=B: the windows' standard errors and the ratios' jackknife come from "
                   "the B batches.");
+  // the travel-time image's errors come from one device's batches, too
+  if (mission.TTCompanion && !mission.bTTImage)
+    throw Runtime(std::string(mission.TTCompanion) + " needs --ttimage: it only says how that image is made.");
+  if (mission.bTTImage && mission.JobErrorBatches)
+    throw Runtime("--ttimage cannot be combined with --job-error-batches: the image is made where ONE device's batch blocks "
+                  "lie (r3d_run_batched_array_image); a job sharded over devices has no image call.  Use --error-batches=B.");
+  if (mission.bTTImage && !mission.ErrorBatches)
+    throw Runtime("--ttimage needs --error-batches=B: the pixels' and the fit's standard errors are jackknives over the B batches.");
+  if (mission.bTTImage && mission.bLapse)
+    throw Runtime("--ttimage cannot be combined with --lapse-windows in one run (each keeps the run's batch blocks for itself): "
+                  "out of scope.");
+  if (mission.bTTNormCurve && mission.TTFit[0] == 0)
+    throw Runtime("--ttimage-normcurve needs --ttimage-fit=IBEGIN,IEND: the curve's range window comes from the fit's array.");
   // the views and the maps are made from the grid: none of their options means anything without it
   if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile || mission.bScatterMaps))
     throw Runtime(std::string(mission.bScatterViews ? "--scatter-views" : mission.bViewAzimuth ? "--scatter-view-azimuth"

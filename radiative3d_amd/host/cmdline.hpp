@@ -7,7 +7,7 @@
 // (cmdline.cpp:343-390).  Engine-only additions: --seed, --gpus, --devices, --host-tables / --device-tables,
 // --scatter-grid / --scatter-grid-file (the scatter-event histogram of a video run, written as a file),
 // --error-batches / --job-error-batches (per-bin standard errors), --lapse-windows and its four companions (lapse-window
-// energies and coda ratios with batch errors).
+// energies and coda ratios with batch errors), --ttimage and its four (the array's travel-time image with jackknife errors).
 #ifndef R3DH_CMDLINE_HPP_
 #define R3DH_CMDLINE_HPP_
 
@@ -64,6 +64,16 @@ struct MissionParams {
   double LapseEdge[2] = {3.6, 0.0}, LapseWindows[4] = {5.0, 20.0, 45.0, 115.0}, LapseAxes[3] = {0.0, 0.0, 1.0};
   double LapseGeoSpread = 2.0, LapseRanges[3] = {8.0, 50.0, 150.0};
   long LapseArray[2] = {0, -1};           // LAST < 0: through the last receiver
+  // --ttimage[=GAMMA,NORM]: the travel-time image of a receiver array (vis/seisplot/arrayimage.m) with jackknife errors of
+  // every pixel and of the power-law fit, made on the GPU from the batches of --error-batches (include/r3d.h
+  // r3d_run_batched_array_image), as ttimage.octv; --ttimage-array=FIRST,LAST the receivers (default all), --ttimage-axes
+  // the weights of the three trace axes, --ttimage-fit=IBEGIN,IEND the 1-based points normcurve_fitpowerlaw.m fits over,
+  // --ttimage-normcurve=C,Q a curve C X^Q given outright for the curve-normalised image.
+  bool bTTImage = false, bTTNormCurve = false;
+  const char* TTCompanion = nullptr;      // one of the four that was given (they are refused without --ttimage)
+  double TTGamma = 2.0, TTNorm = 0.3, TTAxes[3] = {1.0, 1.0, 1.0}, TTNormCurve[2] = {0.0, 0.0};
+  long TTArray[2] = {0, -1};              // LAST < 0: through the last receiver
+  long TTFit[2] = {0, 0};                 // 0, 0: no fit
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

@@ -51,6 +51,13 @@ void LapseRequest(const Model& model, const MissionParams& mission, r3dh_lapse_o
 void LapsePlan(const Model& model, const r3dh_lapse_opts& rq, double* distances, uint32_t* bins, int32_t* clipped);
 void OutputLapse(const Model& model, const r3dh_lapse_opts& rq, const r3dh_lapse_result& res, std::ostream& out);
 
+// The travel-time image of --ttimage (include/r3d_host.h has the request, the plan, the file's items): TTImageRequest fills
+// *rq from the mission (throws if --ttimage-array or --ttimage-fit names what the model's array does not have),
+// TTImagePlan the array's distances and azimuths, OutputTTImage writes the file's text.
+void TTImageRequest(const Model& model, const MissionParams& mission, r3dh_ttimage_opts* rq);
+void TTImagePlan(const Model& model, const r3dh_ttimage_opts& rq, double* distances, double* azimuths);
+void OutputTTImage(const Model& model, const r3dh_ttimage_opts& rq, const r3dh_ttimage_result& res, std::ostream& out);
+
 // --reports keywords (reference main.cpp:223-258) -> R3D_RPT_* mask.  `csv` is the keyword
 // list as given ("ALL_ON", "GEN,SCT,REF", "SCATTERS", ...); empty = none.  ApplyReportKeyword: `mask` after ONE
 // keyword of the list; both throw the one sentence that names the valid keywords for any other word.

@@ -7,7 +7,8 @@
 // is the output stage of scatter_out.cpp; this file builds its job, has it checked before the run and calls it once.
 //
 // Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B`,
-// `--job-error-batches=N` (error bars of a job on any number of shards) and `--lapse-windows` (lapse.octv) are accepted (the reference seeds from the clock,
+// `--job-error-batches=N` (error bars of a job on any number of shards), `--lapse-windows` (lapse.octv) and `--ttimage`
+// (ttimage.octv) are accepted (the reference seeds from the clock,
 // is single-process, has no event histogram and no error bars); the `--reports` stream is written
 // after the run, grouped by history, where the reference writes its lines as they happen (the engine appends binary
 // records in HBM: include/r3d.h r3d_event); tables are built in HBM unless `--host-tables` is given.
@@ -133,6 +134,12 @@ struct SimulationOutput {
   std::vector<uint32_t> lapse_bins;
   std::vector<int32_t> lapse_clipped;
   std::vector<uint64_t> lapse_counts;
+  // --ttimage: the array's plan and its image (include/r3d_host.h r3dh_ttimage_result), [A] receivers
+  r3dh_ttimage_opts tt{};
+  r3dh_ttimage_result tt_res{};
+  std::vector<double> tt_distances, tt_azimuths, tt_image, tt_image_se, tt_summed, tt_summed_se, tt_peak, tt_curve, tt_cimage,
+      tt_cimage_se;
+  std::vector<uint32_t> tt_peak_bin, tt_lit;
 };
 
 // The report stream of the run, shard after shard (ids ascend across shards): at most caps[g] records of engine g,
@@ -203,6 +210,39 @@ SimulationOutput run_simulation(const Model& model, const MissionParams& mission
       for (size_t j = 0; j < B; j++)
         out.lapse_batch_energy.insert(out.lapse_batch_energy.end(), bwe.begin() + 2 * (j * all + lo),
                                       bwe.begin() + 2 * (j * all + lo + S));
+    } else if (mission.bTTImage) {
+      // --ttimage: the same run with its batch blocks kept on the device and the array's image, fit and their jackknives
+      // made there (include/r3d.h r3d_run_batched_array_image)
+      TTImageRequest(model, mission, &out.tt);
+      const size_t A = (size_t)out.tt.last - out.tt.first + 1, px = A * d.params.n_bins;
+      out.tt_distances.assign(A, 0.0), out.tt_azimuths.assign(A, 0.0);
+      TTImagePlan(model, out.tt, out.tt_distances.data(), out.tt_azimuths.data());
+      r3d_array_image_spec spec{};
+      spec.size = sizeof spec, spec.n_seismometers = (uint32_t)d.n_seismometers, spec.n_bins = d.params.n_bins;
+      spec.first = out.tt.first, spec.last = out.tt.last, spec.gamma_log2 = out.tt.gamma_log2, spec.mode = R3D_ARRAY_LEGACY;
+      spec.fit_begin = out.tt.fit_begin, spec.fit_end = out.tt.fit_end, spec.rho = out.tt.norm;
+      for (int k = 0; k < 3; k++) spec.weight[k] = out.tt.axes[k];
+      spec.window_length = d.params.time_per_bin * d.params.n_bins;
+      spec.range[0] = out.tt_distances.front(), spec.range[1] = out.tt_distances.back();
+      spec.curve_c = out.tt.curve_c, spec.curve_q = out.tt.curve_q;
+      const bool fit = spec.fit_begin != 0;
+      out.tt_image.assign(px, 0.0), out.tt_image_se.assign(px, 0.0), out.tt_summed.assign(A, 0.0), out.tt_summed_se.assign(A, 0.0);
+      out.tt_peak.assign(A, 0.0), out.tt_peak_bin.assign(A, 0), out.tt_lit.assign(A, 0);
+      if (fit) out.tt_curve.assign(A, 0.0), out.tt_cimage.assign(px, 0.0), out.tt_cimage_se.assign(px, 0.0);
+      r3d_array_image_result res{};
+      res.size = sizeof res, res.image = out.tt_image.data(), res.image_se = out.tt_image_se.data();
+      res.summed = out.tt_summed.data(), res.summed_se = out.tt_summed_se.data(), res.peak = out.tt_peak.data();
+      res.peak_bin = out.tt_peak_bin.data(), res.lit = out.tt_lit.data();
+      if (fit) res.curve = out.tt_curve.data(), res.image_curve = out.tt_cimage.data(), res.image_curve_se = out.tt_cimage_se.data();
+      if (r3d_run_batched_array_image(engines[0], n, 0, seed, mission.ErrorBatches, &out.total, out.energy_se.data(),
+                                      out.counts_se.data(), &spec, &res))
+        throw Runtime(r3d_last_error());
+      r3dh_ttimage_result& w = out.tt_res;
+      w.size = sizeof w, w.n_batches = mission.ErrorBatches, w.has_fit = fit, w.curve_made = res.curve_made;
+      w.distances = out.tt_distances.data(), w.azimuths = out.tt_azimuths.data(), w.image = res.image, w.image_se = res.image_se;
+      w.lit = res.lit, w.summed = res.summed, w.summed_se = res.summed_se, w.peak = res.peak, w.peak_bin = res.peak_bin;
+      for (int k = 0; k < 2; k++) w.fit[k] = res.fit[k], w.fit_se[k] = res.fit_se[k];
+      w.curve = res.curve, w.image_curve = res.image_curve, w.image_curve_se = res.image_curve_se;
     } else if (r3d_run_batched(engines[0], n, 0, seed, mission.ErrorBatches, &out.total, out.energy_se.data(),
                                out.counts_se.data())) {
       throw Runtime(r3d_last_error());
@@ -271,7 +311,13 @@ int main(int argc, char* argv[]) {
               << "--lapse-windows[=V,T0,B1,E1,B2,E2] (with --error-batches; default 3.6,0,5,20,45,115): the energy in two lapse windows\n"
               << "behind the phase edge (V km/s, T0 s) per receiver and the coda ratios R1, R2 of them, summed on the GPU over every\n"
               << "batch, with standard errors, as lapse.octv; --lapse-axes=X,Y,Z (default 0,0,1)  --lapse-geospread=G (default 2)\n"
-              << "--lapse-ranges=R0,RA,RB (default 8,50,150 km)  --lapse-array=FIRST,LAST (seismometer indices; default all)\n\n";
+              << "--lapse-ranges=R0,RA,RB (default 8,50,150 km)  --lapse-array=FIRST,LAST (seismometer indices; default all)\n"
+              << "--ttimage[=GAMMA,NORM] (with --error-batches; default 2,0.3; GAMMA 1, 2 or 4): the travel-time image of a receiver\n"
+              << "array (arrayimage.m) made on the GPU with jackknife standard errors of every pixel, as ttimage.octv;\n"
+              << "--ttimage-array=FIRST,LAST (default all)  --ttimage-axes=X,Y,Z (default 1,1,1)  --ttimage-fit=IBEGIN,IEND: the power\n"
+              << "law Sum(E dt) = c X^q over the array's 1-based points IBEGIN .. IEND (normcurve_fitpowerlaw.m) with its jackknife, and\n"
+              << "the image normalised by that curve  --ttimage-normcurve=C,Q (with --ttimage-fit): a curve given outright in its place.\n"
+              << "Not in one run with --lapse-windows or --job-error-batches (out of scope)\n\n";
     return 0;
   }
   // A simulation run makes its tables where it uses them (seconds of host work and GBs of upload
@@ -367,6 +413,12 @@ int main(int argc, char* argv[]) {
           const std::string fn = (mission.OutputDir.empty() ? std::string() : mission.OutputDir + "/") + "lapse.octv";
           std::ofstream f(fn.c_str());
           OutputLapse(model, run.lapse, res, f);
+          if (!f) throw Runtime("cannot write " + fn);
+        }
+        if (mission.bTTImage) {
+          const std::string fn = (mission.OutputDir.empty() ? std::string() : mission.OutputDir + "/") + "ttimage.octv";
+          std::ofstream f(fn.c_str());
+          OutputTTImage(model, run.tt, run.tt_res, f);
           if (!f) throw Runtime("cannot write " + fn);
         }
       }

@@ -12,6 +12,7 @@ There is no CPU fallback here: without libr3d_hip.so (or without a GPU)
 ``Engine`` raises.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -310,6 +311,69 @@ class Model:
         if self._lib.r3dh_write_lapse(self._h, C.byref(rq), C.byref(res), str(path).encode()):
             raise RuntimeError("write_lapse failed: " + self._lib.r3dh_last_error().decode())
 
+    @property
+    def ttimage_request(self):
+        """What --ttimage[=GAMMA,NORM] and its companions (--ttimage-array, --ttimage-axes, --ttimage-fit,
+        --ttimage-normcurve) asked for: None, or dict(first, last, gamma_log2, norm, axes, fit, curve) -- the array's
+        seismometers first .. last inclusive, fit the 1-based (IBEGIN, IEND) or (0, 0), curve (C, Q) or NaNs
+        (include/r3d_host.h r3dh_ttimage_opts)."""
+        rq = _ffi.TTImageOpts()
+        rc = self._lib.r3dh_ttimage_request(self._h, C.byref(rq))
+        if rc < 0:
+            raise RuntimeError("ttimage_request failed: " + self._lib.r3dh_last_error().decode())
+        if rc == 0:
+            return None
+        return dict(first=int(rq.first), last=int(rq.last), gamma_log2=int(rq.gamma_log2), norm=rq.norm, axes=tuple(rq.axes),
+                    fit=(int(rq.fit_begin), int(rq.fit_end)), curve=(rq.curve_c, rq.curve_q))
+
+    @staticmethod
+    def _ttimage_opts(request):
+        fit, curve = request.get("fit", (0, 0)), request.get("curve", (math.nan, math.nan))
+        return _ffi.TTImageOpts(size=C.sizeof(_ffi.TTImageOpts), first=int(request["first"]), last=int(request["last"]),
+                                gamma_log2=int(request.get("gamma_log2", 1)), fit_begin=int(fit[0]), fit_end=int(fit[1]),
+                                norm=float(request.get("norm", 0.3)),
+                                axes=(C.c_double * 3)(*[float(v) for v in request.get("axes", (1, 1, 1))]),
+                                curve_c=float(curve[0]), curve_q=float(curve[1]))
+
+    def ttimage_plan(self, request=None):
+        """(distances [A], azimuths [A]) of the image's array (`request`: a dict as ttimage_request gives, of which first
+        and last are read; None: the model's own): every receiver's epicentral distance and azimuth as
+        vis/seisplot/range_km.m and azimuth_deg.m take them from seis_NNN.octv."""
+        request = request if request is not None else self.ttimage_request
+        if request is None:
+            raise RuntimeError("the model's arguments hold no --ttimage")
+        rq = self._ttimage_opts(request)
+        A = int(rq.last) - int(rq.first) + 1
+        if A < 1:
+            raise ValueError("ttimage request: first > last")
+        dist, azi = np.zeros(A), np.zeros(A)
+        if self._lib.r3dh_ttimage_plan(self._h, C.byref(rq), dist.ctypes.data_as(_ffi._dp), azi.ctypes.data_as(_ffi._dp)):
+            raise RuntimeError("ttimage_plan failed: " + self._lib.r3dh_last_error().decode())
+        return dist, azi
+
+    def write_ttimage(self, path, plan, image, n_batches, request=None):
+        """Write ttimage.octv (include/r3d_host.h r3dh_write_ttimage) to `path`: plan = ttimage_plan(request), image the
+        dict Engine.run_batched_array_image returned for the request's array."""
+        request = request if request is not None else self.ttimage_request
+        if request is None:
+            raise RuntimeError("the model's arguments hold no --ttimage")
+        rq = self._ttimage_opts(request)
+        keep = [np.ascontiguousarray(plan[0], dtype=np.float64), np.ascontiguousarray(plan[1], dtype=np.float64)]
+        has_fit = "fit" in image
+        for name, kind in (("image", np.float64), ("image_se", np.float64), ("lit", np.uint32), ("summed", np.float64),
+                           ("summed_se", np.float64), ("peak", np.float64), ("peak_bin", np.uint32)):
+            keep.append(np.ascontiguousarray(image[name], dtype=kind))
+        res = _ffi.TTImageResult(C.sizeof(_ffi.TTImageResult), int(n_batches), int(has_fit), int(image.get("curve_made", 0)),
+                                 *[a.ctypes.data for a in keep])
+        if has_fit:
+            for name in ("curve", "image_curve", "image_curve_se"):
+                keep.append(np.ascontiguousarray(image[name], dtype=np.float64))
+                setattr(res, name, keep[-1].ctypes.data)
+            for k in range(2):
+                res.fit[k], res.fit_se[k] = image["fit"][k], image["fit_se"][k]
+        if self._lib.r3dh_write_ttimage(self._h, C.byref(rq), C.byref(res), str(path).encode()):
+            raise RuntimeError("write_ttimage failed: " + self._lib.r3dh_last_error().decode())
+
     def new_result(self):
         return Result(self.n_seismometers, self.n_bins)
 
@@ -438,6 +502,88 @@ def window_sums(batch_energy, bins, weights, batch_counts=None, window_energy=No
     if rc:
         raise RuntimeError("r3d_window_sums failed: " + lib.r3d_last_error().decode())
     return window_energy, window_counts, bad
+
+
+def array_image_spec(n_seismometers, n_bins, first, last, weights, gamma_log2=1, rho=0.3, curve_ptr=None, window_length=0.0,
+                     fit=(0, 0), ranges=(0.0, 0.0), curve=(math.nan, math.nan)):
+    """An r3d_array_image_spec (include/r3d.h): LEGACY mode with the norm ratio `rho`, or -- with curve_ptr, the device
+    address of the array's [A] curve values -- CURVE mode with window_length = n_bins * dt.  fit (1-based IBEGIN, IEND),
+    ranges (the distances of receivers first and last) and curve (c, q given outright) are read by
+    Engine.run_batched_array_image only."""
+    w = [float(v) for v in weights]
+    if len(w) != _ffi.R3D_N_ENERGY:
+        raise ValueError("five component weights (X, Y, Z, P, S) are needed")
+    return _ffi.ArrayImageSpec(size=C.sizeof(_ffi.ArrayImageSpec), n_seismometers=int(n_seismometers), n_bins=int(n_bins),
+                               first=int(first), last=int(last), gamma_log2=int(gamma_log2),
+                               mode=_ffi.R3D_ARRAY_CURVE if curve_ptr else _ffi.R3D_ARRAY_LEGACY, fit_begin=int(fit[0]),
+                               fit_end=int(fit[1]), weight=(C.c_double * _ffi.R3D_N_ENERGY)(*w), rho=float(rho),
+                               d_curve=curve_ptr, window_length=float(window_length),
+                               range=(C.c_double * 2)(float(ranges[0]), float(ranges[1])), curve_c=float(curve[0]),
+                               curve_q=float(curve[1]))
+
+
+def array_image(batch_energy, first, last, weights, gamma_log2=1, rho=0.3, curve=None, window_length=0.0, with_se=None,
+                image=None, image_se=None, stream=None):
+    """r3d_array_image on torch tensors of one device: batch_energy [B, S, n_bins, 5] float64 are B batch blocks, the array
+    the receivers first .. last (A of them), weights the five component weights (>= 0).  LEGACY mode with the norm ratio
+    rho, or CURVE mode with `curve` (float64 [A] on the device) and window_length = n_bins * dt.  Returns a dict of
+    tensors, all WRITTEN: image [A, n_bins], image_se [A, n_bins] (with_se; default: B >= 2), row_sum [B, A], peak [A],
+    peak_bin [A] and lit [A] (int32), bad [1] (int64: the bad curve values).  include/r3d.h has the arithmetic.
+    Asynchronous on `stream` (a raw hipStream_t; None: torch's current one)."""
+    import torch
+    lib = _ffi.hip_lib()
+    if batch_energy.dim() != 4 or batch_energy.shape[3] != _ffi.R3D_N_ENERGY or batch_energy.dtype != torch.float64:
+        raise ValueError("batch_energy must be float64 [B, S, n_bins, 5]")
+    if not batch_energy.is_cuda or not batch_energy.is_contiguous():
+        raise ValueError("the blocks must be a contiguous tensor on a GPU")
+    B, S, n_bins = (int(v) for v in batch_energy.shape[:3])
+    dev = batch_energy.device
+    A = int(last) - int(first) + 1
+    if A < 1 or last >= S:
+        raise ValueError("the array first .. last must lie within the blocks' seismometers")
+    if curve is not None and (curve.dtype != torch.float64 or curve.numel() != A or curve.device != dev or not curve.is_contiguous()):
+        raise ValueError("curve must be float64 [A] on the blocks' GPU")
+    with_se = B >= 2 if with_se is None else with_se
+    if image is None:
+        image = torch.empty((A, n_bins), dtype=torch.float64, device=dev)
+    if image_se is None and with_se:
+        image_se = torch.empty((A, n_bins), dtype=torch.float64, device=dev)
+    for t in (image, image_se):
+        if t is not None and (t.numel() != A * n_bins or t.dtype != torch.float64 or t.device != dev or not t.is_contiguous()):
+            raise ValueError("image and image_se must be contiguous float64 [A, n_bins] on the blocks' GPU")
+    out = dict(image=image, image_se=image_se, row_sum=torch.empty((B, A), dtype=torch.float64, device=dev),
+               peak=torch.empty(A, dtype=torch.float64, device=dev), peak_bin=torch.empty(A, dtype=torch.int32, device=dev),
+               lit=torch.empty(A, dtype=torch.int32, device=dev), bad=torch.zeros(1, dtype=torch.int64, device=dev))
+    spec = array_image_spec(S, n_bins, first, last, weights, gamma_log2, rho, curve.data_ptr() if curve is not None else None,
+                            window_length)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.r3d_array_image(dev.index or 0, B, batch_energy.data_ptr(), C.byref(spec), image.data_ptr(),
+                             image_se.data_ptr() if image_se is not None else None, out["row_sum"].data_ptr(),
+                             out["peak"].data_ptr(), out["peak_bin"].data_ptr(), out["lit"].data_ptr(), out["bad"].data_ptr(),
+                             stream)
+    if rc:
+        raise RuntimeError("r3d_array_image failed: " + lib.r3d_last_error().decode())
+    return out
+
+
+def array_powerlaw(y, r_first, r_last, ibegin, iend):
+    """r3d_array_powerlaw / r3d_array_powerlaw_jackknife (include/r3d.h; no GPU needed): the power law Y = c X^q over the
+    1-based inclusive points ibegin .. iend of an array whose X runs evenly from r_first to r_last.  y [A]: returns
+    (ln c, q).  y [B, A] batch values: returns (ln c, q, se(ln c), se(q), total [A]) of the batches' totals."""
+    lib = _ffi.hip_lib()
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    fit, se = (C.c_double * 2)(), (C.c_double * 2)()
+    if y.ndim == 1:
+        if lib.r3d_array_powerlaw(y.size, float(r_first), float(r_last), y.ctypes.data_as(_ffi._dp), 1, int(ibegin), int(iend), fit):
+            raise RuntimeError("r3d_array_powerlaw failed: " + lib.r3d_last_error().decode())
+        return fit[0], fit[1]
+    B, A = y.shape
+    total = np.zeros(A)
+    if lib.r3d_array_powerlaw_jackknife(A, float(r_first), float(r_last), B, y.ctypes.data_as(_ffi._dp), A, int(ibegin),
+                                        int(iend), fit, se, total.ctypes.data_as(_ffi._dp)):
+        raise RuntimeError("r3d_array_powerlaw_jackknife failed: " + lib.r3d_last_error().decode())
+    return fit[0], fit[1], se[0], se[1], total
 
 
 def _check_blocks(blocks, lead, what):
@@ -871,6 +1017,41 @@ class Engine:
             raise RuntimeError("r3d_run_batched_windows failed: " + self._lib.r3d_last_error().decode())
         res._from_c(c)
         return (res, ese, cse, we, wc, wse) + ((bwe,) if keep_batch_windows else ())
+
+    def run_batched_array_image(self, n, n_batches, first, last, weights, gamma_log2=1, rho=0.3, fit=(0, 0),
+                                ranges=(0.0, 0.0), curve=(math.nan, math.nan), first_id=0, seed=0x5EED, keep_row_sums=False):
+        """run_batched that also makes the travel-time image of the receivers first .. last where the batch blocks lie
+        (include/r3d.h r3d_run_batched_array_image): weights the five component weights, gamma = 2^gamma_log2, rho the
+        norm ratio; fit the 1-based (IBEGIN, IEND) of the power-law fit with `ranges` the distances of the two end
+        receivers (Model.ttimage_plan), curve a (c, q) given outright.  Returns (Result, energy_se, counts_se, image): a
+        dict of image, image_se [A, n_bins], lit, peak_bin [A] (uint32), summed, summed_se, peak [A] -- summed is the raw
+        sum of bins --, with keep_row_sums batch_row_sum [B, A], and with a fit: fit (c, q), fit_se (se(ln c), se(q)),
+        curve_made, curve [A], image_curve, image_curve_se [A, n_bins]."""
+        m = self.model
+        res = m.new_result()
+        shape = (m.n_seismometers, m.n_bins)
+        A = int(last) - int(first) + 1
+        if A < 1:
+            raise ValueError("the array needs first <= last")
+        spec = array_image_spec(m.n_seismometers, m.n_bins, first, last, weights, gamma_log2, rho, None,
+                                m.n_bins * m.desc.params.time_per_bin, fit, ranges, curve)
+        ese, cse = np.zeros(shape + (_ffi.R3D_N_ENERGY,)), np.zeros(shape + (_ffi.R3D_N_COUNT,))
+        img = dict(image=np.zeros((A, m.n_bins)), image_se=np.zeros((A, m.n_bins)), summed=np.zeros(A), summed_se=np.zeros(A),
+                   peak=np.zeros(A), peak_bin=np.zeros(A, dtype=np.uint32), lit=np.zeros(A, dtype=np.uint32))
+        if keep_row_sums:
+            img["batch_row_sum"] = np.zeros((max(int(n_batches), 0), A))
+        has_fit = bool(fit[0] or fit[1])
+        if has_fit:
+            img.update(curve=np.zeros(A), image_curve=np.zeros((A, m.n_bins)), image_curve_se=np.zeros((A, m.n_bins)))
+        out = _ffi.ArrayImageResult(size=C.sizeof(_ffi.ArrayImageResult), **{k: v.ctypes.data for k, v in img.items()})
+        c = res._as_c()
+        if self._lib.r3d_run_batched_array_image(self._e, n, first_id, seed, n_batches, C.byref(c), ese.ctypes.data_as(_ffi._dp),
+                                                 cse.ctypes.data_as(_ffi._dp), C.byref(spec), C.byref(out)):
+            raise RuntimeError("r3d_run_batched_array_image failed: " + self._lib.r3d_last_error().decode())
+        res._from_c(c)
+        if has_fit:
+            img.update(fit=tuple(out.fit), fit_se=tuple(out.fit_se), curve_made=bool(out.curve_made))
+        return res, ese, cse, img
 
     def run_device(self, n, first_id, seed, d_energy, d_counts, d_scalars, stream=None, carry=None):
         """Asynchronous, device-resident accumulate (pointers are raw device

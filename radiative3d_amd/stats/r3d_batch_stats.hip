@@ -29,7 +29,6 @@ namespace r3d {
 namespace {
 
 constexpr int kMomentsBlock = 256;
-constexpr uint32_t kMaxBatches = 64;   // launches of one engine in flight (include/r3d.h r3d_run_device)
 constexpr int kStreams = 4;            // hardware queues a process gets by default
 
 // One work-item per entry, grid-stride.  The blocks are batch-major, so for every j the lanes of a wave read 64
@@ -282,17 +281,6 @@ hipError_t lanes_for(int device, Lanes** out) {
   return hipSuccess;
 }
 
-// The device a pointer of the caller's lives on (-1: not device memory).
-int device_of(const void* p) {
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return -1;
-  }
-  if (attr.type != hipMemoryTypeDevice) return -1;
-  return attr.device;
-}
-
 int enqueue_moments(uint32_t n_batches, const double* d_batch_energy, uint64_t n_energy, const uint64_t* d_batch_counts,
                     uint64_t n_counts, const uint64_t* d_batch_scalars, uint64_t n_scalars, double* d_energy,
                     uint64_t* d_counts, uint64_t* d_scalars, double* d_energy_se, double* d_counts_se, hipStream_t s) {
@@ -345,27 +333,6 @@ int enqueue_merge(uint32_t n_shards, uint32_t n_batches, uint64_t shard_stride_e
   return err == hipSuccess ? 0 : refuse("r3d_batch_merge", err);
 }
 
-// What a batched run cannot be combined with, asked of the engine through its public calls.
-int refuse_engine_state(r3d_engine* e, const char* who) {
-  if (r3d_engine_carry_pending(e))
-    return refuse(who, "histories carried over by r3d_run_device_carry await their flush; a batch must be a self-contained launch");
-  if (r3d_event_log_read(e, nullptr, 0, 0) != ~uint64_t(0))
-    return refuse(who, "an event log is attached (its launches run the diagnostic kernel, one at a time); detach it first");
-  if (r3d_production_finals_read(e, nullptr, 0, 0) == 0)
-    return refuse(who, "a production-finals buffer is attached; detach it first");
-  return 0;
-}
-
-int check_batches(const char* who, uint64_t n, uint32_t n_batches) {
-  if (n_batches < 2)
-    return refuse(who, "at least 2 batches are needed for a variance (got " + std::to_string(n_batches) + ")");
-  if (n_batches > kMaxBatches)
-    return refuse(who, "at most 64 batches (the engine's launches in flight), got " + std::to_string(n_batches));
-  if (n < n_batches)
-    return refuse(who, "fewer histories (" + std::to_string(n) + ") than batches (" + std::to_string(n_batches) + ")");
-  return 0;
-}
-
 // Batches [j0, j0 + B) of a job of N batches over the ids [first_id, first_id + n), batch j0 + k into block k of `be`,
 // `bc`, `bs` (zeroed on `s` by the caller): ordered behind what `s` holds now, round-robin over the device's lanes so
 // that a batch's drain phase overlaps the batches behind it, and joined back into `s` -- also when a launch was
@@ -389,24 +356,6 @@ int enqueue_batches(const char* who, r3d_engine* e, Lanes* lanes, uint64_t n, ui
     if (j != hipSuccess && rc == 0) rc = refuse(who, j);
   }
   return rc;
-}
-
-// The engine's device, learned from an address it owns: the only one the interface hands out is its event grid's,
-// so an engine without a grid gets one of a single cell for the length of the question.  -1 with the message set.
-int engine_device(r3d_engine* e, const char* who) {
-  int device = -1;
-  if (r3d_volume_len(e)) {
-    device = device_of(r3d_volume_device_ptr(e));
-  } else {
-    r3d_volume_desc one{};
-    one.cell_size[0] = one.cell_size[1] = one.cell_size[2] = 1.0, one.dims[0] = one.dims[1] = one.dims[2] = 1;
-    one.n_frames = 1, one.frame_dt = 1.0;
-    if (r3d_engine_set_volume(e, &one)) return -1;
-    device = device_of(r3d_volume_device_ptr(e));
-    if (r3d_engine_set_volume(e, nullptr)) return -1;
-  }
-  if (device < 0) refuse(who, "the engine's device could not be determined");
-  return device;
 }
 
 // r3d_run_batched, and with a window spec (bins on the HOST, checked by the caller) r3d_run_batched_windows: the batches

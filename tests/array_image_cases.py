@@ -1,0 +1,206 @@
+"""Shared by tests/test_array_image.py (CPU) and tests/test_array_image_gpu.py: the host build of the array-image header
+(radiative3d_amd/arrays/r3d_array_image.h, compiled here by g++), the references it is held to -- vis/seisplot/arraymatrix.m,
+arrayimage.m:42-83 and normcurve_fitpowerlaw.m restated in numpy long double, row sums in exact rationals, the header's
+rounding bounds -- and the shapes the kernel is run on."""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+from fractions import Fraction
+
+import numpy as np
+
+from radiative3d_amd import _ffi
+
+U = 2.0 ** -53
+LD = np.longdouble
+LD_U = float(np.finfo(LD).eps) / 2            # the reference's own unit roundoff (2^-64 where long double is x87's)
+GEOMETRIES = (1, 2, 4, 8, 16, 32, 64)
+LEGACY, CURVE = 0, 1
+
+WRAPPER = r'''
+#include "r3d_array_image.h"
+using namespace r3d;
+extern "C" int array_image_host(int G, const double* x, uint32_t B, uint32_t S, uint32_t n_bins, uint32_t first, uint32_t last,
+                                const double* w, uint32_t k, int mode, double rho, const double* curve, double window_length,
+                                double* image, double* image_se, double* row_sum, double* peak, uint32_t* peak_bin,
+                                uint32_t* lit, uint64_t* bad) {
+  ArrayImageProblem a;
+  a.x = x, a.n_batches = B, a.n_seismometers = S, a.n_bins = n_bins, a.first = first, a.last = last;
+  for (int c = 0; c < 5; c++) a.weight[c] = w[c];
+  a.gamma_log2 = k, a.mode = mode, a.rho = rho, a.curve = curve, a.window_length = window_length;
+  switch (G) {
+    case 1: array_image<1>(a, image, image_se, row_sum, peak, peak_bin, lit, bad); break;
+    case 2: array_image<2>(a, image, image_se, row_sum, peak, peak_bin, lit, bad); break;
+    case 4: array_image<4>(a, image, image_se, row_sum, peak, peak_bin, lit, bad); break;
+    case 8: array_image<8>(a, image, image_se, row_sum, peak, peak_bin, lit, bad); break;
+    case 16: array_image<16>(a, image, image_se, row_sum, peak, peak_bin, lit, bad); break;
+    case 32: array_image<32>(a, image, image_se, row_sum, peak, peak_bin, lit, bad); break;
+    case 64: array_image<64>(a, image, image_se, row_sum, peak, peak_bin, lit, bad); break;
+    default: return 1;
+  }
+  return 0;
+}
+extern "C" int powerlaw_host(uint32_t A, double r0, double r1, const double* y, uint64_t stride, uint32_t ibegin, uint32_t iend,
+                             double* fit) {
+  return array_powerlaw(A, r0, r1, y, stride, ibegin, iend, fit);
+}
+extern "C" int powerlaw_jackknife_host(uint32_t A, double r0, double r1, uint32_t B, const double* y, uint64_t batch_stride,
+                                       uint32_t ibegin, uint32_t iend, double* fit, double* se, double* total) {
+  return array_powerlaw_jackknife(A, r0, r1, B, y, batch_stride, ibegin, iend, fit, se, total);
+}
+'''
+
+_host = None
+_keep = None
+
+
+def host_arrays():
+    """The header's functions as the host compiler builds them (no contraction of a multiply into an add)."""
+    global _host, _keep
+    if _host is None:
+        _keep = tempfile.TemporaryDirectory(prefix="array_image_")
+        src, so = os.path.join(_keep.name, "wrap.cpp"), os.path.join(_keep.name, "libarrays.so")
+        open(src, "w").write(WRAPPER)
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-I",
+                               os.path.join(_ffi.REPO, "radiative3d_amd", "arrays"), "-o", so, src])
+        L = C.CDLL(so)
+        L.array_image_host.argtypes = [C.c_int, C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_uint32, C.c_int, C.c_double,
+                                                                                  C.c_void_p, C.c_double] + [C.c_void_p] * 7
+        L.array_image_host.restype = C.c_int
+        L.powerlaw_host.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.powerlaw_host.restype = C.c_int
+        L.powerlaw_jackknife_host.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32,
+                                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.powerlaw_jackknife_host.restype = C.c_int
+        _host = L
+    return _host
+
+
+def host_array_image(x, first, last, weights, k, mode=LEGACY, rho=0.3, curve=None, window_length=0.0, G=1):
+    """dict(image, image_se (B >= 2), row_sum, peak, peak_bin, lit, bad) of blocks x [B, S, n_bins, 5] by the host build."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    B, S, n_bins = x.shape[:3]
+    A = last - first + 1
+    w = np.array(weights, dtype=np.float64)
+    c = np.ascontiguousarray(curve, dtype=np.float64) if curve is not None else None
+    out = dict(image=np.full((A, n_bins), np.nan), image_se=np.full((A, n_bins), np.nan) if B >= 2 else None,
+               row_sum=np.full((B, A), np.nan), peak=np.full(A, np.nan), peak_bin=np.full(A, 7, dtype=np.uint32),
+               lit=np.full(A, 7, dtype=np.uint32))
+    bad = np.zeros(1, dtype=np.uint64)
+    rc = host_arrays().array_image_host(G, x.ctypes.data, B, S, n_bins, first, last, w.ctypes.data, k, mode, rho,
+                                        c.ctypes.data if c is not None else None, window_length, out["image"].ctypes.data,
+                                        out["image_se"].ctypes.data if B >= 2 else None, out["row_sum"].ctypes.data,
+                                        out["peak"].ctypes.data, out["peak_bin"].ctypes.data, out["lit"].ctypes.data,
+                                        bad.ctypes.data)
+    assert rc == 0
+    out["bad"] = int(bad[0])
+    return out
+
+
+def host_powerlaw(y, r0, r1, ibegin, iend):
+    """(rc, ln c, q) of y [A], or (rc, ln c, q, se(ln c), se(q), total [A]) of batch values y [B, A], by the host build."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    fit, se = np.full(2, -7.0), np.full(2, -7.0)
+    if y.ndim == 1:
+        rc = host_arrays().powerlaw_host(y.size, r0, r1, y.ctypes.data, 1, ibegin, iend, fit.ctypes.data)
+        return rc, fit[0], fit[1]
+    B, A = y.shape
+    total = np.full(A, -7.0)
+    rc = host_arrays().powerlaw_jackknife_host(A, r0, r1, B, y.ctypes.data, A, ibegin, iend, fit.ctypes.data, se.ctypes.data,
+                                               total.ctypes.data)
+    return rc, fit[0], fit[1], se[0], se[1], total
+
+
+# ---- the reference's scripts in long double ---------------------------------------------------------------------------------
+def _image_ld(BB, gamma, mode, rho, norm_curve):
+    """arrayimage.m:54-83 on the matrix BB [A, n_bins] (long double): NORMCURVE normalisation, or gamma scaling and the
+    legacy split between area and peak; a row Octave would fill with NaN (0 / 0) is zero here."""
+    if mode == CURVE:
+        with np.errstate(all="ignore"):
+            out = (BB / norm_curve[:, None]) ** (LD(1) / gamma)
+        return np.where((norm_curve > 0)[:, None] & np.isfinite(norm_curve)[:, None], out, LD(0))
+    BB = BB ** (LD(1) / gamma)
+    area, peak = BB.sum(axis=1, keepdims=True), BB.max(axis=1, keepdims=True)
+    alive = peak > 0
+    safe_area, safe_peak = np.where(alive, area, LD(1)), np.where(alive, peak, LD(1))
+    return np.where(alive, (1 - LD(rho)) * (BB / safe_area) + LD(rho) * (BB / safe_peak), LD(0))
+
+
+def restated_image(x, first, last, weights, k, mode=LEGACY, rho=0.3, curve=None, window_length=0.0):
+    """(image, se, peak, max_j img_(j)) in numpy long double: arraymatrix.m's MegaTrace of the batches' total (the weights
+    in place of AXES), arrayimage.m's pixel, and the delete-one-batch jackknife of it by its textbook formula."""
+    x = np.asarray(x, dtype=LD)[:, first:last + 1]
+    B = x.shape[0]
+    e = (x * np.asarray(weights, dtype=LD)).sum(axis=-1)                      # [B, A, n_bins]
+    gamma = LD(2 ** k)
+    norm_curve = np.asarray(curve, dtype=LD) / LD(window_length) if mode == CURVE else None
+    total = e.sum(axis=0)
+    image = _image_ld(total, gamma, mode, rho, norm_curve)
+    if B < 2:
+        return image, None, total.max(axis=1), None
+    loo = np.stack([_image_ld(np.delete(e, j, axis=0).sum(axis=0) * LD(B) / LD(B - 1), gamma, mode, rho, norm_curve)
+                    for j in range(B)])
+    se = np.sqrt(LD(B - 1) / LD(B) * ((loo - loo.mean(axis=0)) ** 2).sum(axis=0))
+    return image, se, total.max(axis=1), loo.max(axis=0)
+
+
+def pixel_eps(B, n_bins, k, mode):
+    """The header's relative pixel bound eps = d u / (1 - 2 d u), and d."""
+    d = B + 9 + k if mode == CURVE else 2 * (B + 7 + k) + -(-n_bins // 64) + 10
+    return d * U / (1 - 2 * d * U), d
+
+
+def restated_powerlaw(Y, r0, r1, ibegin, iend):
+    """normcurve_fitpowerlaw.m:44-51 in long double: X = linspace, polyfit(log X, log Y, 1) over ibegin:iend (1-based,
+    inclusive) through numpy's least squares.  (ln c, q)."""
+    Y = np.asarray(Y, dtype=LD)
+    A = len(Y)
+    X = LD(r0) + np.arange(A, dtype=LD) * ((LD(r1) - LD(r0)) / LD(A - 1))
+    lx, ly = np.log(X[ibegin - 1:iend]), np.log(Y[ibegin - 1:iend])
+    # polyfit's normal equations, solved in long double (numpy.linalg has no long double)
+    n = LD(len(lx))
+    sx, sy, sxx, sxy = lx.sum(), ly.sum(), (lx * lx).sum(), (lx * ly).sum()
+    q = (n * sxy - sx * sy) / (n * sxx - sx * sx)
+    return (sy - q * sx) / n, q
+
+
+def restated_powerlaw_jackknife(y, r0, r1, ibegin, iend):
+    """(ln c, q, se(ln c), se(q)) of the batches' totals, long double."""
+    y = np.asarray(y, dtype=LD)
+    B = y.shape[0]
+    full = restated_powerlaw(y.sum(axis=0), r0, r1, ibegin, iend)
+    loo = np.array([restated_powerlaw(np.delete(y, j, axis=0).sum(axis=0) * LD(B) / LD(B - 1), r0, r1, ibegin, iend)
+                    for j in range(B)], dtype=LD)
+    se = np.sqrt(LD(B - 1) / LD(B) * ((loo - loo.mean(axis=0)) ** 2).sum(axis=0))
+    return full[0], full[1], se[0], se[1]
+
+
+# ---- exact rational row sums ---------------------------------------------------------------------------------------------
+def exact_row_sum(block, weights):
+    """sum_b sum_c w_c x_bc of block [n_bins, 5], exactly (every term is non-negative here)."""
+    w = [Fraction(float(v)) for v in weights]
+    return sum((w[c] * Fraction(float(block[b, c])) for b in range(block.shape[0]) for c in range(5)), Fraction(0))
+
+
+# ---- the kernel's shapes ----------------------------------------------------------------------------------------------------
+S_ALL, FIRST = 5, 1
+WEIGHTS = ((1, 1, 1, 0, 0), (0, 0, 1, 0, 0), (0.5, 0.25, 2, 1, 3))
+N_BINS = (1, 63, 64, 65, 130)          # below, at and above the 64 strands, and more than two tiles
+BATCHES = (1, 2, 3, 64)
+
+
+def array_blocks(B, n_bins, rng):
+    """Lognormal energy blocks [B, S_ALL, n_bins, 5] with, from FIRST on: a row with a tied peak (two bins, where there are
+    two, hold the same large values in every batch), a row dominated by ONE batch (x 1e12) and a row of zeros."""
+    x = rng.lognormal(0.0, 3.0, (B, S_ALL, n_bins, 5))
+    top = rng.lognormal(20.0, 0.5, (B, 5))
+    x[:, FIRST, n_bins // 3] = top
+    x[:, FIRST, (2 * n_bins) // 3] = top
+    x[B // 2, FIRST + 1] *= 1e12
+    x[:, FIRST + 2] = 0.0
+    return x
+
+
+def curve_values(A, rng):
+    return rng.lognormal(2.0, 1.0, A)
