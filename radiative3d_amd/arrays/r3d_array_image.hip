@@ -297,27 +297,16 @@ int r3d_run_batched_array_image(r3d_engine* e, uint64_t n, uint64_t first_id, ui
           return refuse(who, "the given curve's value at receiver " + std::to_string(s) + " of the array is not finite and > 0");
       }
   }
-  if (check_batches(who, n, n_batches)) return 1;
-  if (refuse_engine_state(e, who)) return 1;
-  const int device = engine_device(e, who);
-  if (device < 0) return 1;
-  OnDevice on(device);
-  if (on.status != hipSuccess) return refuse(who, on.status);
-
-  const size_t ne = r3d_energy_len(e), nc = r3d_counts_len(e), ns = R3D_N_SCALARS, B = n_batches;
-  const size_t px = (size_t)A * nb;
-  // one block: what r3d_run_batched reads (totals of energy, counts, scalars, the two se arrays), then the image's arrays
-  // the host reads (two images with their se, the batches' row sums, four [A] arrays of doubles, two of u32), then the
-  // batches' energy blocks, which it does not
-  const size_t words = 2 * ne + 2 * nc + ns, img_words = 4 * px + B * A + 4 * A + A;
-  DeviceBuffer block;
-  if (hipError_t err = block.alloc((words + img_words + B * ne) * 8); err != hipSuccess) return refuse(who, err);
-  double* const d_e = block.as<double>();
-  uint64_t* const d_c = reinterpret_cast<uint64_t*>(d_e + ne);
-  uint64_t* const d_s = d_c + nc;
-  double* const d_ese = reinterpret_cast<double*>(d_s + ns);
-  double* const d_cse = d_ese + ne;
-  double* const d_img = d_cse + nc;
+  const size_t ne = r3d_energy_len(e), B = n_batches, px = (size_t)A * nb;
+  // behind the result block the image's arrays the host reads (two images with their se, the batches' row sums, four [A]
+  // arrays of doubles, two of u32), all zeroed, then the batches' energy blocks, which it does not
+  const size_t img_words = 4 * px + B * A + 5 * A;
+  ExtraWords extra;
+  extra.read = img_words, extra.unread = B * ne, extra.zeroed = img_words;
+  BatchedRun run(who, e, n, n_batches, extra);
+  if (run.status()) return run.status();
+  hipStream_t const s = run.stream();
+  double* const d_img = reinterpret_cast<double*>(run.extra());
   double* const d_img_se = d_img + px;
   double* const d_cimg = d_img_se + px;
   double* const d_cimg_se = d_cimg + px;
@@ -329,25 +318,20 @@ int r3d_run_batched_array_image(r3d_engine* e, uint64_t n, uint64_t first_id, ui
   uint32_t* const d_peak_bin = reinterpret_cast<uint32_t*>(d_curve + A);
   uint32_t* const d_lit = d_peak_bin + A;
   double* const d_be = reinterpret_cast<double*>(d_peak_bin + 2 * A);
-  std::vector<uint64_t> host(words + img_words);
   double fitted[2] = {std::nan(""), std::nan("")}, fitted_se[2] = {std::nan(""), std::nan("")};
   bool curve_made = false;
 
-  hipStream_t s = nullptr;
-  hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-  if (err == hipSuccess) err = hipMemsetAsync(block.p, 0, (words + img_words) * 8, s);
-  int rc = err == hipSuccess ? 0 : refuse(who, err);
-  if (rc == 0) rc = r3d_run_device_batched(e, n, first_id, seed, n_batches, d_e, d_c, d_s, d_ese, d_cse, d_be, nullptr, s);
+  int rc = run.run(first_id, seed, d_be);
   if (rc == 0)
     rc = enqueue_array_image(n_batches, d_be, spec, kArrayLegacy, nullptr, d_img, d_img_se, d_rows, d_peak, d_peak_bin, d_lit,
                              nullptr, s);
   if (rc == 0)
-    rc = r3d_batch_moments(device, n_batches, d_rows, A, nullptr, 0, nullptr, 0, d_summed, nullptr, nullptr, d_summed_se,
+    rc = r3d_batch_moments(run.device(), n_batches, d_rows, A, nullptr, 0, nullptr, 0, d_summed, nullptr, nullptr, d_summed_se,
                            nullptr, s);
   if (rc == 0 && fit) {
     // the fit on the host, from the [B][A] row sums times dt (Sum(E dt): NS.SummedEnergy); the curve goes back up
     std::vector<double> rows(B * A);
-    err = hipMemcpyAsync(rows.data(), d_rows, B * A * 8, hipMemcpyDeviceToHost, s);
+    hipError_t err = hipMemcpyAsync(rows.data(), d_rows, B * A * 8, hipMemcpyDeviceToHost, s);
     if (err == hipSuccess) err = hipStreamSynchronize(s);
     if (err != hipSuccess) rc = refuse(who, err);
     if (rc == 0) {
@@ -372,27 +356,8 @@ int r3d_run_batched_array_image(r3d_engine* e, uint64_t n, uint64_t first_id, ui
       }
     }
   }
-  if (s) {   // (also after a refusal: what was enqueued reads the block)
-    err = hipStreamSynchronize(s);
-    if (err == hipSuccess && rc == 0) err = hipMemcpy(host.data(), block.p, host.size() * 8, hipMemcpyDeviceToHost);
-    if (err != hipSuccess && rc == 0) rc = refuse(who, err);
-    (void)hipStreamDestroy(s);
-  }
-  if (rc) return rc;
-  const double* const he = reinterpret_cast<const double*>(host.data());
-  const uint64_t* const hc = host.data() + ne;
-  const uint64_t* const hs = hc + nc;
-  const double* const hese = reinterpret_cast<const double*>(hs + ns);
-  for (size_t i = 0; i < ne; i++) out->energy[i] += he[i];
-  for (size_t i = 0; i < nc; i++) out->counts[i] += hc[i];
-  out->n_lost += hs[0], out->n_timeout += hs[1], out->n_invalid += hs[2];
-  for (int r = 0; r < R3D_INV_NUM; r++) out->invalid_reasons[r] += hs[3 + r];
-  for (int k = 0; k < R3D_EV_NUM; k++) out->events[k] += hs[3 + R3D_INV_NUM + k];
-  if (energy_se)
-    for (size_t i = 0; i < ne; i++) energy_se[i] = hese[i];
-  if (counts_se)
-    for (size_t i = 0; i < nc; i++) counts_se[i] = hese[ne + i];
-  const double* const himg = hese + ne + nc;
+  if ((rc = run.close(rc, out, energy_se, counts_se))) return rc;
+  const double* const himg = reinterpret_cast<const double*>(run.host_extra());
   const double* const hrows = himg + 4 * px;
   const double* const hsum = hrows + B * A;
   const uint32_t* const hbin = reinterpret_cast<const uint32_t*>(hsum + 4 * A);

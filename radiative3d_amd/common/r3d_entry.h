@@ -1,13 +1,16 @@
 // r3d_entry.h -- what an entry point of the C-ABI that lives OUTSIDE the engine needs around its launch: the engine's
 // error text, the caller's device kept across the call, device scratch that frees itself, the refusals the calls on
-// the event grid share, and those of the batched runs with the way they learn their engine's device.  Host code only,
-// all inline.  An add-on (stats/, views/, maps/, arrays/) includes this and include/r3d.h and nothing from csrc/;
+// the event grid share, and those of the batched runs with the way they learn their engine's device, the format of
+// the block their results come down in (ResultBlock) and the way a run is brought to the host (BatchedRun).  Host code
+// only, all inline.  An add-on (stats/, views/, maps/, arrays/) includes this and include/r3d.h and nothing from csrc/;
 // csrc/r3d_volume.hip, whose entry points are of the same kind, uses it too.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <optional>
 #include <string>
+#include <vector>
 
 #include "../../include/r3d.h"
 
@@ -127,5 +130,114 @@ inline int engine_device(r3d_engine* e, const char* who) {
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// The block a batched run's totals and errors come down in, 8-byte words: energy [ne], counts [nc], scalars
+// [R3D_N_SCALARS], energy_se [ne], counts_se [nc] -- the order r3d_run_device_batched's five outputs are handed out in;
+// the scalars are n_lost, n_timeout, n_invalid, invalid_reasons[], events[].  Outside csrc/ only this knows the order.
+struct ResultBlock {
+  size_t ne, nc;
+  ResultBlock(size_t n_energy, size_t n_counts) : ne(n_energy), nc(n_counts) {}
+  size_t words() const { return 2 * ne + 2 * nc + R3D_N_SCALARS; }
+  double* energy(void* base) const { return static_cast<double*>(base); }
+  uint64_t* counts(void* base) const { return static_cast<uint64_t*>(base) + ne; }
+  uint64_t* scalars(void* base) const { return counts(base) + nc; }
+  double* energy_se(void* base) const { return reinterpret_cast<double*>(scalars(base) + R3D_N_SCALARS); }
+  double* counts_se(void* base) const { return energy_se(base) + ne; }
+  // A host copy of the block ADDED into *out, the two se arrays written (either may be null).
+  void add_into(const uint64_t* host, r3d_result* out, double* out_energy_se, double* out_counts_se) const {
+    void* const base = const_cast<uint64_t*>(host);   // (only read)
+    const double* const he = energy(base);
+    const uint64_t* const hc = counts(base);
+    const uint64_t* const hs = scalars(base);
+    const double* const hese = energy_se(base);
+    const double* const hcse = counts_se(base);
+    for (size_t i = 0; i < ne; i++) out->energy[i] += he[i];
+    for (size_t i = 0; i < nc; i++) out->counts[i] += hc[i];
+    out->n_lost += hs[0], out->n_timeout += hs[1], out->n_invalid += hs[2];
+    for (int r = 0; r < R3D_INV_NUM; r++) out->invalid_reasons[r] += hs[3 + r];
+    for (int k = 0; k < R3D_EV_NUM; k++) out->events[k] += hs[3 + R3D_INV_NUM + k];
+    if (out_energy_se)
+      for (size_t i = 0; i < ne; i++) out_energy_se[i] = hese[i];
+    if (out_counts_se)
+      for (size_t i = 0; i < nc; i++) out_counts_se[i] = hcse[i];
+  }
+};
+
+// The words a batched run keeps behind its result block: `read` the host reads back, then `unread` it does not; the
+// first `zeroed` of those read back are cleared with the result block.
+struct ExtraWords {
+  size_t read = 0, unread = 0, zeroed = 0;
+};
+
+// A batched run brought to the host, as a scope: opened, it has refused what every batched run refuses (status() non-zero,
+// the message set), made the engine's device current and holds ONE allocation -- the result block and its
+// `ExtraWords` behind it -- and a stream of its own on which the block and the first `zeroed` words behind it are being
+// cleared.  The caller enqueues on stream(): run(), then kernels of its own into extra().  close() waits for the
+// stream, reads back and adds into *out.  On every way out the stream has run out before the allocation is freed,
+// that before the caller's device is restored, and nothing is added to *out unless the whole call succeeded.
+// (The engine's two lengths are read when the scope opens, ahead of the refusals: plain reads, nothing can fail there.)
+class BatchedRun {
+ public:
+  const ResultBlock result;
+
+  BatchedRun(const char* who_, r3d_engine* e_, uint64_t n_, uint32_t n_batches_, const ExtraWords& extra = ExtraWords())
+      : result(r3d_energy_len(e_), r3d_counts_len(e_)), who(who_), e(e_), n(n_), n_batches(n_batches_) {
+    rc = open(extra);
+  }
+  ~BatchedRun() {   // (a way out that did not pass close(): what was enqueued reads the block)
+    if (!s) return;
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+  }
+
+  int status() const { return rc; }   // of opening; non-zero: return it, nothing else is to be done
+  int device() const { return dev; }
+  hipStream_t stream() const { return s; }
+  uint64_t* extra() const { return block.as<uint64_t>() + result.words(); }   // the device address behind the result block
+  const uint64_t* host_extra() const { return host.data() + result.words(); }   // after close(): its `read` words
+  // r3d_run_device_batched into the result block; the batches' blocks are kept where the pointers say (null: not kept)
+  int run(uint64_t first_id, uint64_t seed, double* d_batch_energy = nullptr, uint64_t* d_batch_counts = nullptr) {
+    return r3d_run_device_batched(e, n, first_id, seed, n_batches, result.energy(block.p), result.counts(block.p),
+                                  result.scalars(block.p), result.energy_se(block.p), result.counts_se(block.p),
+                                  d_batch_energy, d_batch_counts, s);
+  }
+  // `status`: how the call went since it was opened; returns the call's status
+  int close(int status, r3d_result* out, double* energy_se, double* counts_se) {
+    if (status == 0) status = rc;
+    if (s) {   // (also after a refusal: what was enqueued reads the block)
+      hipError_t err = hipStreamSynchronize(s);
+      if (err == hipSuccess && status == 0) err = hipMemcpy(host.data(), block.p, host.size() * 8, hipMemcpyDeviceToHost);
+      if (err != hipSuccess && status == 0) status = refuse(who, err);
+      (void)hipStreamDestroy(s);
+      s = nullptr;
+    }
+    if (status == 0) result.add_into(host.data(), out, energy_se, counts_se);
+    return status;
+  }
+  BatchedRun(const BatchedRun&) = delete;
+  BatchedRun& operator=(const BatchedRun&) = delete;
+
+ private:
+  int open(const ExtraWords& x) {
+    if (check_batches(who, n, n_batches) || refuse_engine_state(e, who)) return 1;
+    if ((dev = engine_device(e, who)) < 0) return 1;
+    on.emplace(dev);
+    if (on->status != hipSuccess) return refuse(who, on->status);
+    if (hipError_t err = block.alloc((result.words() + x.read + x.unread) * 8); err != hipSuccess) return refuse(who, err);
+    host.resize(result.words() + x.read);
+    hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (err == hipSuccess) err = hipMemsetAsync(block.p, 0, (result.words() + x.zeroed) * 8, s);
+    return err == hipSuccess ? 0 : refuse(who, err);
+  }
+  const char* const who;
+  r3d_engine* const e;
+  const uint64_t n;
+  const uint32_t n_batches;
+  int dev = -1, rc = 1;
+  std::optional<OnDevice> on;   // (in this order: the stream goes first, then the allocation, then the device comes back)
+  DeviceBuffer block;
+  std::vector<uint64_t> host;
+  hipStream_t s = nullptr;
+};
 
 }  // namespace r3d

@@ -686,6 +686,21 @@ def run_model(model, n, first_id=0, seed=0x5EED, n_gpus=1, devices=None):
     return res
 
 
+def _run_batched_to_host(lib, name, handle, model, n, first_id, seed, n_batches, result, *tail):
+    """What the calls that bring a batched run to the host share: `name` of `lib` on `handle` with the totals ADDED
+    into `result` (a new one when None) and the two standard-error arrays written, `tail` the call's own arguments
+    behind those.  Returns (Result, energy_se, counts_se)."""
+    res = result if result is not None else model.new_result()
+    shape = (model.n_seismometers, model.n_bins)
+    ese, cse = np.zeros(shape + (_ffi.R3D_N_ENERGY,)), np.zeros(shape + (_ffi.R3D_N_COUNT,))
+    c = res._as_c()
+    if getattr(lib, name)(handle, n, first_id, seed, n_batches, C.byref(c), ese.ctypes.data_as(_ffi._dp),
+                          cse.ctypes.data_as(_ffi._dp), *tail):
+        raise RuntimeError(name + " failed: " + lib.r3d_last_error().decode())
+    res._from_c(c)
+    return res, ese, cse
+
+
 class Node:
     """r3d_node_*: one engine per entry of `devices`, kept across runs; a run shards the id range over them
     and sums the shards' blocks on the devices (RCCL ncclReduce to devices[0]; on the host for a node of one
@@ -725,16 +740,8 @@ class Node:
         them on every shard; the shards' moments are merged on the GPU.  Returns (Result, energy_se, counts_se) as
         Engine.run_batched does -- the job's totals (ADDED into `result` when one is given) and the standard error of
         every energy and count entry from the spread of all n_batches batches."""
-        res = result if result is not None else self.model.new_result()
-        shape = (self.model.n_seismometers, self.model.n_bins)
-        ese = np.zeros(shape + (_ffi.R3D_N_ENERGY,))
-        cse = np.zeros(shape + (_ffi.R3D_N_COUNT,))
-        c = res._as_c()
-        if self._lib.r3d_node_run_batched(self._n, n, first_id, seed, n_batches, C.byref(c), ese.ctypes.data_as(_ffi._dp),
-                                          cse.ctypes.data_as(_ffi._dp)):
-            raise RuntimeError("r3d_node_run_batched failed: " + self._lib.r3d_last_error().decode())
-        res._from_c(c)
-        return res, ese, cse
+        return _run_batched_to_host(self._lib, "r3d_node_run_batched", self._n, self.model, n, first_id, seed, n_batches,
+                                    result)
 
     def engine(self, shard):
         """r3d_node_engine: shard g's engine as a raw handle for the library's calls (it stays the node's)."""
@@ -961,17 +968,10 @@ class Engine:
         keep_batches: the run goes through r3d_run_device_batched on torch tensors and the blocks themselves follow
         as numpy arrays, (..., batch_energy[B, seis, bin, 5], batch_counts[B, seis, bin, 2])."""
         m = self.model
+        if not keep_batches:
+            return _run_batched_to_host(self._lib, "r3d_run_batched", self._e, m, n, first_id, seed, n_batches, None)
         res = m.new_result()
         shape = (m.n_seismometers, m.n_bins)
-        if not keep_batches:
-            ese = np.zeros(shape + (_ffi.R3D_N_ENERGY,))
-            cse = np.zeros(shape + (_ffi.R3D_N_COUNT,))
-            c = res._as_c()
-            if self._lib.r3d_run_batched(self._e, n, first_id, seed, n_batches, C.byref(c), ese.ctypes.data_as(_ffi._dp),
-                                         cse.ctypes.data_as(_ffi._dp)):
-                raise RuntimeError("r3d_run_batched failed: " + self._lib.r3d_last_error().decode())
-            res._from_c(c)
-            return res, ese, cse
         import torch
         dev = torch.device("cuda", self.device)
         B = max(int(n_batches), 0)
@@ -998,24 +998,18 @@ class Engine:
         Returns (Result, energy_se, counts_se, window_energy [S, W], window_counts [S, W, 2], window_se [S, W]) and,
         with keep_batch_windows, the batches' own window sums [B, S, W] behind them (window_log_ratio's input)."""
         m = self.model
-        res = m.new_result()
-        shape = (m.n_seismometers, m.n_bins)
         b = np.ascontiguousarray(bins, dtype=np.uint32)
         if b.ndim != 3 or b.shape[0] != m.n_seismometers or b.shape[2] != 2:
             raise ValueError("bins must be [n_seismometers, W, 2]")
         W = b.shape[1]
         spec = window_spec(m.n_seismometers, m.n_bins, W, b.ctypes.data, weights)
-        ese, cse = np.zeros(shape + (_ffi.R3D_N_ENERGY,)), np.zeros(shape + (_ffi.R3D_N_COUNT,))
         we, wse = np.zeros((m.n_seismometers, W)), np.zeros((m.n_seismometers, W))
         wc = np.zeros((m.n_seismometers, W, _ffi.R3D_N_COUNT), dtype=np.uint64)
         bwe = np.zeros((max(int(n_batches), 0), m.n_seismometers, W)) if keep_batch_windows else None
-        c = res._as_c()
-        if self._lib.r3d_run_batched_windows(self._e, n, first_id, seed, n_batches, C.byref(c), ese.ctypes.data_as(_ffi._dp),
-                                             cse.ctypes.data_as(_ffi._dp), C.byref(spec), we.ctypes.data_as(_ffi._dp),
-                                             wc.ctypes.data_as(C.POINTER(C.c_uint64)), wse.ctypes.data_as(_ffi._dp),
-                                             bwe.ctypes.data_as(_ffi._dp) if bwe is not None else None):
-            raise RuntimeError("r3d_run_batched_windows failed: " + self._lib.r3d_last_error().decode())
-        res._from_c(c)
+        res, ese, cse = _run_batched_to_host(
+            self._lib, "r3d_run_batched_windows", self._e, m, n, first_id, seed, n_batches, None, C.byref(spec),
+            we.ctypes.data_as(_ffi._dp), wc.ctypes.data_as(C.POINTER(C.c_uint64)), wse.ctypes.data_as(_ffi._dp),
+            bwe.ctypes.data_as(_ffi._dp) if bwe is not None else None)
         return (res, ese, cse, we, wc, wse) + ((bwe,) if keep_batch_windows else ())
 
     def run_batched_array_image(self, n, n_batches, first, last, weights, gamma_log2=1, rho=0.3, fit=(0, 0),
@@ -1028,14 +1022,11 @@ class Engine:
         sum of bins --, with keep_row_sums batch_row_sum [B, A], and with a fit: fit (c, q), fit_se (se(ln c), se(q)),
         curve_made, curve [A], image_curve, image_curve_se [A, n_bins]."""
         m = self.model
-        res = m.new_result()
-        shape = (m.n_seismometers, m.n_bins)
         A = int(last) - int(first) + 1
         if A < 1:
             raise ValueError("the array needs first <= last")
         spec = array_image_spec(m.n_seismometers, m.n_bins, first, last, weights, gamma_log2, rho, None,
                                 m.n_bins * m.desc.params.time_per_bin, fit, ranges, curve)
-        ese, cse = np.zeros(shape + (_ffi.R3D_N_ENERGY,)), np.zeros(shape + (_ffi.R3D_N_COUNT,))
         img = dict(image=np.zeros((A, m.n_bins)), image_se=np.zeros((A, m.n_bins)), summed=np.zeros(A), summed_se=np.zeros(A),
                    peak=np.zeros(A), peak_bin=np.zeros(A, dtype=np.uint32), lit=np.zeros(A, dtype=np.uint32))
         if keep_row_sums:
@@ -1044,11 +1035,8 @@ class Engine:
         if has_fit:
             img.update(curve=np.zeros(A), image_curve=np.zeros((A, m.n_bins)), image_curve_se=np.zeros((A, m.n_bins)))
         out = _ffi.ArrayImageResult(size=C.sizeof(_ffi.ArrayImageResult), **{k: v.ctypes.data for k, v in img.items()})
-        c = res._as_c()
-        if self._lib.r3d_run_batched_array_image(self._e, n, first_id, seed, n_batches, C.byref(c), ese.ctypes.data_as(_ffi._dp),
-                                                 cse.ctypes.data_as(_ffi._dp), C.byref(spec), C.byref(out)):
-            raise RuntimeError("r3d_run_batched_array_image failed: " + self._lib.r3d_last_error().decode())
-        res._from_c(c)
+        res, ese, cse = _run_batched_to_host(self._lib, "r3d_run_batched_array_image", self._e, m, n, first_id, seed, n_batches,
+                                             None, C.byref(spec), C.byref(out))
         if has_fit:
             img.update(fit=tuple(out.fit), fit_se=tuple(out.fit_se), curve_made=bool(out.curve_made))
         return res, ese, cse, img

@@ -12,7 +12,9 @@
 // shard 0's device, and one kernel there finishes (within-shard plus between-shard deviations).
 //
 // This file stands ON TOP of the engine: it calls only what include/r3d.h declares and owns the streams and
-// events it overlaps the batches with; nothing in csrc/ knows about it.
+// events it overlaps the batches with; nothing in csrc/ knows about it.  The calls that bring a run to the host
+// (r3d_run_batched, r3d_run_batched_windows) are each their own checks around common/r3d_entry.h BatchedRun, which
+// has the protocol, and ResultBlock, which has the format of what comes down; the node uses the latter too.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -358,84 +360,6 @@ int enqueue_batches(const char* who, r3d_engine* e, Lanes* lanes, uint64_t n, ui
   return rc;
 }
 
-// r3d_run_batched, and with a window spec (bins on the HOST, checked by the caller) r3d_run_batched_windows: the batches
-// then run into blocks of this call's own, which stay on the device for the window kernel and the moments of its sums.
-int run_batched_to_host(const char* who, r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
-                        r3d_result* out, double* energy_se, double* counts_se, const r3d_window_spec* w,
-                        double* window_energy, uint64_t* window_counts, double* window_se, double* batch_window_energy) {
-  if (!e) return g_error = "null engine", 1;
-  if (!out || !out->energy || !out->counts) return g_error = "null result", 1;
-  if (check_batches(who, n, n_batches)) return 1;
-  if (refuse_engine_state(e, who)) return 1;
-  const int device = engine_device(e, who);
-  if (device < 0) return 1;
-  OnDevice on(device);
-  if (on.status != hipSuccess) return refuse(who, on.status);
-  const size_t ne = r3d_energy_len(e), nc = r3d_counts_len(e), ns = R3D_N_SCALARS;
-  const size_t B = n_batches, sw = w ? (size_t)w->n_seismometers * w->n_windows : 0;
-  // one block: totals (energy, counts, scalars), then the two se arrays; with windows, behind them what the host reads
-  // of those (sums [sw], counts [sw][2], se [sw], the batches' sums [B][sw]) and what it does not (the batches' window
-  // counts [B][sw][2], the bins, the batch blocks)
-  DeviceBuffer block;
-  const size_t words = 2 * ne + 2 * nc + ns, win_words = (4 + B) * sw;
-  const size_t rest_words = w ? 2 * B * sw + sw + B * (ne + nc) : 0;
-  if (hipError_t err = block.alloc((words + win_words + rest_words) * 8); err != hipSuccess) return refuse(who, err);
-  double* const d_e = block.as<double>();
-  uint64_t* const d_c = reinterpret_cast<uint64_t*>(d_e + ne);
-  uint64_t* const d_s = d_c + nc;
-  double* const d_ese = reinterpret_cast<double*>(d_s + ns);
-  double* const d_cse = d_ese + ne;
-  double* const d_we = d_cse + nc;
-  uint64_t* const d_wc = reinterpret_cast<uint64_t*>(d_we + sw);
-  double* const d_wse = reinterpret_cast<double*>(d_wc + 2 * sw);
-  double* const d_bwe = d_wse + sw;
-  uint64_t* const d_bwc = reinterpret_cast<uint64_t*>(d_bwe + B * sw);
-  uint32_t* const d_bins = reinterpret_cast<uint32_t*>(d_bwc + 2 * B * sw);
-  double* const d_be = w ? reinterpret_cast<double*>(d_bwc + 2 * B * sw + sw) : nullptr;
-  uint64_t* const d_bc = w ? reinterpret_cast<uint64_t*>(d_be + B * ne) : nullptr;
-  std::vector<uint64_t> host(words + win_words);
-  hipStream_t s = nullptr;
-  hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-  if (err == hipSuccess) err = hipMemsetAsync(block.p, 0, (words + 3 * sw) * 8, s);
-  if (err == hipSuccess && w) err = hipMemcpyAsync(d_bins, w->d_bins, sw * 8, hipMemcpyHostToDevice, s);
-  int rc = err == hipSuccess ? 0 : refuse(who, err);
-  if (rc == 0) rc = r3d_run_device_batched(e, n, first_id, seed, n_batches, d_e, d_c, d_s, d_ese, d_cse, d_be, d_bc, s);
-  if (rc == 0 && w) rc = enqueue_window_sums(n_batches, d_be, d_bc, w, d_bins, d_bwe, d_bwc, nullptr, s);
-  if (rc == 0 && w)
-    rc = enqueue_moments(n_batches, d_bwe, sw, d_bwc, 2 * sw, nullptr, 0, d_we, d_wc, nullptr, d_wse, nullptr, s);
-  if (s) {   // (also after a refusal: what was enqueued reads the block)
-    err = hipStreamSynchronize(s);
-    if (err == hipSuccess && rc == 0) err = hipMemcpy(host.data(), block.p, host.size() * 8, hipMemcpyDeviceToHost);
-    if (err != hipSuccess && rc == 0) rc = refuse(who, err);
-    (void)hipStreamDestroy(s);
-  }
-  if (rc) return rc;
-  const double* const he = reinterpret_cast<const double*>(host.data());
-  const uint64_t* const hc = host.data() + ne;
-  const uint64_t* const hs = hc + nc;
-  const double* const hese = reinterpret_cast<const double*>(hs + ns);
-  for (size_t i = 0; i < ne; i++) out->energy[i] += he[i];
-  for (size_t i = 0; i < nc; i++) out->counts[i] += hc[i];
-  out->n_lost += hs[0], out->n_timeout += hs[1], out->n_invalid += hs[2];
-  for (int r = 0; r < R3D_INV_NUM; r++) out->invalid_reasons[r] += hs[3 + r];
-  for (int k = 0; k < R3D_EV_NUM; k++) out->events[k] += hs[3 + R3D_INV_NUM + k];
-  if (energy_se)
-    for (size_t i = 0; i < ne; i++) energy_se[i] = hese[i];
-  if (counts_se)
-    for (size_t i = 0; i < nc; i++) counts_se[i] = hese[ne + i];
-  if (w) {
-    const double* const hwe = hese + ne + nc;
-    const uint64_t* const hwc = reinterpret_cast<const uint64_t*>(hwe + sw);
-    const double* const hwse = reinterpret_cast<const double*>(hwc + 2 * sw);
-    for (size_t i = 0; i < sw; i++) window_energy[i] += hwe[i], window_se[i] = hwse[i];
-    if (window_counts)
-      for (size_t i = 0; i < 2 * sw; i++) window_counts[i] += hwc[i];
-    if (batch_window_energy)
-      for (size_t i = 0; i < B * sw; i++) batch_window_energy[i] = hwse[sw + i];
-  }
-  return 0;
-}
-
 }  // namespace
 }  // namespace r3d
 
@@ -499,8 +423,11 @@ int r3d_run_device_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_
 
 int r3d_run_batched(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches, r3d_result* out,
                     double* energy_se, double* counts_se) {
-  return run_batched_to_host("r3d_run_batched", e, n, first_id, seed, n_batches, out, energy_se, counts_se, nullptr, nullptr,
-                             nullptr, nullptr, nullptr);
+  if (!e) return g_error = "null engine", 1;
+  if (!out || !out->energy || !out->counts) return g_error = "null result", 1;
+  BatchedRun run("r3d_run_batched", e, n, n_batches);
+  if (run.status()) return run.status();
+  return run.close(run.run(first_id, seed), out, energy_se, counts_se);
 }
 
 int r3d_window_sums(int device, uint32_t n_batches, const double* d_batch_energy, const uint64_t* d_batch_counts,
@@ -547,8 +474,39 @@ int r3d_run_batched_windows(r3d_engine* e, uint64_t n, uint64_t first_id, uint64
     if (w->d_bins[2 * i] > w->d_bins[2 * i + 1] || w->d_bins[2 * i + 1] > w->n_bins)
       return refuse(who, "window " + std::to_string(i % w->n_windows) + " of seismometer " +
                              std::to_string(i / w->n_windows) + " is not begin <= end <= n_bins");
-  return run_batched_to_host(who, e, n, first_id, seed, n_batches, out, energy_se, counts_se, w, window_energy, window_counts,
-                             window_se, batch_window_energy);
+  if (!out || !out->energy || !out->counts) return g_error = "null result", 1;
+  // behind the result block what the host reads (sums [sw], counts [sw][2], se [sw], the batches' sums [B][sw]) and what
+  // it does not (the batches' window counts [B][sw][2], the bins, the batch blocks, which stay on the device for the
+  // window kernel and the moments of its sums)
+  const size_t B = n_batches, sw = n_sw, ne = r3d_energy_len(e), nc = r3d_counts_len(e);
+  ExtraWords extra;
+  extra.read = (4 + B) * sw, extra.unread = 2 * B * sw + sw + B * (ne + nc), extra.zeroed = 3 * sw;
+  BatchedRun run(who, e, n, n_batches, extra);
+  if (run.status()) return run.status();
+  double* const d_we = reinterpret_cast<double*>(run.extra());
+  uint64_t* const d_wc = reinterpret_cast<uint64_t*>(d_we + sw);
+  double* const d_wse = reinterpret_cast<double*>(d_wc + 2 * sw);
+  double* const d_bwe = d_wse + sw;
+  uint64_t* const d_bwc = reinterpret_cast<uint64_t*>(d_bwe + B * sw);
+  uint32_t* const d_bins = reinterpret_cast<uint32_t*>(d_bwc + 2 * B * sw);
+  double* const d_be = reinterpret_cast<double*>(d_bwc + 2 * B * sw + sw);
+  uint64_t* const d_bc = reinterpret_cast<uint64_t*>(d_be + B * ne);
+  const hipError_t err = hipMemcpyAsync(d_bins, w->d_bins, sw * 8, hipMemcpyHostToDevice, run.stream());
+  int rc = err == hipSuccess ? 0 : refuse(who, err);
+  if (rc == 0) rc = run.run(first_id, seed, d_be, d_bc);
+  if (rc == 0) rc = enqueue_window_sums(n_batches, d_be, d_bc, w, d_bins, d_bwe, d_bwc, nullptr, run.stream());
+  if (rc == 0)
+    rc = enqueue_moments(n_batches, d_bwe, sw, d_bwc, 2 * sw, nullptr, 0, d_we, d_wc, nullptr, d_wse, nullptr, run.stream());
+  if ((rc = run.close(rc, out, energy_se, counts_se))) return rc;
+  const double* const hwe = reinterpret_cast<const double*>(run.host_extra());
+  const uint64_t* const hwc = reinterpret_cast<const uint64_t*>(hwe + sw);
+  const double* const hwse = reinterpret_cast<const double*>(hwc + 2 * sw);
+  for (size_t i = 0; i < sw; i++) window_energy[i] += hwe[i], window_se[i] = hwse[i];
+  if (window_counts)
+    for (size_t i = 0; i < 2 * sw; i++) window_counts[i] += hwc[i];
+  if (batch_window_energy)
+    for (size_t i = 0; i < B * sw; i++) batch_window_energy[i] = hwse[sw + i];
+  return 0;
 }
 
 int r3d_batch_partial(int device, uint32_t n_batches, const double* d_batch_energy, uint64_t n_energy,
@@ -689,16 +647,16 @@ int r3d_node_run_batched(r3d_node* node, uint64_t n, uint64_t first_id, uint64_t
 
   // the records travel to shard 0's device, each behind its shard's reduction; the merge follows them on that stream
   const Shard& root = shards.v[0];
-  const uint64_t result_words = 2 * ne + 2 * nc + ns;   // totals (energy, counts, scalars), then the two se arrays
-  std::vector<uint64_t> host(result_words);
+  const ResultBlock merged(ne, nc);
+  std::vector<uint64_t> host(merged.words());
   {
     OnDevice on(root.device);
     if (on.status != hipSuccess) return refuse(who, on.status);
-    hipError_t err = hipMalloc(&shards.root, ((uint64_t)D * rec + result_words) * 8);
+    hipError_t err = hipMalloc(&shards.root, ((uint64_t)D * rec + merged.words()) * 8);
     if (err != hipSuccess) return shards.root = nullptr, refuse(who, err);
     uint64_t* const gathered = static_cast<uint64_t*>(shards.root);
     uint64_t* const result = gathered + (uint64_t)D * rec;
-    err = hipMemsetAsync(result, 0, result_words * 8, root.s);
+    err = hipMemsetAsync(result, 0, merged.words() * 8, root.s);
     for (uint32_t g = 0; g < D && err == hipSuccess; g++) {
       err = hipStreamWaitEvent(root.s, shards.v[g].ready, 0);
       if (err == hipSuccess)
@@ -708,31 +666,16 @@ int r3d_node_run_batched(r3d_node* node, uint64_t n, uint64_t first_id, uint64_t
     if (err != hipSuccess) return refuse(who, err);
     const double* const g_e = reinterpret_cast<const double*>(gathered);
     const uint64_t* const g_c = gathered + 2 * ne;
-    double* const r_e = reinterpret_cast<double*>(result);
-    uint64_t* const r_c = result + ne;
-    uint64_t* const r_s = r_c + nc;
-    double* const r_ese = reinterpret_cast<double*>(r_s + ns);
     if (enqueue_merge(D, B, rec, rec, rec, g_e, g_e + ne, ne, g_c, reinterpret_cast<const double*>(g_c + nc), nc,
-                      g_c + 2 * nc, ns, r_e, r_c, r_s, r_ese, r_ese + ne, root.s))
+                      g_c + 2 * nc, ns, merged.energy(result), merged.counts(result), merged.scalars(result),
+                      merged.energy_se(result), merged.counts_se(result), root.s))
       return 1;
     err = hipStreamSynchronize(root.s);
-    if (err == hipSuccess) err = hipMemcpy(host.data(), result, result_words * 8, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(host.data(), result, merged.words() * 8, hipMemcpyDeviceToHost);
     if (err != hipSuccess) return refuse(who, err);
   }
   // (nothing was added to *out until every shard had run and the merged block was read)
-  const double* const he = reinterpret_cast<const double*>(host.data());
-  const uint64_t* const hc = host.data() + ne;
-  const uint64_t* const hs = hc + nc;
-  const double* const hese = reinterpret_cast<const double*>(hs + ns);
-  for (size_t i = 0; i < ne; i++) out->energy[i] += he[i];
-  for (size_t i = 0; i < nc; i++) out->counts[i] += hc[i];
-  out->n_lost += hs[0], out->n_timeout += hs[1], out->n_invalid += hs[2];
-  for (int r = 0; r < R3D_INV_NUM; r++) out->invalid_reasons[r] += hs[3 + r];
-  for (int k = 0; k < R3D_EV_NUM; k++) out->events[k] += hs[3 + R3D_INV_NUM + k];
-  if (energy_se)
-    for (size_t i = 0; i < ne; i++) energy_se[i] = hese[i];
-  if (counts_se)
-    for (size_t i = 0; i < nc; i++) counts_se[i] = hese[ne + i];
+  merged.add_into(host.data(), out, energy_se, counts_se);
   return 0;
 }
 
