@@ -102,9 +102,10 @@ oracle: oracle/libr3d_oracle.so oracle/libr3d_tables_oracle.so
 cli: main
 
 # The command-line program the reference's do-*.sh scripts call as ./main
-main: $(HOSTDIR)/main.cpp $(HOSTDIR)/scatter_out.cpp $(HOSTDIR)/scatter_out.hpp $(HOSTDIR)/scatter_plan.hpp \
+MAIN_SRC := $(HOSTDIR)/main.cpp $(HOSTDIR)/scatter_out.cpp $(HOSTDIR)/batch_out.cpp
+main: $(MAIN_SRC) $(HOSTDIR)/scatter_out.hpp $(HOSTDIR)/scatter_plan.hpp $(HOSTDIR)/batch_out.hpp $(HOSTDIR)/batch_plan.hpp \
       $(LIBDIR)/libr3d_host.so $(LIBDIR)/libr3d_hip.so $(ENGINE_HDR)
-	$(CXX) $(CXXFLAGS) -pthread -o $@ $(HOSTDIR)/main.cpp $(HOSTDIR)/scatter_out.cpp -L$(LIBDIR) -lr3d_host -lr3d_hip \
+	$(CXX) $(CXXFLAGS) -pthread -o $@ $(MAIN_SRC) -L$(LIBDIR) -lr3d_host -lr3d_hip \
 	    -Wl,-rpath,'$$ORIGIN/$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
 $(LIBDIR)/libr3d_host.so: $(HOST_SRC) $(HOST_HDR)

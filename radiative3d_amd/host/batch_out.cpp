@@ -1,0 +1,140 @@
+// batch_out.cpp -- see batch_out.hpp.
+#include "batch_out.hpp"
+
+#include <fstream>
+#include <iostream>
+
+#include "batch_plan.hpp"
+#include "dataout.hpp"
+
+namespace {
+
+// --lapse-windows: the batched run with its batch blocks kept on the device and the array's two windows per receiver
+// summed there (include/r3d.h r3d_run_batched_windows).  The call serves the whole model: receivers outside the array
+// get empty windows, and the array's rows are taken back out of what it returns.
+void run_lapse(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total,
+               BatchProducts& p) {
+  const size_t first = job.lapse.first, last = job.lapse.last, S = last - first + 1, all = (size_t)d.n_seismometers, B = job.batches;
+  std::vector<uint32_t> bins(4 * all);
+  batch_plan::spread_rows(job.lapse_bins.data(), first, last, all, 4, bins.data());
+  r3d_window_spec spec{};
+  spec.size = sizeof spec, spec.n_seismometers = (uint32_t)all, spec.n_bins = d.params.n_bins, spec.n_windows = 2;
+  spec.d_bins = bins.data();   // (for this call: on the host)
+  for (int k = 0; k < 3; k++) spec.weight[k] = job.lapse.axes[k];
+  std::vector<double> we(2 * all, 0.0), wse(2 * all, 0.0), bwe(B * 2 * all, 0.0);
+  std::vector<uint64_t> wc(4 * all, 0);
+  if (r3d_run_batched_windows(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data(), &spec, we.data(),
+                              wc.data(), wse.data(), bwe.data()))
+    throw Runtime(r3d_last_error());
+  p.window_energy.resize(2 * S), p.window_se.resize(2 * S), p.window_counts.resize(4 * S), p.batch_window_energy.resize(B * 2 * S);
+  batch_plan::take_rows(we.data(), 1, all, 2, first, last, p.window_energy.data());
+  batch_plan::take_rows(wse.data(), 1, all, 2, first, last, p.window_se.data());
+  batch_plan::take_rows(wc.data(), 1, all, 4, first, last, p.window_counts.data());
+  batch_plan::take_rows(bwe.data(), B, all, 2, first, last, p.batch_window_energy.data());
+}
+
+// --ttimage: the batched run with its batch blocks kept on the device and the array's image, fit and their jackknives
+// made there (include/r3d.h r3d_run_batched_array_image).
+void run_image(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total,
+               BatchProducts& p) {
+  const r3dh_ttimage_opts& tt = job.tt;
+  const size_t A = (size_t)tt.last - tt.first + 1, px = A * d.params.n_bins;
+  r3d_array_image_spec spec{};
+  spec.size = sizeof spec, spec.n_seismometers = (uint32_t)d.n_seismometers, spec.n_bins = d.params.n_bins;
+  spec.first = tt.first, spec.last = tt.last, spec.gamma_log2 = tt.gamma_log2, spec.mode = R3D_ARRAY_LEGACY;
+  spec.fit_begin = tt.fit_begin, spec.fit_end = tt.fit_end, spec.rho = tt.norm;
+  for (int k = 0; k < 3; k++) spec.weight[k] = tt.axes[k];
+  spec.window_length = d.params.time_per_bin * d.params.n_bins;
+  spec.range[0] = job.tt_distances.front(), spec.range[1] = job.tt_distances.back();
+  spec.curve_c = tt.curve_c, spec.curve_q = tt.curve_q;
+  const bool fit = spec.fit_begin != 0;
+  p.image.assign(px, 0.0), p.image_se.assign(px, 0.0), p.summed.assign(A, 0.0), p.summed_se.assign(A, 0.0);
+  p.peak.assign(A, 0.0), p.peak_bin.assign(A, 0), p.lit.assign(A, 0);
+  if (fit) p.curve.assign(A, 0.0), p.image_curve.assign(px, 0.0), p.image_curve_se.assign(px, 0.0);
+  r3d_array_image_result res{};
+  res.size = sizeof res, res.image = p.image.data(), res.image_se = p.image_se.data();
+  res.summed = p.summed.data(), res.summed_se = p.summed_se.data(), res.peak = p.peak.data();
+  res.peak_bin = p.peak_bin.data(), res.lit = p.lit.data();
+  if (fit) res.curve = p.curve.data(), res.image_curve = p.image_curve.data(), res.image_curve_se = p.image_curve_se.data();
+  if (r3d_run_batched_array_image(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data(), &spec, &res))
+    throw Runtime(r3d_last_error());
+  p.curve_made = res.curve_made;
+  for (int k = 0; k < 2; k++) p.fit[k] = res.fit[k], p.fit_se[k] = res.fit_se[k];
+}
+
+}  // namespace
+
+BatchJob make_batch_job(const MissionParams& mission, const Model& model) {
+  BatchJob job;
+  if (!mission.bRunSim || !(mission.ErrorBatches || mission.JobErrorBatches)) return job;
+  job.dir = mission.OutputDir, job.batches = mission.ErrorBatches ? mission.ErrorBatches : mission.JobErrorBatches;
+  job.kind = !mission.ErrorBatches ? BatchJob::JOB_ERRORS : mission.bLapse ? BatchJob::LAPSE : mission.bTTImage ? BatchJob::IMAGE : BatchJob::ERRORS;
+  if (job.kind == BatchJob::LAPSE) {
+    LapseRequest(model, mission, &job.lapse);
+    const size_t S = (size_t)job.lapse.last - job.lapse.first + 1;
+    job.lapse_distances.assign(S, 0.0), job.lapse_bins.assign(4 * S, 0), job.lapse_clipped.assign(2 * S, 0);
+    LapsePlan(model, job.lapse, job.lapse_distances.data(), job.lapse_bins.data(), job.lapse_clipped.data());
+  } else if (job.kind == BatchJob::IMAGE) {
+    TTImageRequest(model, mission, &job.tt);
+    const size_t A = (size_t)job.tt.last - job.tt.first + 1;
+    job.tt_distances.assign(A, 0.0), job.tt_azimuths.assign(A, 0.0);
+    TTImagePlan(model, job.tt, job.tt_distances.data(), job.tt_azimuths.data());
+  }
+  return job;
+}
+
+void check_batch_job(const BatchJob& job, size_t n_shards, uint32_t report_mask) {
+  if (job.kind == BatchJob::NONE || job.kind == BatchJob::JOB_ERRORS) return;
+  if (n_shards > 1)
+    throw Runtime("--error-batches runs on one device: --gpus / --devices name " + std::to_string(n_shards) +
+                  " shards (standard errors over several devices are not built: DESIGN.md section 5)." +
+                  "  --job-error-batches=N cuts the whole job into N batches over any number of shards.");
+  if (report_mask)
+    throw Runtime("--error-batches cannot be combined with --reports (the event log's launches run one at a time).");
+}
+
+BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& d, r3d_node* node, uint64_t n, uint64_t seed,
+                            r3d_result& total) {
+  BatchProducts p;
+  p.energy_se.assign((size_t)d.n_seismometers * d.params.n_bins * R3D_N_ENERGY, 0.0);
+  p.counts_se.assign((size_t)d.n_seismometers * d.params.n_bins * R3D_N_COUNT, 0.0);
+  // JOB_ERRORS: the whole job as N batches dealt to the shards, every shard's moments taken on its device and merged on
+  // shard 0's (include/r3d.h r3d_node_run_batched).  The others: the one shard's ids as B batches, every bin's standard
+  // error from their spread (r3d_run_batched); the totals are those of the plain run up to summation order
+  const bool shards = job.kind == BatchJob::JOB_ERRORS;
+  r3d_engine* e = r3d_node_engine(node, 0);
+  if (job.kind == BatchJob::LAPSE) run_lapse(job, d, e, n, seed, total, p);
+  else if (job.kind == BatchJob::IMAGE) run_image(job, d, e, n, seed, total, p);
+  else if (shards ? r3d_node_run_batched(node, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data())
+                  : r3d_run_batched(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data()))
+    throw Runtime(r3d_last_error());
+  if (shards) std::cout << "|  Batches: " << job.batches << " over " << r3d_node_size(node) << " shards\n";
+  else std::cout << "|  Batches: " << job.batches << " (standard errors from batch means)\n";
+  return p;
+}
+
+void write_batch_outputs(const BatchJob& job, const Model& model, const BatchProducts& p) {
+  if (job.kind == BatchJob::NONE) return;
+  OutputSeismometerErrors(model, p.energy_se.data(), p.counts_se.data(), job.batches, job.dir);
+  if (job.kind != BatchJob::LAPSE && job.kind != BatchJob::IMAGE) return;
+  const std::string fn = output_path(job.dir, job.kind == BatchJob::LAPSE ? "lapse.octv" : "ttimage.octv");
+  std::ofstream f(fn.c_str());
+  if (job.kind == BatchJob::LAPSE) {
+    r3dh_lapse_result res{};
+    res.size = sizeof res, res.n_batches = job.batches;
+    res.distances = job.lapse_distances.data(), res.bins = job.lapse_bins.data(), res.clipped = job.lapse_clipped.data();
+    res.window_energy = p.window_energy.data(), res.window_se = p.window_se.data();
+    res.window_counts = p.window_counts.data(), res.batch_window_energy = p.batch_window_energy.data();
+    OutputLapse(model, job.lapse, res, f);
+  } else {
+    r3dh_ttimage_result res{};   // (the three arrays of the fit are read with has_fit only)
+    res.size = sizeof res, res.n_batches = job.batches, res.has_fit = job.tt.fit_begin != 0, res.curve_made = p.curve_made;
+    res.distances = job.tt_distances.data(), res.azimuths = job.tt_azimuths.data();
+    res.image = p.image.data(), res.image_se = p.image_se.data(), res.lit = p.lit.data();
+    res.summed = p.summed.data(), res.summed_se = p.summed_se.data(), res.peak = p.peak.data(), res.peak_bin = p.peak_bin.data();
+    for (int k = 0; k < 2; k++) res.fit[k] = p.fit[k], res.fit_se[k] = p.fit_se[k];
+    res.curve = p.curve.data(), res.image_curve = p.image_curve.data(), res.image_curve_se = p.image_curve_se.data();
+    OutputTTImage(model, job.tt, res, f);
+  }
+  if (!f) throw Runtime("cannot write " + fn);
+}

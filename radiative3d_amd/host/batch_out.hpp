@@ -1,0 +1,65 @@
+// batch_out.hpp -- the batched-run stage of ./main: what --error-batches, --job-error-batches, --lapse-windows and
+// --ttimage run in place of the plain run, and what they write after it (seis_NNN_err.octv, lapse.octv, ttimage.octv).
+// Compiled into ./main beside main.cpp (it calls r3d_run_batched* and r3d_node_run_batched of the engine's library, so
+// it is no part of libr3d_host.so); its row arithmetic is batch_plan.hpp.
+#ifndef R3DH_BATCH_OUT_HPP_
+#define R3DH_BATCH_OUT_HPP_
+
+#include <string>
+#include <vector>
+
+#include "../../include/r3d.h"
+#include "../../include/r3d_host.h"
+#include "cmdline.hpp"
+#include "model.hpp"
+
+// A file of the run: `name` under --output-dir ("" = the current directory).
+inline std::string output_path(const std::string& dir, const std::string& name) { return dir.empty() ? name : dir + "/" + name; }
+
+// What the four options ask for, and where it goes.
+struct BatchJob {
+  // ERRORS: --error-batches alone; LAPSE, IMAGE: with --lapse-windows, --ttimage; JOB_ERRORS: --job-error-batches
+  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS } kind = NONE;
+  unsigned batches = 0;
+  std::string dir;   // --output-dir
+  // LAPSE: the request and the array's plan, [S] receivers (include/r3d_host.h r3dh_lapse_plan)
+  r3dh_lapse_opts lapse{};
+  std::vector<double> lapse_distances;
+  std::vector<uint32_t> lapse_bins;
+  std::vector<int32_t> lapse_clipped;
+  // IMAGE: the request and the array's plan, [A] receivers (include/r3d_host.h r3dh_ttimage_plan)
+  r3dh_ttimage_opts tt{};
+  std::vector<double> tt_distances, tt_azimuths;
+};
+
+// What a batched run hands back beside its totals: every bin's standard error, then the kind's own arrays (the shapes
+// are those of include/r3d_host.h r3dh_lapse_result, r3dh_ttimage_result).  Vectors and values only.
+struct BatchProducts {
+  std::vector<double> energy_se, counts_se;
+  // LAPSE
+  std::vector<double> window_energy, window_se, batch_window_energy;
+  std::vector<uint64_t> window_counts;
+  // IMAGE (curve, image_curve, image_curve_se: with --ttimage-fit only)
+  std::vector<double> image, image_se, summed, summed_se, peak, curve, image_curve, image_curve_se;
+  std::vector<uint32_t> peak_bin, lit;
+  uint32_t curve_made = 0;
+  double fit[2] = {0, 0}, fit_se[2] = {0, 0};
+};
+
+// The job of a simulation run (`kind` stays NONE without one of the options).  The model is needed for the arrays:
+// throws what LapseRequest / LapsePlan / TTImageRequest / TTImagePlan (dataout.hpp) throw.
+BatchJob make_batch_job(const MissionParams& mission, const Model& model);
+
+// What --error-batches cannot be combined with, told BEFORE the node is built.  Throws Runtime.
+void check_batch_job(const BatchJob& job, size_t n_shards, uint32_t report_mask);
+
+// The run of the ids 0 .. n - 1 in the job's batches (kind != NONE), on the node's one shard or, for JOB_ERRORS, over
+// all of them: `total` (whose arrays the caller owns) gets the sums, the returned products the rest.  Prints the
+// `|  Batches: ...` line.  Throws Runtime.
+BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& model, r3d_node* node, uint64_t n, uint64_t seed,
+                            r3d_result& total);
+
+// seis_NNN_err.octv, then lapse.octv or ttimage.octv, under the job's directory.  Throws Runtime.
+void write_batch_outputs(const BatchJob& job, const Model& model, const BatchProducts& products);
+
+#endif

@@ -4,7 +4,9 @@
 // ("@@ __PHASE__", "#  R3D_GRID:", "#  BEGIN SCATTERER DUMP:"), same output
 // files.  The N-phonon loop itself (Model::RunSimulation, model.cpp:602-633)
 // is one call into the engine's C-ABI.  What a run with --scatter-grid writes afterwards (the grid, its views, its maps)
-// is the output stage of scatter_out.cpp; this file builds its job, has it checked before the run and calls it once.
+// is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches, --lapse-windows and --ttimage run
+// and write (the batched runs, seis_NNN_err.octv, lapse.octv, ttimage.octv) is the stage of batch_out.cpp.  This file
+// makes both jobs, has them checked before the node is built, and calls each once to run and once to write.
 //
 // Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B`,
 // `--job-error-batches=N` (error bars of a job on any number of shards), `--lapse-windows` (lapse.octv) and `--ttimage`
@@ -23,6 +25,7 @@
 
 #include "../../include/r3d.h"
 #include "../csrc/r3d_physics.h"   // rt_weights(): the --rtcoef-test mission
+#include "batch_out.hpp"
 #include "cmdline.hpp"
 #include "dataout.hpp"
 #include "scatter_out.hpp"
@@ -120,26 +123,19 @@ struct StdoutToStderr {
 };
 
 // What a simulation run hands back: the summed result with the arrays it points into, the report stream where one
-// was asked for, and the bins' standard errors under --error-batches.
+// was asked for, and what a batched run made beside them (batch_out.hpp).  `total` points into `energy` and `counts`:
+// the struct moves (the vectors keep their arrays) and cannot be copied.
 struct SimulationOutput {
   r3d_result total{};
   std::vector<double> energy;
   std::vector<uint64_t> counts;
   std::vector<r3d_event> events;
   uint64_t events_dropped = 0;
-  std::vector<double> energy_se, counts_se;
-  // --lapse-windows: the array's plan and its window sums (include/r3d_host.h r3dh_lapse_result), [S] receivers
-  r3dh_lapse_opts lapse{};
-  std::vector<double> lapse_distances, lapse_energy, lapse_se, lapse_batch_energy;
-  std::vector<uint32_t> lapse_bins;
-  std::vector<int32_t> lapse_clipped;
-  std::vector<uint64_t> lapse_counts;
-  // --ttimage: the array's plan and its image (include/r3d_host.h r3dh_ttimage_result), [A] receivers
-  r3dh_ttimage_opts tt{};
-  r3dh_ttimage_result tt_res{};
-  std::vector<double> tt_distances, tt_azimuths, tt_image, tt_image_se, tt_summed, tt_summed_se, tt_peak, tt_curve, tt_cimage,
-      tt_cimage_se;
-  std::vector<uint32_t> tt_peak_bin, tt_lit;
+  BatchProducts batch;
+  SimulationOutput() = default;
+  SimulationOutput(const SimulationOutput&) = delete;
+  SimulationOutput& operator=(const SimulationOutput&) = delete;
+  SimulationOutput(SimulationOutput&&) = default;
 };
 
 // The report stream of the run, shard after shard (ids ascend across shards): at most caps[g] records of engine g,
@@ -159,9 +155,9 @@ void read_reports(const std::vector<r3d_engine*>& engines, const std::vector<uin
 // the requested devices (mission.Devices), one engine per entry, and sums the shards' blocks on the devices (RCCL; on
 // the host when two shards share a device).  With a scatter grid every shard's engine fills its own grid in HBM; the
 // grids are then added by frame (r3d_volume_reduce_by_frame: every engine ends with the job's counts for its share of
-// the frames) and handed to the output stage (scatter_out.hpp).
+// the frames) and handed to the output stage (scatter_out.hpp).  A batch job (batch_out.hpp) runs in the plain run's place.
 SimulationOutput run_simulation(const Model& model, const MissionParams& mission, r3d_node* node, uint32_t report_mask,
-                                const GridJob& grid) {
+                                const GridJob& grid, const BatchJob& batch) {
   const r3d_model_desc& d = model.Desc();
   const uint64_t n = (uint64_t)std::max(0L, model.NumPhonons()), seed = mission.Seed;
   const int gpus = r3d_node_size(node);
@@ -181,80 +177,8 @@ SimulationOutput run_simulation(const Model& model, const MissionParams& mission
     if (report_mask && r3d_engine_set_event_log(e, report_mask, caps[g])) throw Runtime(r3d_last_error());
     if (grid.on && r3d_engine_set_volume(e, &grid.desc)) throw Runtime(r3d_last_error());
   }
-  if (mission.ErrorBatches) {
-    // --error-batches: the one shard's ids as B batches, every bin's standard error from their spread
-    // (include/r3d.h r3d_run_batched); the totals are those of the plain run up to summation order
-    out.energy_se.assign(ne, 0.0), out.counts_se.assign(nc, 0.0);
-    if (mission.bLapse) {
-      // --lapse-windows: the same run with its batch blocks kept on the device and the array's two windows per receiver
-      // summed there (include/r3d.h r3d_run_batched_windows); receivers outside the array get empty windows
-      LapseRequest(model, mission, &out.lapse);
-      const size_t S = (size_t)out.lapse.last - out.lapse.first + 1, all = (size_t)d.n_seismometers, B = mission.ErrorBatches;
-      out.lapse_distances.assign(S, 0.0), out.lapse_bins.assign(4 * S, 0), out.lapse_clipped.assign(2 * S, 0);
-      LapsePlan(model, out.lapse, out.lapse_distances.data(), out.lapse_bins.data(), out.lapse_clipped.data());
-      std::vector<uint32_t> bins(4 * all, 0);
-      std::copy(out.lapse_bins.begin(), out.lapse_bins.end(), bins.begin() + 4 * out.lapse.first);
-      r3d_window_spec spec{};
-      spec.size = sizeof spec, spec.n_seismometers = (uint32_t)all, spec.n_bins = d.params.n_bins, spec.n_windows = 2;
-      spec.d_bins = bins.data();   // (for this call: on the host)
-      for (int k = 0; k < 3; k++) spec.weight[k] = out.lapse.axes[k];
-      std::vector<double> we(2 * all, 0.0), wse(2 * all, 0.0), bwe(B * 2 * all, 0.0);
-      std::vector<uint64_t> wc(4 * all, 0);
-      if (r3d_run_batched_windows(engines[0], n, 0, seed, mission.ErrorBatches, &out.total, out.energy_se.data(),
-                                  out.counts_se.data(), &spec, we.data(), wc.data(), wse.data(), bwe.data()))
-        throw Runtime(r3d_last_error());
-      const size_t lo = out.lapse.first;
-      out.lapse_energy.assign(we.begin() + 2 * lo, we.begin() + 2 * (lo + S));
-      out.lapse_se.assign(wse.begin() + 2 * lo, wse.begin() + 2 * (lo + S));
-      out.lapse_counts.assign(wc.begin() + 4 * lo, wc.begin() + 4 * (lo + S));
-      for (size_t j = 0; j < B; j++)
-        out.lapse_batch_energy.insert(out.lapse_batch_energy.end(), bwe.begin() + 2 * (j * all + lo),
-                                      bwe.begin() + 2 * (j * all + lo + S));
-    } else if (mission.bTTImage) {
-      // --ttimage: the same run with its batch blocks kept on the device and the array's image, fit and their jackknives
-      // made there (include/r3d.h r3d_run_batched_array_image)
-      TTImageRequest(model, mission, &out.tt);
-      const size_t A = (size_t)out.tt.last - out.tt.first + 1, px = A * d.params.n_bins;
-      out.tt_distances.assign(A, 0.0), out.tt_azimuths.assign(A, 0.0);
-      TTImagePlan(model, out.tt, out.tt_distances.data(), out.tt_azimuths.data());
-      r3d_array_image_spec spec{};
-      spec.size = sizeof spec, spec.n_seismometers = (uint32_t)d.n_seismometers, spec.n_bins = d.params.n_bins;
-      spec.first = out.tt.first, spec.last = out.tt.last, spec.gamma_log2 = out.tt.gamma_log2, spec.mode = R3D_ARRAY_LEGACY;
-      spec.fit_begin = out.tt.fit_begin, spec.fit_end = out.tt.fit_end, spec.rho = out.tt.norm;
-      for (int k = 0; k < 3; k++) spec.weight[k] = out.tt.axes[k];
-      spec.window_length = d.params.time_per_bin * d.params.n_bins;
-      spec.range[0] = out.tt_distances.front(), spec.range[1] = out.tt_distances.back();
-      spec.curve_c = out.tt.curve_c, spec.curve_q = out.tt.curve_q;
-      const bool fit = spec.fit_begin != 0;
-      out.tt_image.assign(px, 0.0), out.tt_image_se.assign(px, 0.0), out.tt_summed.assign(A, 0.0), out.tt_summed_se.assign(A, 0.0);
-      out.tt_peak.assign(A, 0.0), out.tt_peak_bin.assign(A, 0), out.tt_lit.assign(A, 0);
-      if (fit) out.tt_curve.assign(A, 0.0), out.tt_cimage.assign(px, 0.0), out.tt_cimage_se.assign(px, 0.0);
-      r3d_array_image_result res{};
-      res.size = sizeof res, res.image = out.tt_image.data(), res.image_se = out.tt_image_se.data();
-      res.summed = out.tt_summed.data(), res.summed_se = out.tt_summed_se.data(), res.peak = out.tt_peak.data();
-      res.peak_bin = out.tt_peak_bin.data(), res.lit = out.tt_lit.data();
-      if (fit) res.curve = out.tt_curve.data(), res.image_curve = out.tt_cimage.data(), res.image_curve_se = out.tt_cimage_se.data();
-      if (r3d_run_batched_array_image(engines[0], n, 0, seed, mission.ErrorBatches, &out.total, out.energy_se.data(),
-                                      out.counts_se.data(), &spec, &res))
-        throw Runtime(r3d_last_error());
-      r3dh_ttimage_result& w = out.tt_res;
-      w.size = sizeof w, w.n_batches = mission.ErrorBatches, w.has_fit = fit, w.curve_made = res.curve_made;
-      w.distances = out.tt_distances.data(), w.azimuths = out.tt_azimuths.data(), w.image = res.image, w.image_se = res.image_se;
-      w.lit = res.lit, w.summed = res.summed, w.summed_se = res.summed_se, w.peak = res.peak, w.peak_bin = res.peak_bin;
-      for (int k = 0; k < 2; k++) w.fit[k] = res.fit[k], w.fit_se[k] = res.fit_se[k];
-      w.curve = res.curve, w.image_curve = res.image_curve, w.image_curve_se = res.image_curve_se;
-    } else if (r3d_run_batched(engines[0], n, 0, seed, mission.ErrorBatches, &out.total, out.energy_se.data(),
-                               out.counts_se.data())) {
-      throw Runtime(r3d_last_error());
-    }
-    std::cout << "|  Batches: " << mission.ErrorBatches << " (standard errors from batch means)\n";
-  } else if (mission.JobErrorBatches) {
-    // --job-error-batches: the whole job as N batches dealt to the shards, every shard's moments taken on its device
-    // and merged on shard 0's (include/r3d.h r3d_node_run_batched)
-    out.energy_se.assign(ne, 0.0), out.counts_se.assign(nc, 0.0);
-    if (r3d_node_run_batched(node, n, 0, seed, mission.JobErrorBatches, &out.total, out.energy_se.data(), out.counts_se.data()))
-      throw Runtime(r3d_last_error());
-    std::cout << "|  Batches: " << mission.JobErrorBatches << " over " << gpus << " shards\n";
+  if (batch.kind != BatchJob::NONE) {
+    out.batch = run_batch_job(batch, d, node, n, seed, out.total);
   } else if (r3d_node_run(node, n, 0, seed, &out.total)) {
     throw Runtime(r3d_last_error());
   }
@@ -326,9 +250,7 @@ int main(int argc, char* argv[]) {
   if (mission.bRunSim && !par.HostTables) par.DeviceTables = true;
   OutputModelParams(par, std::cout);
   if (mission.bOutputModParamsOctv) {
-    std::string fn = mission.OutputDir.empty() ? mission.FNModParamsOctv
-                                               : mission.OutputDir + "/" + mission.FNModParamsOctv;
-    std::ofstream f(fn.c_str());
+    std::ofstream f(output_path(mission.OutputDir, mission.FNModParamsOctv).c_str());
     OutputModelParamsOctave(par, f);
   }
   uint32_t report_mask = 0;
@@ -353,12 +275,9 @@ int main(int argc, char* argv[]) {
       if (mission.Devices.empty())
         for (int g = 0; g < std::max(1, mission.Gpus); g++) mission.Devices.push_back(g);
       const std::vector<int>& devices = mission.Devices;
-      if (mission.bRunSim && mission.ErrorBatches && devices.size() > 1)
-        throw Runtime("--error-batches runs on one device: --gpus / --devices name " + std::to_string(devices.size()) +
-                      " shards (standard errors over several devices are not built: DESIGN.md section 5)." +
-                      "  --job-error-batches=N cuts the whole job into N batches over any number of shards.");
-      if (mission.bRunSim && mission.ErrorBatches && report_mask)
-        throw Runtime("--error-batches cannot be combined with --reports (the event log's launches run one at a time).");
+      // what the run is asked for beyond its seismograms is made into jobs and checked here: a refusal needs no device
+      const BatchJob batch = make_batch_job(mission, model);
+      check_batch_job(batch, devices.size(), report_mask);
       const GridJob grid = make_grid_job(mission, par);
       check_grid_job(grid, devices.size());
       NodeHolder held;
@@ -384,14 +303,12 @@ int main(int argc, char* argv[]) {
       phase = "during simulation execution:";
       if (mission.bRunSim) {
         std::cout << "@@ __BEGINNING_SIMULATION__" << std::endl;
-        const SimulationOutput run = run_simulation(model, mission, held.node, report_mask, grid);
+        const SimulationOutput run = run_simulation(model, mission, held.node, report_mask, grid, batch);
         if (report_mask) {   // the reference writes them as they happen: stdout, or --report-file
           if (mission.ReportFile.empty()) {
             OutputReports(run.events.data(), run.events.size(), std::cout);
           } else {
-            const std::string fn = mission.OutputDir.empty() ? mission.ReportFile
-                                                             : mission.OutputDir + "/" + mission.ReportFile;
-            std::ofstream f(fn.c_str());
+            std::ofstream f(output_path(mission.OutputDir, mission.ReportFile).c_str());
             OutputReports(run.events.data(), run.events.size(), f);
           }
           if (run.events_dropped) std::cerr << "Note: " << run.events_dropped << " report lines did not fit the event buffer.\n";
@@ -401,26 +318,7 @@ int main(int argc, char* argv[]) {
         // seis_traces_asc.dat is opened in the CWD whatever --output-dir says (dataout.hpp:332)
         std::ofstream trace("seis_traces_asc.dat");
         OutputPostSimSummary(model, run.total, mission.OutputDir, std::cout, trace);
-        if (mission.ErrorBatches || mission.JobErrorBatches)
-          OutputSeismometerErrors(model, run.energy_se.data(), run.counts_se.data(),
-                                  mission.ErrorBatches ? mission.ErrorBatches : mission.JobErrorBatches, mission.OutputDir);
-        if (mission.bLapse) {
-          r3dh_lapse_result res{};
-          res.size = sizeof res, res.n_batches = mission.ErrorBatches;
-          res.distances = run.lapse_distances.data(), res.bins = run.lapse_bins.data(), res.clipped = run.lapse_clipped.data();
-          res.window_energy = run.lapse_energy.data(), res.window_se = run.lapse_se.data();
-          res.window_counts = run.lapse_counts.data(), res.batch_window_energy = run.lapse_batch_energy.data();
-          const std::string fn = (mission.OutputDir.empty() ? std::string() : mission.OutputDir + "/") + "lapse.octv";
-          std::ofstream f(fn.c_str());
-          OutputLapse(model, run.lapse, res, f);
-          if (!f) throw Runtime("cannot write " + fn);
-        }
-        if (mission.bTTImage) {
-          const std::string fn = (mission.OutputDir.empty() ? std::string() : mission.OutputDir + "/") + "ttimage.octv";
-          std::ofstream f(fn.c_str());
-          OutputTTImage(model, run.tt, run.tt_res, f);
-          if (!f) throw Runtime("cannot write " + fn);
-        }
+        write_batch_outputs(batch, model, run.batch);
       }
     }
   } catch (std::exception& e) {

@@ -64,7 +64,7 @@ def run_do_script(ref, work, script, edit=None):
 
 def user_lib(ref, tmp):
     out = os.path.join(tmp, "libr3d_host_user.so")
-    srcs = [f for f in glob.glob(os.path.join(HOST, "*.cpp")) if os.path.basename(f) not in ("main.cpp", "scatter_out.cpp")]   # (the two of ./main)
+    srcs = [f for f in glob.glob(os.path.join(HOST, "*.cpp")) if os.path.basename(f) not in ("main.cpp", "scatter_out.cpp", "batch_out.cpp")]   # (the three of ./main)
     # user.cpp says #include "grid.hpp": feed it on stdin so that the quote-include resolves through -I to
     # THIS repository's grid.hpp, and the user_*_inc.cpp files through the second -I to the checkout
     cmd = ["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-pthread", "-I", HOST, "-I", ref,

@@ -252,3 +252,42 @@ def test_cli_error_batches_end_to_end(tmp_path):
         assert (err["TracePS_se"] <= eb[:, 3:5] * (1 + 1e-5) + 1e-300).all(), name
         some_error += int((err["TracePS_se"] > 0).sum())
     assert some_error > 100
+
+
+# (the options beyond --error-batches / --job-error-batches, the Batches line, the one file beside the seis files)
+CLI_KINDS = {"errors": (["--error-batches=4"], "|  Batches: 4 (standard errors from batch means)", None),
+             "lapse": (["--error-batches=4", "--lapse-windows", "--lapse-array=48,95"],
+                       "|  Batches: 4 (standard errors from batch means)", "lapse.octv"),
+             "image": (["--error-batches=4", "--ttimage", "--ttimage-array=48,95", "--ttimage-fit=4,48"],
+                       "|  Batches: 4 (standard errors from batch means)", "ttimage.octv"),
+             "job": (["--devices=0,0", "--job-error-batches=4"], "|  Batches: 4 over 2 shards", None)}
+
+
+@pytest.mark.parametrize("kind", list(CLI_KINDS))
+def test_cli_every_batched_kind_says_its_line_once_and_writes_its_files_and_no_other(tmp_path, kind):
+    """The four kinds of the batched-run stage (host/batch_out.cpp) through ./main: where the Batches line stands, which
+    files there are, which receivers and how many batches they name.  An array that starts at neither end of the model
+    is the smallest input at which spreading it and taking it back out can go wrong; the values are the business of the
+    end-to-end tests of each kind."""
+    extra, line, own = CLI_KINDS[kind]
+    out = tmp_path / "out"
+    out.mkdir()
+    r = subprocess.run([main_exe()] + halfspace(3) + ["--num-phonons=20K", "--seed=77", f"--output-dir={out}"] + extra,
+                       cwd=tmp_path, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = r.stdout.split("\n")
+    at = [i for i, ln in enumerate(lines) if ln.startswith("|  Batches: ")]
+    assert len(at) == 1 and lines[at[0]] == line, [lines[i] for i in at]
+    assert lines[at[0] + 1].startswith("|  Shards: "), lines[at[0] + 1]
+    assert lines.index("@@ __BEGINNING_SIMULATION__") < at[0]
+    want = {f"seis_{s:03d}.octv" for s in range(144)} | {f"seis_{s:03d}_err.octv" for s in range(144)} | ({own} if own else set())
+    assert {p.name for p in out.iterdir()} == want
+    for s in (0, 48, 143):
+        assert read_octave(out / f"seis_{s:03d}_err.octv")["NumBatches"] == 4
+    if kind == "lapse":
+        got = read_octave(out / "lapse.octv")
+        assert (got["LapseSeismometers"][:, 0] == np.arange(48, 96)).all() and got["LapseBatches"] == 4
+    if kind == "image":
+        got = read_octave(out / "ttimage.octv")
+        assert (got["TTSeismometers"][:, 0] == np.arange(48, 96)).all() and got["TTBatches"] == 4
+        assert got["TTFitRange"].tolist() == [[4, 48]]
