@@ -5,6 +5,7 @@
 #   make engine     radiative3d_amd/lib/libr3d_hip.so    (hipcc, gfx950)
 #   make oracle     oracle/libr3d_oracle.so              (g++; test infrastructure)
 #   make cli        ./main                               (g++; the reference's command-line surface)
+#   make devtest    tests/emul/libr3d_physics_device{,_repro}.so  (hipcc, gfx950; test infrastructure)
 #
 # `make -q` succeeding is what scripts/do-fundamentals.sh (reference :145-152)
 # checks before a run.
@@ -52,7 +53,7 @@ addon_hdr = $(wildcard radiative3d_amd/$(1)/*.h) $(COMMON)/r3d_entry.h include/r
 OBJDIR   := build/obj
 
 # (the default goal is the first target of the file: it has to come before the generated object rules)
-.PHONY: default all host engine repro oracle cli clean
+.PHONY: default all host engine repro oracle cli devtest clean
 default: all
 # addon_object(tag, extra flags, add-on): its object in one engine build
 define addon_object
@@ -87,7 +88,7 @@ engine_objs = $(foreach a,$(ADDONS),$(OBJDIR)/$(1)_$(a).o) $(OBJDIR)/$(1)_engine
 $(eval $(call engine_objects,main,))
 $(eval $(call engine_objects,repro,-DR3D_REPRODUCIBLE -ffp-contract=off))
 
-all: host engine repro oracle cli
+all: host engine repro oracle cli devtest
 
 host: $(LIBDIR)/libr3d_host.so
 engine: $(LIBDIR)/libr3d_hip.so
@@ -130,8 +131,19 @@ oracle/libr3d_oracle.so: oracle/r3d_oracle.cpp oracle/philox.h include/r3d.h
 oracle/libr3d_tables_oracle.so: oracle/r3d_tables_oracle.cpp
 	$(CXX) -std=c++17 -O2 -ffp-contract=off -fPIC -Wall -shared -o $@ oracle/r3d_tables_oracle.cpp
 
+# The per-lane physics case by case on the device (tests/test_physics_device.py): ONE test-only unit outside csrc/,
+# which includes the engine's headers and tests/emul/physics_cases.h, compiled with the engine's flags and with the
+# reproducible build's -- sibling compilations of the same text, not the traversal kernels' code objects.
+DEVTEST_SRC := tests/emul/physics_device.hip
+DEVTEST_HDR := tests/emul/physics_cases.h $(ENGINE_HDR)
+devtest: tests/emul/libr3d_physics_device.so tests/emul/libr3d_physics_device_repro.so
+tests/emul/libr3d_physics_device.so: $(DEVTEST_SRC) $(DEVTEST_HDR)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(DEVTEST_SRC)
+tests/emul/libr3d_physics_device_repro.so: $(DEVTEST_SRC) $(DEVTEST_HDR)
+	$(HIPCC) $(HIPFLAGS) -DR3D_REPRODUCIBLE -ffp-contract=off -shared -o $@ $(DEVTEST_SRC)
+
 clean:
-	rm -f $(LIBDIR)/*.so oracle/*.so main
+	rm -f $(LIBDIR)/*.so oracle/*.so tests/emul/libr3d_physics_device*.so main
 	rm -rf $(OBJDIR)
 
 # Developer variants of the engine (timing-only / diagnostic builds, never shipped as libr3d_hip.so;

@@ -151,390 +151,67 @@ extern "C" void r3d_emul_sample_cdf(const double* cdf, uint64_t n, uint32_t bits
   }
 }
 
-// ---- the tetra move's two searches side by side (tests/test_face_filter.py) ------------------------------
-// Random tetrahedra with a linear velocity, a start and a direction per case; the local form
-// (tet_fast_exit) and the reference's construction (tet_arc / tet_exit / tet_exit_length) both run.  Where
-// the local form CERTIFIES its answer the two must agree: same face, same arc length.  mode:
-//   0 interior starts, any direction          1 starts on a face (to rounding, either side), moving in
-//   2 starts on / near an edge or a vertex    3 directions aimed at an edge or a vertex (ties)
-//   4 starts outside a face by 1e-17 .. 1e-7 R, moving in or out (retrograde micro-steps)
-//   5 sliver cells (faces meeting at shallow angles)   6 arcs tangent to a face (strong gradients)
-//   7 strongly graded cells 1e3 .. 1e5 from the origin, starts on a face moving in
-// out[0] cases, out[1] certified, out[2] certified and face differs, out[3] certified, same face, arc
-// lengths differ by more than tol * R, out[4] the reference gave no exit (len = inf) among the certified, out[5]
-// (with an oracle) certified cases on which the engine's sine-space search and the oracle's differ;
-// dev[0] largest |len_local - len_ref| / R among the certified, dev[1] the same / max(len, 1e-300).
+// ---- the case families of the per-lane physics beside the oracle (tests/emul/physics_cases.h) -------------------
+// Each family is three steps: GENERATE a table of cases (host), EVALUATE the engine's code row by row (the same R3D_HD
+// function a kernel of tests/emul/physics_device.hip calls per lane), COMPARE the output table with the oracle's
+// callbacks.  The five r3d_emul_* entries below run the three steps on the host, a block of rows at a time (the stream
+// and the counters carry over from block to block); the r3d_cases_* entries after them are the steps one by one, for a
+// caller that evaluates a table elsewhere (tests/test_physics_device.py: on the device).
+#include "physics_cases.h"
+using namespace r3d_cases;
 namespace {
-struct SplitMix {
-  uint64_t s;
-  uint64_t next() {
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-  }
-  double u() { return (double)(next() >> 11) * (1.0 / 9007199254740992.0); }   // [0, 1)
-  double sym() { return 2.0 * u() - 1.0; }
-  double logu(double lo, double hi) { return lo * std::pow(hi / lo, u()); }
-};
-static V3 rnd_unit(SplitMix& g) {
-  for (;;) {
-    V3 v = v3(g.sym(), g.sym(), g.sym());
-    const double m = mag2(v);
-    if (m > 1e-4 && m <= 1.0) return (1.0 / std::sqrt(m)) * v;
+constexpr uint64_t kBlockRows = 1u << 14;
+template <bool FLAT>
+void eval_host(int family, const double* in, double* out, uint64_t n) {
+  for (uint64_t i = 0; i < n; i++) eval_row<FLAT>(family, in, out, i);
+}
+void eval_host(int family, bool flat, const double* in, double* out, uint64_t n) {
+  if (flat) eval_host<true>(family, in, out, n);
+  else eval_host<false>(family, in, out, n);
+}
+// generate -> evaluate -> compare over n cases in blocks: gen(rows, count), cmp(in, out, count, base)
+template <class Gen, class Cmp>
+void run_family(int family, bool flat, uint64_t n, Gen gen, Cmp cmp) {
+  std::vector<double> in(kBlockRows * in_width(family)), out(kBlockRows * out_width(family));
+  for (uint64_t base = 0; base < n; base += kBlockRows) {
+    const uint64_t m = std::min<uint64_t>(kBlockRows, n - base);
+    gen(in.data(), m);
+    eval_host(family, flat, in.data(), out.data(), m);
+    cmp(in.data(), out.data(), m, base);
   }
 }
 }  // namespace
-typedef int (*tet_search_fn)(const double normals[12], const double points[12], const double g[3], double v0,
-                             const double loc[3], const double dir[3], double* len);
+
+// The tetra move's two searches side by side (tests/test_face_filter.py): the local form (tet_fast_exit) and the
+// reference's construction (tet_arc / tet_exit / tet_exit_length) both run; modes, counters and deviations: physics_cases.h
+// gen_tet / cmp_tet.  oracle: oracle/r3d_oracle.cpp r3d_oracle_tet_search, or null.
 extern "C" void r3d_emul_face_filter(int mode, uint64_t n, uint64_t seed, double tol, uint64_t* out, double* dev,
-                                     double* first_bad /* 16 doubles or null */,
-                                     tet_search_fn oracle /* oracle/r3d_oracle.cpp r3d_oracle_tet_search, or null */) {
-  SplitMix g{seed * 0x2545F4914F6CDD1Dull + (uint64_t)mode};
+                                     double* first_bad /* 16 doubles or null */, tet_search_fn oracle) {
+  SplitMix g = tet_stream(mode, seed);
   for (int i = 0; i < 6; i++) out[i] = 0;
   dev[0] = dev[1] = 0.0;
-  for (uint64_t it = 0; it < n; it++) {
-    // the cell: four corners in a box of edge ~10; slivers: the fourth corner close to the others' plane
-    V3 x[4];
-    for (;;) {
-      for (int k = 0; k < 4; k++) x[k] = v3(10 * g.u(), 10 * g.u(), 10 * g.u());
-      if (mode == 7) {   // a cell far from the origin (strongly graded: the arc's radius is much less than |loc|)
-        const V3 off = g.logu(1e3, 1e5) * rnd_unit(g);
-        for (int k = 0; k < 4; k++) x[k] = x[k] + off;
-      }
-      if (mode == 5) {
-        const V3 nn = unit(cross(x[1] - x[0], x[2] - x[0]));
-        const V3 c3 = (1.0 / 3.0) * (x[0] + x[1] + x[2]);
-        x[3] = c3 + g.logu(1e-4, 1e-1) * nn + 3.0 * (g.sym() * unit(x[1] - x[0]) + g.sym() * unit(x[2] - x[0]));
-      }
-      const double vol6 = std::fabs(dot(cross(x[1] - x[0], x[2] - x[0]), x[3] - x[0]));
-      if (vol6 > (mode == 5 ? 1e-6 : 1.0)) break;
-    }
-    CellTet c;
-    std::memset(&c, 0, sizeof c);
-    double points[12];
-    for (int f = 0; f < 4; f++) {   // face f: opposite corner f, normal pointing away from it
-      const V3 a = x[(f + 1) & 3], b = x[(f + 2) & 3], d = x[(f + 3) & 3];
-      V3 nn = unit(cross(b - a, d - a));
-      if (dot(nn, x[f] - a) > 0) nn = -nn;
-      c.n[f][0] = nn.x, c.n[f][1] = nn.y, c.n[f][2] = nn.z;
-      c.d[f] = dot(nn, a);
-      points[3 * f] = a.x, points[3 * f + 1] = a.y, points[3 * f + 2] = a.z;
-    }
-    const V3 centre = 0.25 * (x[0] + x[1] + x[2] + x[3]);
-    // velocity: 5 at the centre, gradient of any direction; arc radius from ~the cell's size to 1e5 of it
-    const V3 gd = rnd_unit(g);
-    const double gm = (mode == 6 || mode == 7) ? 5.0 / g.logu(12.0, 60.0) : 5.0 / g.logu(20.0, 1e6);   // (velocity > 0 throughout the cell)
-    c.g[0] = gm * gd.x, c.g[1] = gm * gd.y, c.g[2] = gm * gd.z;
-    c.v0 = 5.0 - dot(v3(c.g), centre);
-    c.inv_gmag = 1.0 / gm;
-    c.att = -0.01;
-    Phonon p;
-    std::memset(&p, 0, sizeof p);
-    p.pc = 1.0, p.type = 0;
-    // start
-    double w[4];
-    double sum = 0;
-    for (int k = 0; k < 4; k++) sum += (w[k] = -std::log(1.0 - g.u()));
-    for (int k = 0; k < 4; k++) w[k] /= sum;
-    const int f0 = (int)(g.next() & 3), f1 = (f0 + 1 + (int)(g.next() % 3)) & 3;
-    if (mode == 1 || mode == 4 || mode == 7) w[f0] = 0;        // on face f0 (corner f0 has no weight)
-    if (mode == 2) {
-      w[f0] = 0, w[f1] = (g.u() < 0.5) ? 0.0 : g.logu(1e-16, 1e-6);   // on / near the edge shared by f0 and f1
-      if (g.u() < 0.3) w[(f1 + 1) & 3 == f0 ? (f1 + 2) & 3 : (f1 + 1) & 3] = g.logu(1e-16, 1e-6);   // near a vertex
-    }
-    sum = w[0] + w[1] + w[2] + w[3];
-    p.loc = v3(0, 0, 0);
-    for (int k = 0; k < 4; k++) p.loc = p.loc + (w[k] / sum) * x[k];
-    p.dir = rnd_unit(g);
-    const V3 nf0 = v3(c.n[f0]);
-    if (mode == 1 || mode == 2 || mode == 7) {   // moving in through f0 (any angle, grazing included)
-      if (dot(nf0, p.dir) > 0) p.dir = p.dir - (2.0 * dot(nf0, p.dir)) * nf0;
-      if (g.u() < 0.2) {             // grazing: mostly along the face
-        V3 tang = unit(cross(nf0, rnd_unit(g)));
-        p.dir = unit(tang + (-g.logu(1e-9, 1e-1)) * nf0);
-      }
-      if (mode == 1 && g.u() < 0.5) p.loc = p.loc + (g.sym() * g.logu(1e-17, 1e-12) * 10.0) * nf0;   // rounding, either side
-    }
-    if (mode == 3) {   // aimed at a point of an edge or at a vertex, from inside
-      V3 target = x[f0];
-      if (g.u() < 0.7) {
-        const double s = g.u();
-        target = s * x[f0] + (1 - s) * x[f1];
-      }
-      if (g.u() < 0.5) target = target + (g.logu(1e-14, 1e-4)) * rnd_unit(g);
-      p.dir = unit(target - p.loc);   // (a straight aim: the arc misses by its sagitta, which varies with the gradient)
-    }
-    if (mode == 4) {   // outside f0 by a hair (or more), moving in or out
-      const double R_guess = 5.0 / gm;
-      p.loc = p.loc + (g.logu(1e-17, 1e-7) * R_guess) * nf0;
-      if (g.u() < 0.5 && dot(nf0, p.dir) > 0) p.dir = p.dir - (2.0 * dot(nf0, p.dir)) * nf0;
-    }
-    if (mode == 6) {   // a direction nearly parallel to face f1, so that the arc bends to or away from it
-      V3 tang = unit(cross(v3(c.n[f1]), rnd_unit(g)));
-      p.dir = unit(tang + (g.sym() * g.logu(1e-6, 3e-1)) * v3(c.n[f1]));
-    }
-    out[0]++;
-    TetLocal L;
-    const TetFast F = tet_fast_exit(c, p, L);
-    if (!F.ok) continue;
-    out[1]++;
-    const double len_loc = L.R * two_atan(F.t, F.sn, F.cs);
-    const TetArc A = tet_arc(c, p);
-    const TetExit E = tet_exit(c, A);
-    double len_ref = tet_exit_length(A, E);
-    int face_ref = E.face;
-    bool bad = false;
-    if (oracle) {   // the reference's construction as the ORACLE has it (angles, acos, atan2): it must say the same
-      const double loc[3] = {p.loc.x, p.loc.y, p.loc.z}, dir[3] = {p.dir.x, p.dir.y, p.dir.z};
-      double len_o = 0;
-      const int face_o = oracle(&c.n[0][0], points, c.g, c.v0, loc, dir, &len_o);
-      if (face_o != face_ref || !(std::fabs(len_o - len_ref) <= tol * L.R)) out[5]++;   // (engine's sine-space search vs oracle)
-      face_ref = face_o, len_ref = len_o;
-    }
-    if (!(len_ref < pos_inf())) out[4]++, bad = true;
-    else if (face_ref != F.face) out[2]++, bad = true;
-    else {
-      const double d = std::fabs(len_loc - len_ref);
-      if (!(d <= tol * L.R)) out[3]++, bad = true;
-      if (d / L.R > dev[0]) dev[0] = d / L.R;
-      if (d / std::fmax(std::fabs(len_ref), 1e-300) > dev[1]) dev[1] = d / std::fmax(std::fabs(len_ref), 1e-300);
-    }
-    static int want_kind = getenv("R3D_FF_KIND") ? atoi(getenv("R3D_FF_KIND")) : 0;   // debugging: which kind of mismatch to record
-    const bool rec = want_kind == 0 ? (out[2] + out[3] + out[4] == 1) : (want_kind == 4 ? (!(len_ref < pos_inf()) && out[4] == 1) : (want_kind == 2 ? (face_ref != F.face && out[2] == 1) : false));
-    if (bad && first_bad && rec) {
-      first_bad[0] = (double)it, first_bad[1] = F.face, first_bad[2] = face_ref, first_bad[3] = len_loc, first_bad[4] = len_ref;
-      first_bad[5] = L.R, first_bad[6] = F.t;
-      for (int f = 0; f < 4; f++) first_bad[7 + f] = c.d[f] - dot(v3(c.n[f]), p.loc);
-      for (int f = 0; f < 4; f++) first_bad[11 + f] = dot(v3(c.n[f]), p.dir);
-    }
-  }
+  run_family(FAM_TET, false, n, [&](double* rows, uint64_t m) { gen_tet(g, mode, m, rows); },
+             [&](const double* in, const double* res, uint64_t m, uint64_t base) { cmp_tet(in, res, m, base, tol, out, dev, first_bad, oracle); });
 }
-
-// ---- the shell move's two searches side by side (tests/test_face_filter.py) -------------------------------
-// Random shells v = a r^2 + c (a < 0, velocity 3 .. 9 growing 0.1 .. 30 % from top to bottom, top radius 1000 .. 6371,
-// thickness 5 .. 2000) about the origin; the local form (sph_fast_exit) and the reference's construction
-// (sph_arc / sph_exit) both run; where the local form certifies they must agree.  mode:
-//   0 interior starts, any direction        1 on the top face (to rounding, either side), moving in
-//   2 on the bottom face, moving in (up)    3 near the bottom, nearly horizontal (arcs tangent to the bottom face)
-//   4 outside either face by 1e-17 .. 1e-7 of the radius, moving in or out
-//   5 nearly vertical rays                  6 thin shells with strong gradients (legs of many degrees)
-// out[] / dev[] as r3d_emul_face_filter.
-typedef int (*shell_search_fn)(double a, double c0, double r_top, double r_bottom, const double loc[3], const double dir[3], double* len);
+// The shell move's two searches (sph_fast_exit; sph_arc / sph_exit): gen_shell / cmp_shell.
 extern "C" void r3d_emul_shell_filter(int mode, uint64_t n, uint64_t seed, double tol, uint64_t* out, double* dev,
                                       double* first_bad, shell_search_fn oracle) {
-  SplitMix g{seed * 0x9E3779B97F4A7C15ull + 77u + (uint64_t)mode};
+  SplitMix g = shell_stream(mode, seed);
   for (int i = 0; i < 6; i++) out[i] = 0;
   dev[0] = dev[1] = 0.0;
-  for (uint64_t it = 0; it < n; it++) {
-    const double rt = 1000.0 + 5371.0 * g.u();
-    const double thick = (mode == 6) ? g.logu(2.0, 60.0) : std::fmin(g.logu(5.0, 2000.0), 0.8 * rt);
-    const double rb = rt - thick;
-    const double vt = 3.0 + 6.0 * g.u();
-    const double vb = vt * (1.0 + ((mode == 6) ? g.logu(0.05, 0.6) : g.logu(1e-3, 0.3)));
-    CellSph c;
-    std::memset(&c, 0, sizeof c);
-    c.a = (vt - vb) / (rt * rt - rb * rb);
-    c.c = vt - c.a * rt * rt;
-    c.zero_rad2 = -c.c / c.a;
-    c.att = -0.01;
-    c.radius[0] = rt, c.radius[1] = -rb;
-    Phonon p;
-    std::memset(&p, 0, sizeof p);
-    p.pc = 1.0;
-    const V3 up = rnd_unit(g);
-    double r = rb + thick * g.u();
-    if (mode == 1) r = rt;
-    if (mode == 2) r = rb;
-    if (mode == 3) r = rb + thick * g.logu(1e-12, 1e-2);
-    if (mode == 4) r = (g.u() < 0.5) ? rt * (1.0 + g.logu(1e-17, 1e-7)) : rb * (1.0 - g.logu(1e-17, 1e-7));
-    p.loc = r * up;
-    if ((mode == 1 || mode == 2) && g.u() < 0.5) p.loc = (1.0 + g.sym() * g.logu(1e-17, 1e-13)) * p.loc;
-    p.dir = rnd_unit(g);
-    const double vert = dot(p.dir, up);
-    if (mode == 1 && vert > 0) p.dir = p.dir - (2.0 * vert) * up;      // down into the shell
-    if (mode == 2 && vert < 0) p.dir = p.dir - (2.0 * vert) * up;      // up into the shell
-    if ((mode == 1 || mode == 2) && g.u() < 0.2) {                     // grazing entries
-      const V3 tang = unit(cross(up, rnd_unit(g)));
-      p.dir = unit(tang + ((mode == 1 ? -1.0 : 1.0) * g.logu(1e-9, 1e-1)) * up);
-    }
-    if (mode == 3) {
-      const V3 tang = unit(cross(up, rnd_unit(g)));
-      p.dir = unit(tang + (g.sym() * g.logu(1e-8, 2e-1)) * up);
-    }
-    if (mode == 4 && g.u() < 0.5) {   // moving in
-      const double vv = dot(p.dir, up);
-      if ((r > rt) == (vv > 0)) p.dir = p.dir - (2.0 * vv) * up;
-    }
-    if (mode == 5) {
-      const V3 tang = unit(cross(up, rnd_unit(g)));
-      p.dir = unit((g.u() < 0.5 ? 1.0 : -1.0) * up + g.logu(1e-12, 1e-2) * tang);
-    }
-    out[0]++;
-    TetLocal L;
-    const SphFast F = sph_fast_exit(c, v3(0, 0, 0), p, L);
-    if (!F.ok) continue;
-    out[1]++;
-    const double len_loc = L.R * two_atan(F.t, F.sn, F.cs);
-    const SphArc A = sph_arc(c, v3(0, 0, 0), p);
-    const SphExit E = sph_exit(c, A, p);
-    double len_ref = E.len;
-    int face_ref = E.face;
-    bool bad = false;
-    if (oracle) {
-      const double loc[3] = {p.loc.x, p.loc.y, p.loc.z}, dir[3] = {p.dir.x, p.dir.y, p.dir.z};
-      double len_o = 0;
-      const int face_o = oracle(c.a, c.c, rt, rb, loc, dir, &len_o);
-      if (face_o != face_ref || !(std::fabs(len_o - len_ref) <= tol * L.R)) out[5]++;
-      face_ref = face_o, len_ref = len_o;
-    }
-    if (!(len_ref < pos_inf())) out[4]++, bad = true;
-    else if (face_ref != F.face) out[2]++, bad = true;
-    else {
-      const double d = std::fabs(len_loc - len_ref);
-      if (!(d <= tol * L.R)) out[3]++, bad = true;
-      if (d / L.R > dev[0]) dev[0] = d / L.R;
-      if (d / std::fmax(std::fabs(len_ref), 1e-300) > dev[1]) dev[1] = d / std::fmax(std::fabs(len_ref), 1e-300);
-    }
-    if (bad && first_bad && out[2] + out[3] + out[4] == 1) {
-      first_bad[0] = (double)it, first_bad[1] = F.face, first_bad[2] = face_ref, first_bad[3] = len_loc, first_bad[4] = len_ref;
-      first_bad[5] = L.R, first_bad[6] = F.t, first_bad[7] = rt, first_bad[8] = rb, first_bad[9] = r, first_bad[10] = dot(p.dir, up);
-      first_bad[11] = c.a, first_bad[12] = c.c;
-    }
-  }
+  run_family(FAM_SHELL, false, n, [&](double* rows, uint64_t m) { gen_shell(g, mode, m, rows); },
+             [&](const double* in, const double* res, uint64_t m, uint64_t base) { cmp_shell(in, res, m, base, tol, out, dev, first_bad, oracle); });
 }
-
-// ---- the reflection / transmission event on random bare interfaces: the engine's slowness-form solve (r3d_physics.h
-//      rt_choose / rt_apply) beside the oracle's restatement of RTCoef (oracle/r3d_oracle.cpp r3d_oracle_rt_event),
-//      the same interface, phonon and uniforms for both.
-// mode: 0 solid on solid, moderate contrasts; 1 free surface; 2 incidence within 1e-12 .. 1e-2 of a critical angle of one
-//       of the outgoing rays; 3 grazing incidence, cos(i) = 1e-6 .. 1e-2; 4 nearly identical media; 5 a fluid (beta = 0)
-//       on either side: the reference's default outcome; 6 contrasts up to 1e3; 7 near-normal incidence, sin(i) = 1e-9 ..
-//       1e-3; 8 along the normal exactly (the reference's substitute axis, geom_r3.cpp:146-171); 9 HORIZONTAL faces, normal
-//       (0, 0, +-1), through the layered models' flat-face form (rt_choose<true> / rt_apply<true>), vertical rays included
-// Two places where the REFERENCE's formulation is the ill-conditioned side, and the comparison allows what it loses:
-//   * it takes cos(i) as sqrt(1 - sin(i)^2), good to 1.1e-16 / cos(i) (absolutely), where the engine has n.d itself: the
-//     weights (which carry cos(i)) then differ by 1e-16 / cos(i)^2 of themselves, the reflected direction by 1e-16 / cos(i);
-//   * its axis normal to the plane of incidence is unit(n x d), good to 1e-16 / sin(i): so is the SH fraction an S ray's
-//     polarisation draw is compared with, and the outgoing polarisation.
-// out[0] cases, [1] outcomes that differ (type or side), [2] of those: with both draws further than the margin from their
-//       thresholds, [3] directions off by more than the tolerance, [4] polarisations off by more than the tolerance,
-//       [5] transmitted, [6] outgoing S rays, [7] incident S rays counted as SH
-// dev[0] largest direction error, dev[1] largest polarisation error (radians) x sin(theta) of the outgoing ray, over the
-//       cases with equal outcome
-typedef void (*rt_event_fn)(const double media[6], int has_neighbor, const double normal[3], double theta, double phi,
-                            double pol, int type, double u_pol, double u_out, double out[8]);
+// The reflection / transmission event on random bare interfaces: the engine's slowness-form solve (r3d_physics.h
+// rt_choose / rt_apply; mode 9 through the flat-face form) beside the oracle's restatement of RTCoef
+// (oracle/r3d_oracle.cpp r3d_oracle_rt_event), the same interface, phonon and uniforms for both: gen_rt / cmp_rt.
 extern "C" void r3d_emul_rt_events(int mode, uint64_t n, uint64_t seed, double tol, double margin, uint64_t* out,
                                    double* dev, double* first_bad /* 16 doubles or null */, rt_event_fn oracle) {
-  SplitMix g{seed * 0x2545F4914F6CDD1Dull + 977u * (uint64_t)mode};
+  SplitMix g = rt_stream(mode, seed);
   for (int i = 0; i < 8; i++) out[i] = 0;
   dev[0] = dev[1] = 0.0;
-  for (uint64_t it = 0; it < n; it++) {
-    double media[6];
-    int has_nbr = 1;
-    auto medium = [&](double* m) {
-      m[1] = 1.5 + 11.5 * g.u();              // alpha
-      m[2] = m[1] / (1.45 + 0.7 * g.u());     // beta
-      m[0] = 1.0 + 5.0 * g.u();               // rho
-    };
-    medium(media), medium(media + 3);
-    if (mode == 1) has_nbr = 0;
-    if (mode == 4) {
-      const double e = g.logu(1e-10, 1e-2);
-      for (int k = 0; k < 3; k++) media[3 + k] = media[k] * (1.0 + e * g.sym());
-    }
-    if (mode == 5) {
-      if (g.u() < 0.5) media[5] = 0.0;
-      else media[2] = 0.0;
-    }
-    if (mode == 6) {
-      const double f = g.logu(1.0, 1e3);
-      const bool up = g.u() < 0.5;
-      for (int k = 0; k < 3; k++) media[3 + k] = up ? media[k] * f * (0.5 + g.u()) : media[k] / f * (0.5 + g.u());
-    }
-    int type = g.u() < 0.5 ? RAY_P : RAY_S;
-    if (mode == 5 && media[2] == 0.0) type = RAY_P;   // (no S ray travels in a fluid)
-    // (mode 8: +z is the one normal whose (theta, phi) give the unit vector back exactly)
-    const V3 nrm = mode == 8 ? v3(0, 0, 1) : mode == 9 ? v3(0, 0, g.u() < 0.5 ? 1.0 : -1.0) : rnd_unit(g);
-    // incidence: the sine of the angle to the normal
-    double sini = std::sqrt(g.u());
-    if (mode == 2) {
-      // a critical angle of one of the other rays: v_k sin(i) / v_in = 1
-      const double v_in = media[type == RAY_P ? 1 : 2];
-      double vk[4] = {media[1], media[2], media[4], media[5]};
-      double s_crit = 2.0;
-      for (int tries = 0; tries < 8 && !(s_crit < 1.0); tries++) s_crit = v_in / vk[(int)(4 * g.u()) & 3];
-      if (s_crit < 1.0) sini = s_crit * (1.0 + g.logu(1e-12, 1e-2) * (g.u() < 0.5 ? 1.0 : -1.0));
-      if (!(sini < 1.0)) sini = s_crit;
-    }
-    if (mode == 3) sini = std::sqrt(1.0 - std::pow(g.logu(1e-6, 1e-2), 2));   // grazing
-    if (mode == 7) sini = g.logu(1e-9, 1e-3);                                  // near normal
-    if (mode == 8) sini = 0.0;                                                 // along the normal exactly
-    if (mode == 9 && g.u() < 0.05) sini = 0.0;
-    // a direction with that incidence: normal cos(i) + tangent sin(i)
-    V3 tng = cross(nrm, rnd_unit(g));
-    while (mag2(tng) < 1e-6) tng = cross(nrm, rnd_unit(g));
-    tng = (1.0 / std::sqrt(mag2(tng))) * tng;
-    V3 dir = std::sqrt(std::fmax(0.0, 1.0 - sini * sini)) * nrm + sini * tng;
-    if (mode == 8 || (mode == 9 && sini == 0.0)) dir = nrm;
-    // the reference's phonon carries (theta, phi): both sides start from the direction those angles give
-    const double theta = std::acos(std::fmax(-1.0, std::fmin(1.0, dir.z))), phi = std::atan2(dir.y, dir.x);
-    dir = v3(std::sin(theta) * std::cos(phi), std::sin(theta) * std::sin(phi), std::cos(theta));
-    if (!(dot(nrm, dir) > 0.0)) {   // (rounding turned a grazing ray away from the face: not an arrival)
-      it--;
-      continue;
-    }
-    const double pol = kPi * g.sym();
-    const double u_pol = 1.0 - g.u(), u_out = 1.0 - g.u();   // (0, 1]
-    Phonon p;
-    p.t = p.path = p.recent = p.lamp = 0.0, p.loc = v3(0, 0, 0), p.cell = 0, p.moves = 0;
-    p.dir = dir, p.pc = std::cos(pol), p.ps = std::sin(pol), p.type = type;
-    Iface f;
-    f.normal = nrm, f.has_neighbor = has_nbr != 0;
-    f.rhoR = media[0], f.vR[0] = media[1], f.vR[1] = media[2];
-    f.rhoT = media[3], f.vT[0] = media[4], f.vT[1] = media[5];
-    const RtChoice ch = mode == 9 ? rt_choose<true>(p, f, u_pol, u_out) : rt_choose<false>(p, f, u_pol, u_out);
-    const bool crossed = mode == 9 ? rt_apply<true>(p, f.normal, ch) : rt_apply<false>(p, f.normal, ch);
-    double o[8];
-    const double nn[3] = {nrm.x, nrm.y, nrm.z};
-    oracle(media, has_nbr, nn, theta, phi, pol, type, u_pol, u_out, o);
-    out[0]++;
-    out[5] += crossed ? 1 : 0, out[6] += p.type == RAY_S ? 1 : 0, out[7] += (ch.code & 4) ? 1 : 0;
-    bool bad = false;
-    // what the reference's own formulation is good to at this incidence (above)
-    const double ci = dot(nrm, dir), si = std::sqrt(mag2(cross(nrm, dir)));
-    const double lost_w = 4e-16 / (ci * ci), lost_dir = 4e-16 / ci, lost_axis = si > 0 ? 4e-16 / si : 0.0;
-    if ((int)o[0] != p.type || (o[4] != 0.0) != crossed) {
-      out[1]++;
-      if (o[6] > margin + lost_w && o[7] > margin + lost_axis) out[2]++, bad = true;
-    } else if (((ch.code & 4) != 0) != ((int)o[5] == 2 || (int)o[5] == 5) && p.type == RAY_S && type == RAY_S &&
-               !(o[7] > margin + lost_axis)) {
-      // (the polarisation draw sat on its threshold and fell the other way: SH one side, SV the other -- same ray, the
-      //  particle motion a quarter turn apart; counted with the differing outcomes)
-      out[1]++;
-    } else {
-      const V3 od = v3(std::sin(o[1]) * std::cos(o[2]), std::sin(o[1]) * std::sin(o[2]), std::cos(o[1]));
-      const double dd = std::sqrt(mag2(p.dir - od));
-      if (!(dd <= tol + lost_dir)) out[3]++, bad = true;
-      if (dd > dev[0]) dev[0] = dd;
-      if (p.type == RAY_S) {
-        // (the polarisation angle is defined about the direction: both as unit vectors in the (theta^, phi^) plane)
-        const double dp = std::sqrt((p.pc - std::cos(o[3])) * (p.pc - std::cos(o[3])) + (p.ps - std::sin(o[3])) * (p.ps - std::sin(o[3])));
-        // a ray along the pole has no azimuth of its own: phi = atan2(0, 0) on one side, the limit on the other; near
-        // the pole the (theta^, phi^) frame turns by (error of the direction) / sin(theta)
-        const double st = std::sqrt(od.x * od.x + od.y * od.y);
-        if (st > 1e-6) {
-          if (!(dp <= tol + (lost_dir + lost_axis) / st)) out[4]++, bad = true;
-          if (dp * st > dev[1]) dev[1] = dp * st;
-        }
-      }
-    }
-    if (bad && first_bad && first_bad[4] == 0.0) {
-      first_bad[0] = (double)it, first_bad[1] = type, first_bad[2] = sini, first_bad[3] = has_nbr;
-      for (int k = 0; k < 6; k++) first_bad[4 + k] = media[k];
-      first_bad[10] = o[5], first_bad[11] = ch.code, first_bad[12] = o[6], first_bad[13] = u_out, first_bad[14] = u_pol, first_bad[15] = pol;
-    }
-  }
+  run_family(FAM_RT, mode == 9, n, [&](double* rows, uint64_t m) { gen_rt(g, mode, m, rows); },
+             [&](const double* in, const double* res, uint64_t m, uint64_t base) { cmp_rt(in, res, m, base, tol, margin, out, dev, first_bad, oracle); });
 }
 // rt_weights for one interface and incidence sine: w[0..5] the six weights, w[6] the squared determinant they carry
 extern "C" void r3d_emul_rt_weights(const double media[6], double sini, int intype, double* w) {
@@ -547,112 +224,73 @@ extern "C" void r3d_emul_rt_weights(const double media[6], double sini, int inty
   w[6] = det2;
 }
 
-// ---- the Snell bend without conversion on random bare faces: bend<FLAT_FACES> (r3d_physics.h) beside the oracle's
-//      restatement of Phonon::Refraction_Bend (oracle/r3d_oracle.cpp r3d_oracle_bend_event).
-// mode: 0 random faces, moderate velocity steps; 1 steps of 1e-5 .. 1e-3 (what the STEP class of a smooth model sees);
-//       2 within 1e-12 .. 1e-2 of total reflection (either side); 3 grazing and near-normal incidence; 4 HORIZONTAL faces
-//       through the layered models' flat-face form, vertical rays included
-// out[0] cases, [1] crossed / reflected differs, [2] of those: outgoing sine further than `margin` from 1, [3] directions
-//       off, [4] polarisations off, [5] crossed, [6] S rays;  dev[0] / dev[1]: largest direction / polarisation x sin(theta) error
-typedef void (*bend_event_fn)(const double normal[3], double theta, double phi, double pol, int type, double veli, double velo,
-                              double out[4]);
+// The Snell bend without conversion on random bare faces: bend<FLAT_FACES> (mode 4: the flat-face form) beside the
+// oracle's restatement of Phonon::Refraction_Bend (r3d_oracle_bend_event): gen_bend / cmp_bend.
 extern "C" void r3d_emul_bend_events(int mode, uint64_t n, uint64_t seed, double tol, double margin, uint64_t* out, double* dev,
                                      bend_event_fn oracle) {
-  SplitMix g{seed * 0x2545F4914F6CDD1Dull + 7919u * (uint64_t)mode};
+  SplitMix g = bend_stream(mode, seed);
   for (int i = 0; i < 8; i++) out[i] = 0;
   dev[0] = dev[1] = 0.0;
-  for (uint64_t it = 0; it < n; it++) {
-    const V3 nrm = mode == 4 ? v3(0, 0, g.u() < 0.5 ? 1.0 : -1.0) : rnd_unit(g);
-    const double veli = 1.5 + 7.0 * g.u();
-    double velo = veli * (0.6 + 0.9 * g.u());
-    if (mode == 1) velo = veli * (1.0 + g.logu(1e-5, 1e-3) * (g.u() < 0.5 ? 1.0 : -1.0));
-    double sini = std::sqrt(g.u());
-    if (mode == 2) {
-      velo = veli * (1.05 + g.u());
-      sini = (veli / velo) * (1.0 + g.logu(1e-12, 1e-2) * (g.u() < 0.5 ? 1.0 : -1.0));
-      if (!(sini < 1.0)) sini = veli / velo;
-    }
-    if (mode == 3) sini = g.u() < 0.5 ? std::sqrt(1.0 - std::pow(g.logu(1e-6, 1e-2), 2)) : g.logu(1e-9, 1e-3);
-    if (mode == 4 && g.u() < 0.05) sini = 0.0;
-    V3 tng = cross(nrm, rnd_unit(g));
-    while (mag2(tng) < 1e-6) tng = cross(nrm, rnd_unit(g));
-    tng = (1.0 / std::sqrt(mag2(tng))) * tng;
-    V3 dir = std::sqrt(std::fmax(0.0, 1.0 - sini * sini)) * nrm + sini * tng;
-    if (mode == 4 && sini == 0.0 && nrm.z > 0) dir = nrm;
-    const double theta = std::acos(std::fmax(-1.0, std::fmin(1.0, dir.z))), phi = std::atan2(dir.y, dir.x);
-    dir = v3(std::sin(theta) * std::cos(phi), std::sin(theta) * std::sin(phi), std::cos(theta));
-    if (!(dot(nrm, dir) > 0.0)) {
-      it--;
-      continue;
-    }
-    const int type = g.u() < 0.4 ? RAY_P : RAY_S;
-    const double pol = type == RAY_P ? 0.0 : kPi * g.sym();
-    Phonon p;
-    p.t = p.path = p.recent = p.lamp = 0.0, p.loc = v3(0, 0, 0), p.cell = 0, p.moves = 0;
-    p.dir = dir, p.pc = std::cos(pol), p.ps = std::sin(pol), p.type = type;
-    const bool crossed = mode == 4 ? bend<true>(p, nrm, veli, velo) : bend<false>(p, nrm, veli, velo);
-    double o[4];
-    const double nn[3] = {nrm.x, nrm.y, nrm.z};
-    oracle(nn, theta, phi, pol, type, veli, velo, o);
-    out[0]++, out[5] += crossed ? 1 : 0, out[6] += type == RAY_S ? 1 : 0;
-    const double ci = dot(nrm, dir), si = std::sqrt(mag2(cross(nrm, dir)));
-    const double sino = (velo / veli) * si;
-    // (the reference's cos(i) = sqrt(1 - sin^2) and its unit axis unit(n x d): good to 1e-16 / cos(i), 1e-16 / sin(i))
-    const double lost_dir = 4e-16 / std::fmax(ci, 1e-300) + (sino < 1.0 ? 4e-16 / std::sqrt(std::fmax(1.0 - sino * sino, 1e-300)) : 0.0);
-    const double lost_axis = si > 0 ? 4e-16 / si : 0.0;
-    if ((o[3] != 0.0) != crossed) {
-      out[1]++;
-      if (std::fabs(sino - 1.0) > margin) out[2]++;
-      continue;
-    }
-    const V3 od = v3(std::sin(o[0]) * std::cos(o[1]), std::sin(o[0]) * std::sin(o[1]), std::cos(o[0]));
-    const double dd = std::sqrt(mag2(p.dir - od));
-    if (!(dd <= tol + lost_dir)) out[3]++;
-    if (dd > dev[0]) dev[0] = dd;
-    if (type == RAY_S) {
-      const double dp = std::sqrt((p.pc - std::cos(o[2])) * (p.pc - std::cos(o[2])) + (p.ps - std::sin(o[2])) * (p.ps - std::sin(o[2])));
-      const double st = std::sqrt(od.x * od.x + od.y * od.y);
-      if (st > 1e-6) {
-        if (!(dp <= tol + (lost_dir + lost_axis) / st)) out[4]++;
-        if (dp * st > dev[1]) dev[1] = dp * st;
-      }
-    }
-  }
+  run_family(FAM_BEND, mode == 4, n, [&](double* rows, uint64_t m) { gen_bend(g, mode, m, rows); },
+             [&](const double* in, const double* res, uint64_t m, uint64_t) { cmp_bend(in, res, m, tol, margin, out, dev, oracle); });
 }
-
-// ---- the scattering's rotation: scatter_transform (r3d_physics.h) beside the oracle's Phonon::Transform
-//      (oracle/r3d_oracle.cpp r3d_oracle_transform), random phonons and deflections; mode 1: deflections within 1e-9 .. 1e-3
-//      of forward and backward, mode 2: phonons within 1e-9 .. 1e-3 of the poles (where theta^, phi^ turn fastest)
-// out[0] cases, [1] directions off, [2] polarisations off;  dev[0] / dev[1] largest direction / polarisation x sin(theta) error
-typedef void (*transform_fn)(double theta, double phi, double pol, double rth, double rph, double rpol, double out[3]);
+// The scattering's rotation: scatter_transform beside the oracle's Phonon::Transform (r3d_oracle_transform): gen_rot / cmp_rot.
 extern "C" void r3d_emul_transforms(int mode, uint64_t n, uint64_t seed, double tol, uint64_t* out, double* dev, transform_fn oracle) {
-  SplitMix g{seed * 0x2545F4914F6CDD1Dull + 104729u * (uint64_t)mode};
+  SplitMix g = rot_stream(mode, seed);
   out[0] = out[1] = out[2] = 0;
   dev[0] = dev[1] = 0.0;
-  for (uint64_t it = 0; it < n; it++) {
-    double theta = std::acos(g.sym()), phi = kPi * g.sym(), pol = kPi * g.sym();
-    double rth = std::acos(g.sym()), rph = kPi * g.sym(), rpol = g.u() < 0.5 ? 0.0 : kPi * g.sym();
-    if (mode == 1) rth = g.u() < 0.5 ? g.logu(1e-9, 1e-3) : kPi - g.logu(1e-9, 1e-3);
-    if (mode == 2) theta = g.u() < 0.5 ? g.logu(1e-9, 1e-3) : kPi - g.logu(1e-9, 1e-3);
-    Phonon p;
-    p.t = p.path = p.recent = p.lamp = 0.0, p.loc = v3(0, 0, 0), p.cell = 0, p.moves = 0, p.type = RAY_S;
-    p.dir = v3(std::sin(theta) * std::cos(phi), std::sin(theta) * std::sin(phi), std::cos(theta));
-    p.pc = std::cos(pol), p.ps = std::sin(pol);
-    const double dirn[4] = {std::cos(rth), std::cos(rph), std::sin(rph), std::sin(rth)};
-    scatter_transform(p, dirn, std::cos(rpol), std::sin(rpol), RAY_S);
-    double o[3];
-    oracle(theta, phi, pol, rth, rph, rpol, o);
-    out[0]++;
-    const V3 od = v3(std::sin(o[0]) * std::cos(o[1]), std::sin(o[0]) * std::sin(o[1]), std::cos(o[0]));
-    const double dd = std::sqrt(mag2(p.dir - od));
-    if (!(dd <= tol)) out[1]++;
-    if (dd > dev[0]) dev[0] = dd;
-    const double dp = std::sqrt((p.pc - std::cos(o[2])) * (p.pc - std::cos(o[2])) + (p.ps - std::sin(o[2])) * (p.ps - std::sin(o[2])));
-    const double st = std::sqrt(od.x * od.x + od.y * od.y);
-    if (st > 1e-6) {
-      // (both sides carry the polarisation as an angle about axes that turn by (direction error) / sin(theta) near a pole)
-      if (!(dp * st <= tol)) out[2]++;
-      if (dp * st > dev[1]) dev[1] = dp * st;
-    }
+  run_family(FAM_ROT, false, n, [&](double* rows, uint64_t m) { gen_rot(g, mode, m, rows); },
+             [&](const double* in, const double* res, uint64_t m, uint64_t) { cmp_rot(in, res, m, tol, out, dev, oracle); });
+}
+
+// ---- the three steps one by one.  family: 0 R/T events, 1 bends, 2 rotations, 3 tetra search, 4 shell search.
+// r3d_cases_<family>_generate(mode, n, seed, in): n rows of r3d_cases_width(family, 0) doubles -- the rows the entry above
+//   runs for (mode, n, seed);
+// r3d_cases_<family>_evaluate(flat_form, in, out, n): the host build on every row, rows of r3d_cases_width(family, 1)
+//   doubles (flat_form: the R/T event and the bend through the flat-face form; ignored by the other families);
+// r3d_cases_<family>_compare(in, out, n, tol, margin, counters, dev, first_bad, oracle): counters (8), dev (2) and
+//   first_bad (16, or null) as the entry above fills them, zeroed first (margin, first_bad: where the family has them).
+extern "C" int r3d_cases_width(int family, int output) { return output ? out_width(family) : in_width(family); }
+#define R3D_CASES_STEPS(name, FAM, stream, gen)                                                                      \
+  extern "C" void r3d_cases_##name##_generate(int mode, uint64_t n, uint64_t seed, double* in) {                     \
+    SplitMix g = stream(mode, seed);                                                                                  \
+    gen(g, mode, n, in);                                                                                              \
+  }                                                                                                                   \
+  extern "C" void r3d_cases_##name##_evaluate(int flat_form, const double* in, double* out, uint64_t n) {            \
+    eval_host(FAM, flat_form != 0, in, out, n);                                                                       \
   }
+R3D_CASES_STEPS(rt, FAM_RT, rt_stream, gen_rt)
+R3D_CASES_STEPS(bend, FAM_BEND, bend_stream, gen_bend)
+R3D_CASES_STEPS(rot, FAM_ROT, rot_stream, gen_rot)
+R3D_CASES_STEPS(tet, FAM_TET, tet_stream, gen_tet)
+R3D_CASES_STEPS(shell, FAM_SHELL, shell_stream, gen_shell)
+#undef R3D_CASES_STEPS
+static void zero_counters(uint64_t* counters, double* dev) {
+  for (int i = 0; i < 8; i++) counters[i] = 0;
+  dev[0] = dev[1] = 0.0;
+}
+extern "C" void r3d_cases_rt_compare(const double* in, const double* out, uint64_t n, double tol, double margin, uint64_t* counters,
+                                     double* dev, double* first_bad, rt_event_fn oracle) {
+  zero_counters(counters, dev);
+  cmp_rt(in, out, n, 0, tol, margin, counters, dev, first_bad, oracle);
+}
+extern "C" void r3d_cases_bend_compare(const double* in, const double* out, uint64_t n, double tol, double margin, uint64_t* counters,
+                                       double* dev, double*, bend_event_fn oracle) {
+  zero_counters(counters, dev);
+  cmp_bend(in, out, n, tol, margin, counters, dev, oracle);
+}
+extern "C" void r3d_cases_rot_compare(const double* in, const double* out, uint64_t n, double tol, double, uint64_t* counters,
+                                      double* dev, double*, transform_fn oracle) {
+  zero_counters(counters, dev);
+  cmp_rot(in, out, n, tol, counters, dev, oracle);
+}
+extern "C" void r3d_cases_tet_compare(const double* in, const double* out, uint64_t n, double tol, double, uint64_t* counters,
+                                      double* dev, double* first_bad, tet_search_fn oracle) {
+  zero_counters(counters, dev);
+  cmp_tet(in, out, n, 0, tol, counters, dev, first_bad, oracle);
+}
+extern "C" void r3d_cases_shell_compare(const double* in, const double* out, uint64_t n, double tol, double, uint64_t* counters,
+                                        double* dev, double* first_bad, shell_search_fn oracle) {
+  zero_counters(counters, dev);
+  cmp_shell(in, out, n, 0, tol, counters, dev, first_bad, oracle);
 }

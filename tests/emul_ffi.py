@@ -15,7 +15,7 @@ def lib():
     if _lib is None:
         so = os.path.join(_HERE, "emul", "libr3d_emul.so")
         src = os.path.join(_HERE, "emul", "emul.cpp")
-        deps = [src] + [os.path.join(_ffi.REPO, "radiative3d_amd", "csrc", f)
+        deps = [src, os.path.join(_HERE, "emul", "physics_cases.h")] + [os.path.join(_ffi.REPO, "radiative3d_amd", "csrc", f)
                         for f in os.listdir(os.path.join(_ffi.REPO, "radiative3d_amd", "csrc"))
                         if f.endswith(".h")]
         if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
@@ -93,3 +93,57 @@ def sample_cdf_both_ways(cdf, u, bits=0):
     lib().r3d_emul_sample_cdf(cdf.ctypes.data_as(dp), cdf.size, bits, u.ctypes.data_as(dp), u.size,
                               a.ctypes.data_as(up), b.ctypes.data_as(up), C.byref(longest))
     return a, b, int(longest.value)
+
+
+# ---- the case families of the per-lane physics, step by step (tests/emul/physics_cases.h) ----
+# generate -> evaluate -> compare; the r3d_emul_* entries of the CPU tests run the three in one call on the host, a
+# caller that evaluates a table elsewhere (tests/test_physics_device.py: on the device) takes the steps one by one.
+CASE_FAMILIES = ("rt", "bend", "rot", "tet", "shell")       # the family numbers of physics_cases.h, in order
+
+
+def cases_width(family, output=False):
+    lib().r3d_cases_width.restype = C.c_int
+    return int(lib().r3d_cases_width(CASE_FAMILIES.index(family), 1 if output else 0))
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def cases_generate(family, mode, n, seed):
+    """The n input rows that the family's r3d_emul_* entry runs for (mode, n, seed)."""
+    import numpy as np
+    table = np.zeros((n, cases_width(family)), dtype=np.float64)
+    fn = getattr(lib(), f"r3d_cases_{family}_generate")
+    fn.restype = None
+    fn.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]
+    fn(mode, n, seed, _dp(table))
+    return table
+
+
+def cases_evaluate(family, table, flat_form=False):
+    """The host build's output rows for the input rows `table`."""
+    import numpy as np
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    out = np.zeros((table.shape[0], cases_width(family, True)), dtype=np.float64)
+    fn = getattr(lib(), f"r3d_cases_{family}_evaluate")
+    fn.restype = None
+    fn.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64]
+    fn(1 if flat_form else 0, _dp(table), _dp(out), table.shape[0])
+    return out
+
+
+def cases_compare(family, table, out, tol, margin, oracle):
+    """An output table against the oracle's callback `oracle` (a ctypes function, or None where the family allows):
+    (counters[8], dev[2], first_bad[16]) as the family's r3d_emul_* entry fills them."""
+    import numpy as np
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    out = np.ascontiguousarray(out, dtype=np.float64)
+    assert table.shape == (out.shape[0], cases_width(family)) and out.shape[1] == cases_width(family, True)
+    counters, dev, first = (C.c_uint64 * 8)(), (C.c_double * 2)(), (C.c_double * 16)()
+    fn = getattr(lib(), f"r3d_cases_{family}_compare")
+    fn.restype = None
+    fn.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, C.c_double, C.c_double, C.POINTER(C.c_uint64),
+                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
+    fn(_dp(table), _dp(out), table.shape[0], tol, margin, counters, dev, first, C.cast(oracle, C.c_void_p) if oracle else None)
+    return list(counters), list(dev), list(first)
