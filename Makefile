@@ -5,7 +5,7 @@
 #   make engine     radiative3d_amd/lib/libr3d_hip.so    (hipcc, gfx950)
 #   make oracle     oracle/libr3d_oracle.so              (g++; test infrastructure)
 #   make cli        ./main                               (g++; the reference's command-line surface)
-#   make devtest    tests/emul/libr3d_physics_device{,_repro}.so  (hipcc, gfx950; test infrastructure)
+#   make devtest    tests/emul/libr3d_{physics,tables}_device{,_repro}.so  (hipcc, gfx950; test infrastructure)
 #
 # `make -q` succeeding is what scripts/do-fundamentals.sh (reference :145-152)
 # checks before a run.
@@ -134,16 +134,26 @@ oracle/libr3d_tables_oracle.so: oracle/r3d_tables_oracle.cpp
 # The per-lane physics case by case on the device (tests/test_physics_device.py): ONE test-only unit outside csrc/,
 # which includes the engine's headers and tests/emul/physics_cases.h, compiled with the engine's flags and with the
 # reproducible build's -- sibling compilations of the same text, not the traversal kernels' code objects.
+# (Its guided draws can take their guide from the engine's build_guide_on_device: the engine's table object is linked in,
+# named BEFORE the source on the command line: hipcc reads whatever follows a .hip file as HIP text.)
 DEVTEST_SRC := tests/emul/physics_device.hip
 DEVTEST_HDR := tests/emul/physics_cases.h $(ENGINE_HDR)
-devtest: tests/emul/libr3d_physics_device.so tests/emul/libr3d_physics_device_repro.so
-tests/emul/libr3d_physics_device.so: $(DEVTEST_SRC) $(DEVTEST_HDR)
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(DEVTEST_SRC)
-tests/emul/libr3d_physics_device_repro.so: $(DEVTEST_SRC) $(DEVTEST_HDR)
-	$(HIPCC) $(HIPFLAGS) -DR3D_REPRODUCIBLE -ffp-contract=off -shared -o $@ $(DEVTEST_SRC)
+devtest: tests/emul/libr3d_physics_device.so tests/emul/libr3d_physics_device_repro.so \
+         tests/emul/libr3d_tables_device.so tests/emul/libr3d_tables_device_repro.so
+tests/emul/libr3d_physics_device.so: $(DEVTEST_SRC) $(DEVTEST_HDR) $(OBJDIR)/main_tables.o
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(OBJDIR)/main_tables.o $(DEVTEST_SRC)
+tests/emul/libr3d_physics_device_repro.so: $(DEVTEST_SRC) $(DEVTEST_HDR) $(OBJDIR)/repro_tables.o
+	$(HIPCC) $(HIPFLAGS) -DR3D_REPRODUCIBLE -ffp-contract=off -shared -o $@ $(OBJDIR)/repro_tables.o $(DEVTEST_SRC)
+# The table builders entry by entry (tests/test_tables_build_device.py): thin test-only entries linked with the table
+# OBJECTS of the two engine builds -- the code libr3d_hip.so and libr3d_hip_repro.so carry, not a sibling compilation.
+TABTEST_SRC := tests/emul/tables_device.hip
+tests/emul/libr3d_tables_device.so: $(TABTEST_SRC) $(ENGINE_HDR) $(OBJDIR)/main_tables.o
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(OBJDIR)/main_tables.o $(TABTEST_SRC)
+tests/emul/libr3d_tables_device_repro.so: $(TABTEST_SRC) $(ENGINE_HDR) $(OBJDIR)/repro_tables.o
+	$(HIPCC) $(HIPFLAGS) -DR3D_REPRODUCIBLE -ffp-contract=off -shared -o $@ $(OBJDIR)/repro_tables.o $(TABTEST_SRC)
 
 clean:
-	rm -f $(LIBDIR)/*.so oracle/*.so tests/emul/libr3d_physics_device*.so main
+	rm -f $(LIBDIR)/*.so oracle/*.so tests/emul/libr3d_physics_device*.so tests/emul/libr3d_tables_device*.so main
 	rm -rf $(OBJDIR)
 
 # Developer variants of the engine (timing-only / diagnostic builds, never shipped as libr3d_hip.so;

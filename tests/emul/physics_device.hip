@@ -7,7 +7,8 @@
 // reproducible build's (-DR3D_REPRODUCIBLE -ffp-contract=off).
 //
 // It is a SIBLING compilation of the same text under the same flags, with its own inlining and schedule: not the code
-// object of the traversal kernels.  It stands outside radiative3d_amd/csrc/, is not part of the C-ABI and is loaded by
+// object of the traversal kernels.  (Only build_guide_on_device, for the guided draws, is the engine's own object:
+// build/obj/main_tables.o resp. repro_tables.o is linked in.)  It stands outside radiative3d_amd/csrc/, is not part of the C-ABI and is loaded by
 // nothing but the tests.
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,7 @@
 #define R3D_LOC_REASON(k, mask) ((void)0)
 #include "../../radiative3d_amd/csrc/r3d_pack.h"
 #include "../../radiative3d_amd/csrc/r3d_physics.h"
+#include "../../radiative3d_amd/csrc/r3d_tables_build.h"
 #include "physics_cases.h"
 
 using namespace r3d;
@@ -141,10 +143,11 @@ extern "C" int r3d_devtest_quad(int device, const double* in, double* out, uint6
   return 0;
 }
 
-// out[i] = sample_cdf_guided(cdf, guide, bits, cdf[n - 1], u[i]) on the device, the guide built here by build_guide_cells
-// (bits = 0: the width the engine chooses for a table of n entries).
+// out[i] = sample_cdf_guided(cdf, guide, bits, cdf[n - 1], u[i]) on the device (bits = 0: the width the engine chooses for a
+// table of n entries).  The guide is built here by build_guide_cells, or, with guide_on_device, in HBM by the engine's own
+// build_guide_on_device (the library is linked with the engine's table object): the builder of every guide a run reads.
 extern "C" int r3d_devtest_guided(int device, const double* cdf, uint64_t n, uint32_t bits, const double* u, uint64_t m,
-                                  uint64_t* out) {
+                                  uint64_t* out, int guide_on_device) {
   if (!cdf || !u || !out) return fail("r3d_devtest_guided: null table");
   if (n == 0 || n > (1ull << 31) || bits > 24 || m > kMaxCases) return fail("r3d_devtest_guided: table or guide out of range");
   if (m == 0) return 0;
@@ -152,11 +155,16 @@ extern "C" int r3d_devtest_guided(int device, const double* cdf, uint64_t n, uin
     if (!(u[i] >= 0.0 && u[i] <= 1.0)) return fail("r3d_devtest_guided: a draw outside [0, 1]");
   if (!bits) bits = guide_bits_for(n);
   std::vector<GuideCell> cells;
-  build_guide_cells(cdf, n, bits, cells);
+  if (!guide_on_device) build_guide_cells(cdf, n, bits, cells);
   DEVTEST_OK(hipSetDevice(device));
   DevMem dcdf, dguide, du, dout;
   DEVTEST_OK(dcdf.upload(cdf, n * sizeof(double)));
-  DEVTEST_OK(dguide.upload(cells.data(), cells.size() * sizeof(GuideCell)));
+  DEVTEST_OK(dguide.upload(guide_on_device ? nullptr : cells.data(), (size_t(1) << bits) * sizeof(GuideCell)));
+  if (guide_on_device) {
+    DEVTEST_OK(hipMemset(dguide.p, 0, (size_t(1) << bits) * sizeof(GuideCell)));
+    DEVTEST_OK(build_guide_on_device((const double*)dcdf.p, n, bits, (GuideCell*)dguide.p, nullptr));
+    DEVTEST_OK(hipDeviceSynchronize());
+  }
   DEVTEST_OK(du.upload(u, m * sizeof(double)));
   DEVTEST_OK(dout.upload(nullptr, m * sizeof(uint64_t)));
   DEVTEST_OK(hipMemset(dout.p, 0, m * sizeof(uint64_t)));

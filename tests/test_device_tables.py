@@ -79,7 +79,9 @@ class _Patched:
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,deg", [("crustpinch", 5), ("lopnor", 4), ("sphere", 4), ("halfspace", 6),
-                                      ("sphere_deep", 4), ("crustpinch_vids", 4)])
+                                      ("sphere_deep", 4), ("crustpinch_vids", 4),
+                                      # 320 directions: ONE partial scan block, 20 of its 256 work-items hold data; guides of 2^7 cells
+                                      ("halfspace", 2), ("lopnor", 2)])
 def test_device_tables_match_the_tables_oracle_and_the_path_oracle(name, deg):
     from oracle import oracle_ffi
     from oracle import tables_ffi as T

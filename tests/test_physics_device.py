@@ -67,7 +67,7 @@ def device_lib(repro=False):
     L.r3d_devtest_quad.restype = C.c_int
     L.r3d_devtest_quad.argtypes = [C.c_int, dp, dp, C.c_uint64]
     L.r3d_devtest_guided.restype = C.c_int
-    L.r3d_devtest_guided.argtypes = [C.c_int, dp, C.c_uint64, C.c_uint32, dp, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.r3d_devtest_guided.argtypes = [C.c_int, dp, C.c_uint64, C.c_uint32, dp, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
     return L
 
 
@@ -304,12 +304,19 @@ def _guided_tables():
     return tables + [(f"tiny {n}", rng.uniform(0.1, 1.0, n), 4) for n in (1, 2, 3, 9, 17)]
 
 
+def _guided_cases():
+    """Every table through a guide built on the host (the case keeps the table's name) and through one built on the device."""
+    tables = _guided_tables()
+    return [pytest.param(n, w, b, 0, id=n) for n, w, b in tables] + [pytest.param(n, w, b, 1, id=n + ", device-built guide") for n, w, b in tables]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,weights,bits", _guided_tables(), ids=[t[0] for t in _guided_tables()])
-def test_device_guided_draw_is_the_bisection(name, weights, bits):
+@pytest.mark.parametrize("name,weights,bits,guide_on_device", _guided_cases())
+def test_device_guided_draw_is_the_bisection(name, weights, bits, guide_on_device):
     """`sample_cdf_guided` in its device form (address-space-1 loads of the cells and of the table) returns the index the
     host bisection `sample_cdf` returns, for every draw: random ones, the ends, and every table entry's own quantile
-    with its two neighbours in floating point."""
+    with its two neighbours in floating point -- through a guide made by `build_guide_cells` on the host, and through one
+    made in HBM by the engine's `build_guide_on_device`, the builder of every guide a run reads."""
     rng = np.random.default_rng(8)
     cdf = np.cumsum(weights)
     on = cdf / cdf[-1]
@@ -322,7 +329,7 @@ def test_device_guided_draw_is_the_bisection(name, weights, bits):
         assert 8 <= longest <= 64
     L = device_lib()
     got = np.zeros(u.size, dtype=np.uint64)
-    rc = L.r3d_devtest_guided(0, _dp(cdf), cdf.size, bits, _dp(u), u.size, got.ctypes.data_as(C.POINTER(C.c_uint64)))
+    rc = L.r3d_devtest_guided(0, _dp(cdf), cdf.size, bits, _dp(u), u.size, got.ctypes.data_as(C.POINTER(C.c_uint64)), guide_on_device)
     assert rc == 0, L.r3d_devtest_last_error().decode()
     assert np.array_equal(got, plain), (name, np.flatnonzero(got != plain)[:5], longest)
 
@@ -335,8 +342,8 @@ def test_device_entries_refuse_what_they_cannot_run():
     calls = [lambda: L.r3d_devtest_eval(0, 2, 0, None, _dp(out), 64), lambda: L.r3d_devtest_eval(0, 2, 0, _dp(table), None, 64),
              lambda: L.r3d_devtest_eval(0, 5, 0, _dp(table), _dp(out), 64), lambda: L.r3d_devtest_eval(0, -1, 0, _dp(table), _dp(out), 64),
              lambda: L.r3d_devtest_quad(0, None, _dp(out), 4), lambda: L.r3d_devtest_quad(0, _dp(table), None, 4),
-             lambda: L.r3d_devtest_guided(0, None, 8, 4, _dp(table), 8, None),
-             lambda: L.r3d_devtest_guided(0, _dp(table), 8, 4, None, 8, out.ctypes.data_as(C.POINTER(C.c_uint64)))]
+             lambda: L.r3d_devtest_guided(0, None, 8, 4, _dp(table), 8, None, 0),
+             lambda: L.r3d_devtest_guided(0, _dp(table), 8, 4, None, 8, out.ctypes.data_as(C.POINTER(C.c_uint64)), 1)]
     for call in calls:
         assert call() == 1 and L.r3d_devtest_last_error().decode().startswith("r3d_devtest_")
     assert not out.any()
