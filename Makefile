@@ -1,12 +1,18 @@
 # Build of the MI355X phonon-transport engine and its host-side pieces.
 #
-#   make            host model builder + HIP engine + oracle (default)
+#   make            every binary the package, ./main and the tests load (default: all of the below)
 #   make host       radiative3d_amd/lib/libr3d_host.so   (g++)
 #   make engine     radiative3d_amd/lib/libr3d_hip.so    (hipcc, gfx950)
-#   make oracle     oracle/libr3d_oracle.so              (g++; test infrastructure)
+#   make repro      radiative3d_amd/lib/libr3d_hip_repro.so  (the same engine, bit-defined per history)
+#   make oracle     oracle/libr3d_oracle.so, oracle/libr3d_tables_oracle.so  (g++; test infrastructure)
 #   make cli        ./main                               (g++; the reference's command-line surface)
 #   make devtest    tests/emul/libr3d_{physics,tables}_device{,_repro}.so  (hipcc, gfx950; test infrastructure)
+#   make emul       tests/emul/libr3d_emul.so            (g++; the kernels' per-lane code on the host, test infrastructure)
+#   make stepfinals radiative3d_amd/lib/variant_STEPFINALS.so  (make variant NAME=STEPFINALS ...; test infrastructure)
+#   make variant NAME=X DEFS=... [DEFS_CYL= DEFS_TET= DEFS_SPH=]   a developer build of the engine (at the end of this file)
 #
+# Every engine object -- of the two shipped builds and of any variant -- comes from ONE rule template (engine_object)
+# over ONE table of units; parallelism is make's -j everywhere.
 # `make -q` succeeding is what scripts/do-fundamentals.sh (reference :145-152)
 # checks before a run.
 
@@ -38,7 +44,6 @@ HOST_SRC := $(HOSTDIR)/ecs.cpp $(HOSTDIR)/grid.cpp $(HOSTDIR)/model.cpp \
             $(HOSTDIR)/models_builtin.cpp $(HOSTDIR)/cmdline.cpp $(HOSTDIR)/dataout.cpp \
             $(HOSTDIR)/capi.cpp
 HOST_HDR := $(wildcard $(HOSTDIR)/*.hpp) include/r3d.h include/r3d_host.h radiative3d_amd/stats/r3d_window_sums.h
-ENGINE_SRC := $(CSRC)/r3d_engine.hip $(CSRC)/r3d_tables_build.hip $(CSRC)/r3d_kernels_kind.hip $(CSRC)/r3d_volume.hip
 ENGINE_HDR := $(wildcard $(CSRC)/*.h) include/r3d.h
 # The add-ons: what stands beside the engine on its C-ABI, each a directory radiative3d_amd/<name>/ of ONE .hip and
 # its headers, which includes $(COMMON)/r3d_entry.h and include/r3d.h and nothing from csrc/.  A new one is a word here.
@@ -53,42 +58,51 @@ addon_hdr = $(wildcard radiative3d_amd/$(1)/*.h) $(COMMON)/r3d_entry.h include/r
 OBJDIR   := build/obj
 
 # (the default goal is the first target of the file: it has to come before the generated object rules)
-.PHONY: default all host engine repro oracle cli devtest clean
-default: all
-# addon_object(tag, extra flags, add-on): its object in one engine build
-define addon_object
-$(OBJDIR)/$(1)_$(3).o: $(call addon_src,$(3)) $(call addon_hdr,$(3))
+.PHONY: all host engine repro oracle cli devtest emul stepfinals variant clean FORCE
+.DELETE_ON_ERROR:
+all: host engine repro oracle cli devtest emul stepfinals
+
+# The engine's own units.  The traversal kernels are one source compiled once per cell kind: KIND_<unit> is the name
+# the kind's switches carry (HIPFLAGS_<K> above, DEFS_<K> of a variant) and its number.
+UNITS      := engine tables volume cyl tet sph
+SRC_engine := $(CSRC)/r3d_engine.hip
+SRC_tables := $(CSRC)/r3d_tables_build.hip
+SRC_volume := $(CSRC)/r3d_volume.hip
+$(foreach k,cyl tet sph,$(eval SRC_$(k) := $(CSRC)/r3d_kernels_kind.hip))
+HDR_volume := $(COMMON)/r3d_entry.h
+KIND_cyl   := CYL 0
+KIND_tet   := TET 1
+KIND_sph   := SPH 2
+# unit_src(unit), unit_hdr(unit): of an engine unit from the table, of an add-on from its directory
+unit_src = $(or $(SRC_$(1)),$(call addon_src,$(1)))
+unit_hdr = $(if $(SRC_$(1)),$(ENGINE_HDR) $(HDR_$(1)),$(call addon_hdr,$(1)))
+# unit_cc(unit, flags of the build): the compile line of one unit up to its -o
+unit_cc = $(HIPCC) $(HIPFLAGS) $(HIPFLAGS_$(word 1,$(KIND_$(1)))) $(2) $(addprefix -DR3D_KIND=,$(word 2,$(KIND_$(1)))) -c
+# engine_object(tag, unit, flags of the build, further prerequisites): THE rule for an object of any engine build
+define engine_object
+$(OBJDIR)/$(1)_$(2).o: $(call unit_src,$(2)) $(call unit_hdr,$(2)) $(4)
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(call addon_src,$(3))
+	$(call unit_cc,$(2),$(3)) -o $$@ $(call unit_src,$(2))
 
 endef
-# engine_objects(tag, extra flags): the objects of one engine build, six of the engine and one per add-on
-define engine_objects
-$(OBJDIR)/$(1)_engine.o: $(CSRC)/r3d_engine.hip $(ENGINE_HDR)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(CSRC)/r3d_engine.hip
-$(OBJDIR)/$(1)_tables.o: $(CSRC)/r3d_tables_build.hip $(ENGINE_HDR)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(CSRC)/r3d_tables_build.hip
-$(OBJDIR)/$(1)_volume.o: $(CSRC)/r3d_volume.hip $(ENGINE_HDR) $(COMMON)/r3d_entry.h
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(2) -c -o $$@ $(CSRC)/r3d_volume.hip
-$(OBJDIR)/$(1)_cyl.o: $(CSRC)/r3d_kernels_kind.hip $(ENGINE_HDR)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_CYL) $(2) -DR3D_KIND=0 -c -o $$@ $(CSRC)/r3d_kernels_kind.hip
-$(OBJDIR)/$(1)_tet.o: $(CSRC)/r3d_kernels_kind.hip $(ENGINE_HDR)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_TET) $(2) -DR3D_KIND=1 -c -o $$@ $(CSRC)/r3d_kernels_kind.hip
-$(OBJDIR)/$(1)_sph.o: $(CSRC)/r3d_kernels_kind.hip $(ENGINE_HDR)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_SPH) $(2) -DR3D_KIND=2 -c -o $$@ $(CSRC)/r3d_kernels_kind.hip
-$(foreach a,$(ADDONS),$(call addon_object,$(1),$(2),$(a)))
-endef
-engine_objs = $(foreach a,$(ADDONS),$(OBJDIR)/$(1)_$(a).o) $(OBJDIR)/$(1)_engine.o $(OBJDIR)/$(1)_tables.o $(OBJDIR)/$(1)_volume.o $(OBJDIR)/$(1)_cyl.o $(OBJDIR)/$(1)_tet.o $(OBJDIR)/$(1)_sph.o
-$(eval $(call engine_objects,main,))
-$(eval $(call engine_objects,repro,-DR3D_REPRODUCIBLE -ffp-contract=off))
+# engine_library(library, tag, units in link order): THE link rule
+engine_objs = $(foreach u,$(2),$(OBJDIR)/$(1)_$(u).o)
+define engine_library
+$(1): $(call engine_objs,$(2),$(3))
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) --offload-arch=gfx950 -shared -pthread -o $$@ $(call engine_objs,$(2),$(3)) $(RCCL_LIBS)
 
-all: host engine repro oracle cli devtest
+endef
+# (librccl is bound at first use, csrc/r3d_rccl.h: the copy already in the process if there is one)
+RCCL_LIBS ?= -ldl
+
+# The two shipped builds: `main` with the flags above, `repro` with two more.  build_suffix(tag) is what a build's libraries
+# carry in their names: nothing for main, _repro for repro.
+BUILDS      := main repro
+FLAGS_repro := -DR3D_REPRODUCIBLE -ffp-contract=off
+build_suffix = $(subst _main,,_$(1))
+$(foreach b,$(BUILDS),$(foreach u,$(UNITS) $(ADDONS),$(eval $(call engine_object,$(b),$(u),$(FLAGS_$(b))))))
+$(foreach b,$(BUILDS),$(eval $(call engine_library,$(LIBDIR)/libr3d_hip$(call build_suffix,$(b)).so,$(b),$(ADDONS) $(UNITS))))
 
 host: $(LIBDIR)/libr3d_host.so
 engine: $(LIBDIR)/libr3d_hip.so
@@ -113,16 +127,6 @@ $(LIBDIR)/libr3d_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS) -shared -pthread -o $@ $(HOST_SRC)
 
-# (librccl is bound at first use, csrc/r3d_rccl.h: the copy already in the process if there is one)
-RCCL_LIBS ?= -ldl
-$(LIBDIR)/libr3d_hip.so: $(call engine_objs,main)
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) --offload-arch=gfx950 -shared -pthread -o $@ $(call engine_objs,main) $(RCCL_LIBS)
-
-$(LIBDIR)/libr3d_hip_repro.so: $(call engine_objs,repro)
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) --offload-arch=gfx950 -shared -pthread -o $@ $(call engine_objs,repro) $(RCCL_LIBS)
-
 oracle/libr3d_oracle.so: oracle/r3d_oracle.cpp oracle/philox.h include/r3d.h
 	$(CXX) $(CXXFLAGS) -shared -o $@ oracle/r3d_oracle.cpp
 
@@ -136,46 +140,65 @@ oracle/libr3d_tables_oracle.so: oracle/r3d_tables_oracle.cpp
 # reproducible build's -- sibling compilations of the same text, not the traversal kernels' code objects.
 # (Its guided draws can take their guide from the engine's build_guide_on_device: the engine's table object is linked in,
 # named BEFORE the source on the command line: hipcc reads whatever follows a .hip file as HIP text.)
-DEVTEST_SRC := tests/emul/physics_device.hip
-DEVTEST_HDR := tests/emul/physics_cases.h $(ENGINE_HDR)
-devtest: tests/emul/libr3d_physics_device.so tests/emul/libr3d_physics_device_repro.so \
-         tests/emul/libr3d_tables_device.so tests/emul/libr3d_tables_device_repro.so
-tests/emul/libr3d_physics_device.so: $(DEVTEST_SRC) $(DEVTEST_HDR) $(OBJDIR)/main_tables.o
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(OBJDIR)/main_tables.o $(DEVTEST_SRC)
-tests/emul/libr3d_physics_device_repro.so: $(DEVTEST_SRC) $(DEVTEST_HDR) $(OBJDIR)/repro_tables.o
-	$(HIPCC) $(HIPFLAGS) -DR3D_REPRODUCIBLE -ffp-contract=off -shared -o $@ $(OBJDIR)/repro_tables.o $(DEVTEST_SRC)
 # The table builders entry by entry (tests/test_tables_build_device.py): thin test-only entries linked with the table
 # OBJECTS of the two engine builds -- the code libr3d_hip.so and libr3d_hip_repro.so carry, not a sibling compilation.
-TABTEST_SRC := tests/emul/tables_device.hip
-tests/emul/libr3d_tables_device.so: $(TABTEST_SRC) $(ENGINE_HDR) $(OBJDIR)/main_tables.o
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(OBJDIR)/main_tables.o $(TABTEST_SRC)
-tests/emul/libr3d_tables_device_repro.so: $(TABTEST_SRC) $(ENGINE_HDR) $(OBJDIR)/repro_tables.o
-	$(HIPCC) $(HIPFLAGS) -DR3D_REPRODUCIBLE -ffp-contract=off -shared -o $@ $(OBJDIR)/repro_tables.o $(TABTEST_SRC)
+DEVTESTS    := physics tables
+HDR_physics := tests/emul/physics_cases.h
+device_test_lib = tests/emul/libr3d_$(1)_device$(call build_suffix,$(2)).so
+# device_test(name, build): tests/emul/<name>_device.hip under the build's flags, with the build's table object
+define device_test
+$(call device_test_lib,$(1),$(2)): tests/emul/$(1)_device.hip $(HDR_$(1)) $(ENGINE_HDR) $(OBJDIR)/$(2)_tables.o
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_$(2)) -shared -o $$@ $(OBJDIR)/$(2)_tables.o tests/emul/$(1)_device.hip
+
+endef
+$(foreach t,$(DEVTESTS),$(foreach b,$(BUILDS),$(eval $(call device_test,$(t),$(b)))))
+devtest: $(foreach t,$(DEVTESTS),$(foreach b,$(BUILDS),$(call device_test_lib,$(t),$(b))))
+
+# The kernels' per-lane code built for the host (tests/emul_ffi.py, tests/emul/emul.cpp: it includes csrc/'s headers)
+emul: tests/emul/libr3d_emul.so
+tests/emul/libr3d_emul.so: tests/emul/emul.cpp tests/emul/physics_cases.h $(ENGINE_HDR)
+	$(CXX) -std=c++17 -O2 -fPIC -shared -o $@ tests/emul/emul.cpp
+
+# A test-only sibling compilation of the engine: the chain-step kernel with its final-record stores compiled in
+# (tests/test_gpu_parity.py holds it per history against the oracle; never loaded by the product)
+stepfinals:
+	$(MAKE) variant NAME=STEPFINALS DEFS=-DR3D_STEP_FINALS=1
 
 clean:
-	rm -f $(LIBDIR)/*.so oracle/*.so tests/emul/libr3d_physics_device*.so tests/emul/libr3d_tables_device*.so main
+	rm -f $(LIBDIR)/*.so oracle/*.so tests/emul/*.so main
 	rm -rf $(OBJDIR)
 
 # Developer variants of the engine (timing-only / diagnostic builds, never shipped as libr3d_hip.so;
 # the only builds that say -DR3D_DEV_BUILD, without which the R3D_ABLATE_* / R3D_PHASE_TIMING switches
 # are a compile error -- csrc/r3d_tables.h):
-#   make variant NAME=PHASE DEFS="-DR3D_PHASE_TIMING"   ->  radiative3d_amd/lib/variant_PHASE.so
+#   make -j8 variant NAME=PHASE DEFS="-DR3D_PHASE_TIMING"   ->  radiative3d_amd/lib/variant_PHASE.so
 # run through the tools with R3D_HIP_LIB=radiative3d_amd/lib/variant_PHASE.so (tools/time_chain.py,
 # tools/pool_stats.py pass it to Engine(lib=...); the library itself reads no environment).
-# Every object is compiled afresh and each compile's status is checked: a failed one cannot leave
-# an older object to be linked in its place.
-VOBJ = $(OBJDIR)/v$(NAME)
+# The objects are engine_object's, tagged v$(NAME), each with a prerequisite more: a stamp that holds its compile line and
+# is rewritten only when that line changes.  So a changed switch recompiles the units it reaches and no other, and
+# the library is never linked from an object compiled under other flags.  Nor from one a failed compile left behind:
+# the library is removed before anything is brought up to date, and linked again only after every object is.
 VDEFS = -DR3D_DEV_BUILD $(DEFS)
-VOBJS = $(foreach o,engine tables volume cyl tet sph $(ADDONS),$(VOBJ)_$(o).o)
+# flags_stamp(file, text): every line runs under -n and -q too (the +), so that those see the objects as they are
+define flags_stamp
+$(1): export R3D_STAMP_TEXT := $(2)
+$(1): FORCE
+	+@mkdir -p $(OBJDIR); printf '%s\n' "$$$$R3D_STAMP_TEXT" | cmp -s - $$@ || printf '%s\n' "$$$$R3D_STAMP_TEXT" > $$@
+
+endef
+ifneq ($(NAME),)
+VARIANT := $(LIBDIR)/variant_$(NAME).so
+vflags = $(VDEFS) $(DEFS_$(word 1,$(KIND_$(1))))
+vstamp = $(OBJDIR)/v$(NAME)_$(1).flags
+$(foreach u,$(UNITS) $(ADDONS),$(eval $(call flags_stamp,$(call vstamp,$(u)),$(call unit_cc,$(u),$(call vflags,$(u)))))\
+                               $(eval $(call engine_object,v$(NAME),$(u),$(call vflags,$(u)),$(call vstamp,$(u)))))
+$(eval $(call engine_library,$(VARIANT),v$(NAME),$(UNITS) $(ADDONS)))
+variant: $(VARIANT)
+# (when `variant` is a goal, and the run is neither a dry one nor a question: those remove nothing)
+ifeq ($(filter variant,$(MAKECMDGOALS))$(findstring n,$(firstword -$(MAKEFLAGS)))$(findstring q,$(firstword -$(MAKEFLAGS))),variant)
+$(shell rm -f $(VARIANT))
+endif
+else
 variant:
-	@mkdir -p $(OBJDIR)
-	rm -f $(VOBJS) $(LIBDIR)/variant_$(NAME).so
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_engine.o $(CSRC)/r3d_engine.hip & p1=$$!; \
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_tables.o $(CSRC)/r3d_tables_build.hip & p2=$$!; \
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_volume.o $(CSRC)/r3d_volume.hip & p6=$$!; \
-	$(foreach a,$(ADDONS),$(HIPCC) $(HIPFLAGS) $(VDEFS) -c -o $(VOBJ)_$(a).o $(call addon_src,$(a)) & p_$(a)=$$!;) \
-	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_CYL) $(VDEFS) $(DEFS_CYL) -DR3D_KIND=0 -c -o $(VOBJ)_cyl.o $(CSRC)/r3d_kernels_kind.hip & p3=$$!; \
-	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_TET) $(VDEFS) $(DEFS_TET) -DR3D_KIND=1 -c -o $(VOBJ)_tet.o $(CSRC)/r3d_kernels_kind.hip & p4=$$!; \
-	$(HIPCC) $(HIPFLAGS) $(HIPFLAGS_SPH) $(VDEFS) $(DEFS_SPH) -DR3D_KIND=2 -c -o $(VOBJ)_sph.o $(CSRC)/r3d_kernels_kind.hip & p5=$$!; \
-	rc=0; for p in $$p1 $$p2 $$p3 $$p4 $$p5 $$p6 $(foreach a,$(ADDONS),$$p_$(a)); do wait $$p || rc=1; done; exit $$rc
-	$(HIPCC) --offload-arch=gfx950 -shared -pthread -o $(LIBDIR)/variant_$(NAME).so $(VOBJS) $(RCCL_LIBS)
+	$(error make variant NAME=X DEFS="..." [DEFS_CYL= DEFS_TET= DEFS_SPH=]: NAME is not set)
+endif

@@ -4,12 +4,12 @@ arrayimage.m:42-83 and normcurve_fitpowerlaw.m restated in numpy long double, ro
 rounding bounds -- and the shapes the kernel is run on."""
 import ctypes as C
 import os
-import subprocess
 import tempfile
 from fractions import Fraction
 
 import numpy as np
 
+from native_build import host_build
 from radiative3d_amd import _ffi
 
 U = 2.0 ** -53
@@ -60,11 +60,8 @@ def host_arrays():
     global _host, _keep
     if _host is None:
         _keep = tempfile.TemporaryDirectory(prefix="array_image_")
-        src, so = os.path.join(_keep.name, "wrap.cpp"), os.path.join(_keep.name, "libarrays.so")
-        open(src, "w").write(WRAPPER)
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-I",
-                               os.path.join(_ffi.REPO, "radiative3d_amd", "arrays"), "-o", so, src])
-        L = C.CDLL(so)
+        L = C.CDLL(host_build(_keep.name, "libarrays.so", WRAPPER, [os.path.join(_ffi.REPO, "radiative3d_amd", "arrays")],
+                              flags=("-O2", "-ffp-contract=off", "-fPIC", "-shared")))
         L.array_image_host.argtypes = [C.c_int, C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_uint32, C.c_int, C.c_double,
                                                                                   C.c_void_p, C.c_double] + [C.c_void_p] * 7
         L.array_image_host.restype = C.c_int

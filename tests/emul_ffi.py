@@ -2,8 +2,8 @@
 (tests/emul/libr3d_emul.so).  See tests/emul/emul.cpp."""
 import ctypes as C
 import os
-import subprocess
 
+import native_build
 from radiative3d_amd import _ffi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -13,14 +13,8 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(_HERE, "emul", "libr3d_emul.so")
-        src = os.path.join(_HERE, "emul", "emul.cpp")
-        deps = [src, os.path.join(_HERE, "emul", "physics_cases.h")] + [os.path.join(_ffi.REPO, "radiative3d_amd", "csrc", f)
-                        for f in os.listdir(os.path.join(_ffi.REPO, "radiative3d_amd", "csrc"))
-                        if f.endswith(".h")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-o", so, src])
-        L = C.CDLL(so)
+        native_build.make("emul")      # (every time: make knows what the library is built from)
+        L = C.CDLL(os.path.join(_HERE, "emul", "libr3d_emul.so"))
         L.r3d_emul_run.restype = C.c_int
         L.r3d_emul_run.argtypes = [C.POINTER(_ffi.ModelDesc), C.c_uint64, C.c_uint64, C.c_uint64,
                                    C.POINTER(_ffi.Result), C.POINTER(_ffi.Final)]

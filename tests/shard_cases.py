@@ -3,10 +3,10 @@ sharded estimator (include/r3d.h r3d_batch_partial / r3d_batch_merge) is held at
 arithmetic both halves share with the kernels (radiative3d_amd/stats/r3d_batch_moments.h)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+from native_build import host_build
 from radiative3d_amd import _ffi
 
 # one shard (the one-device estimator), the smallest job, odd sizes, a square, and N = 64 dealt to four
@@ -38,12 +38,7 @@ extern "C" void merge_u64(const uint64_t* sum, const double* ss, uint64_t len, u
 
 def build_host_shard_stats(directory):
     """The header compiled by g++ with the flags tests/test_batch_stats.py uses, as a ctypes library."""
-    src, so = os.path.join(str(directory), "wrap.cpp"), os.path.join(str(directory), "libshardstats.so")
-    with open(src, "w") as f:
-        f.write(WRAPPER)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Werror", "-I",
-                           os.path.join(_ffi.REPO, "radiative3d_amd", "stats"), "-o", so, src])
-    L = C.CDLL(so)
+    L = C.CDLL(host_build(directory, "libshardstats.so", WRAPPER, [os.path.join(_ffi.REPO, "radiative3d_amd", "stats")]))
     p, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
     for f in (L.moments_f64, L.moments_u64, L.partial_f64, L.partial_u64):
         f.argtypes, f.restype = [p, u64, u32, p, p], None

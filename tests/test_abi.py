@@ -129,6 +129,19 @@ def test_the_shipped_engine_reads_no_environment_and_holds_no_developer_switch()
         assert "environ.get(\"R3D_" not in open(os.path.join(_ffi.REPO, "radiative3d_amd", py)).read(), py
 
 
+def test_make_all_is_everything_and_a_built_variant_is_not_compiled_again():
+    """On a built tree `make all` has nothing left to do -- the emulation library and the STEPFINALS variant are its
+    targets, not steps beside it -- and the variant's objects are make's: a second call compiles nothing."""
+    q = subprocess.run(["make", "-C", _ffi.REPO, "-q", "all"], capture_output=True, text=True)
+    assert q.returncode == 0, q.stdout + q.stderr
+    for so in (os.path.join(_ffi.REPO, "tests", "emul", "libr3d_emul.so"), os.path.join(_ffi.LIBDIR, "variant_STEPFINALS.so")):
+        assert os.path.exists(so), so
+    n = subprocess.run(["make", "-C", _ffi.REPO, "-n", "variant", "NAME=STEPFINALS", "DEFS=-DR3D_STEP_FINALS=1"],
+                       capture_output=True, text=True)
+    assert n.returncode == 0, n.stdout + n.stderr
+    assert not [l for l in n.stdout.splitlines() if re.search(r"\s-c\s", l)], n.stdout
+
+
 def test_engine_opts_mirror_matches_c_layout(tmp_path):
     prog = r'''
     #include <stdio.h>

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from cli_support import main_exe
+from native_build import host_build
 from radiative3d_amd import _ffi
 from tests.configs import halfspace
 
@@ -31,11 +32,7 @@ ARRAYS = ((5, 1, 3), (5, 0, 4), (5, 2, 2), (5, 0, 0), (5, 4, 4), (1, 0, 0))
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
     d = tmp_path_factory.mktemp("batch_plan")
-    src, so = d / "wrap.cpp", d / "libbatchplan.so"
-    src.write_text(WRAPPER)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Werror", "-I",
-                           os.path.join(REPO, "radiative3d_amd", "host"), "-o", str(so), str(src)])
-    L = C.CDLL(str(so))
+    L = C.CDLL(host_build(d, "libbatchplan.so", WRAPPER, [os.path.join(REPO, "radiative3d_amd", "host")]))
     L.spread_u32.argtypes = [C.c_void_p] + [C.c_size_t] * 4 + [C.c_void_p]
     L.spread_u32.restype = None
     for f in (L.take_f64, L.take_u64):

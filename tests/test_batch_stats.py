@@ -11,6 +11,7 @@ import pytest
 
 from batch_cases import BATCHES, check_se, count_families, families, sum_in_order
 from cli_support import main_exe
+from native_build import host_build
 from octave_text import read_octave
 from radiative3d_amd import Model, _ffi
 from tests.configs import halfspace
@@ -31,11 +32,7 @@ extern "C" void moments_u64(const uint64_t* x, uint64_t len, uint32_t b, uint64_
 @pytest.fixture(scope="module")
 def host_moments(tmp_path_factory):
     d = tmp_path_factory.mktemp("moments")
-    src, so = d / "wrap.cpp", d / "libmoments.so"
-    src.write_text(WRAPPER)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Werror", "-I",
-                           os.path.join(REPO, "radiative3d_amd", "stats"), "-o", str(so), str(src)])
-    L = C.CDLL(str(so))
+    L = C.CDLL(host_build(d, "libmoments.so", WRAPPER, [os.path.join(REPO, "radiative3d_amd", "stats")]))
     L.moments_f64.argtypes = L.moments_u64.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.moments_f64.restype = L.moments_u64.restype = None
     return L

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from native_build import host_build
 from radiative3d_amd import Model, _ffi
 from tests.configs import halfspace
 
@@ -74,10 +75,8 @@ int main(int, char** argv) {
 
 def test_the_grid_header_is_the_stored_bytes(tmp_path):
     """A 17-digit frame length and an events count above 2^32."""
-    src, exe, out = tmp_path / "driver.cpp", tmp_path / "driver", tmp_path / "scattergrid.octv"
-    src.write_text(GRID_DRIVER)
-    subprocess.check_call(["g++", "-std=c++17", "-O0", "-Wall", "-Werror", "-I", os.path.join(REPO, "radiative3d_amd", "host"),
-                           "-I", os.path.join(REPO, "include"), "-o", str(exe), str(src), "-L", _ffi.LIBDIR, "-lr3d_host",
-                           "-Wl,-rpath," + _ffi.LIBDIR])
-    subprocess.check_call([str(exe), str(out)])
+    out = tmp_path / "scattergrid.octv"
+    exe = host_build(tmp_path, "driver", GRID_DRIVER, [os.path.join(REPO, "radiative3d_amd", "host"), os.path.join(REPO, "include")],
+                     flags=("-O0",), link=("-L", _ffi.LIBDIR, "-lr3d_host", "-Wl,-rpath," + _ffi.LIBDIR))
+    subprocess.check_call([exe, str(out)])
     assert out.read_bytes() == golden("scattergrid_header.octv")

@@ -23,17 +23,16 @@ Each device test prints the largest deviations from the oracle per mode, next to
 import ctypes as C
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import emul_ffi as E
+import native_build
 from oracle import oracle_ffi as O
 from test_rt_solve import MARGIN, TOL
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 N = 2 ** 18 + 37
 
 # family -> (oracle callback, seed of mode 0 in the CPU tests, modes, mode of the flat-face form)
@@ -56,10 +55,7 @@ def cases(family, mode):
 @functools.lru_cache(maxsize=None)
 def device_lib(repro=False):
     so = os.path.join(HERE, "emul", "libr3d_physics_device_repro.so" if repro else "libr3d_physics_device.so")
-    if not os.path.exists(so):   # (__graft_entry__.build() makes it, through `make all`; a tree built otherwise: here)
-        subprocess.run(["make", "-C", REPO, "devtest"], capture_output=True, timeout=900)
-    assert os.path.exists(so), f"{os.path.basename(so)} is not built (make devtest)"
-    L = C.CDLL(so)
+    L = C.CDLL(native_build.make("devtest", missing=so))
     dp = C.POINTER(C.c_double)
     L.r3d_devtest_last_error.restype = C.c_char_p
     L.r3d_devtest_eval.restype = C.c_int

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from native_build import host_build
 from radiative3d_amd import _ffi
 from radiative3d_amd.model import volume_desc
 from tests.configs import halfspace
@@ -42,12 +43,7 @@ extern "C" void plan_stills(const uint32_t* dims, uint32_t n_range, const uint32
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
     d = tmp_path_factory.mktemp("scatter_plan")
-    src, so = d / "wrap.cpp", d / "libscatterplan.so"
-    src.write_text(WRAPPER)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Werror", "-I",
-                           os.path.join(REPO, "radiative3d_amd", "host"), "-I", os.path.join(REPO, "include"),
-                           "-o", str(so), str(src)])
-    L = C.CDLL(str(so))
+    L = C.CDLL(host_build(d, "libscatterplan.so", WRAPPER, [os.path.join(REPO, "radiative3d_amd", "host"), os.path.join(REPO, "include")]))
     L.plan_piece_end.argtypes = [C.c_uint32] * 3
     L.plan_piece_end.restype = C.c_uint32
     L.plan_box.argtypes = [C.c_void_p] * 3

@@ -33,15 +33,14 @@ import ctypes as C
 import functools
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import native_build
 from oracle import tables_ffi as T
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 LD = np.longdouble
 U = 2.0 ** -53
 
@@ -242,10 +241,7 @@ def p(a):
 @functools.lru_cache(maxsize=None)
 def device_lib(repro=False):
     so = os.path.join(HERE, "emul", "libr3d_tables_device_repro.so" if repro else "libr3d_tables_device.so")
-    if not os.path.exists(so):   # (__graft_entry__.build() makes it, through `make all`; a tree built otherwise: here)
-        subprocess.run(["make", "-C", REPO, "devtest"], capture_output=True, timeout=900)
-    assert os.path.exists(so), f"{os.path.basename(so)} is not built (make devtest)"
-    L = C.CDLL(so)
+    L = C.CDLL(native_build.make("devtest", missing=so))
     L.r3d_devtest_last_error.restype = C.c_char_p
     for name, args in [("toa", [C.c_int, C.c_int, C.c_uint64, _dp]),
                        ("toa_xyz", [C.c_int, _dp, C.c_uint64, C.c_double, C.c_double, _dp]),

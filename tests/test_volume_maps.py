@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from native_build import host_build
 from radiative3d_amd import _ffi
 from radiative3d_amd.model import volume_desc
 from volume_maps_cases import NEVER, SHAPES, frame_ranges, grids_of, merge_numpy, neutral_maps, time_maps_numpy
@@ -45,11 +46,7 @@ extern "C" void maps_merge(uint64_t n, uint32_t* first, uint32_t* peak_frame, ui
 @pytest.fixture(scope="module")
 def host_maps(tmp_path_factory):
     d = tmp_path_factory.mktemp("maps")
-    src, so = d / "wrap.cpp", d / "libmaps.so"
-    src.write_text(WRAPPER)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Werror", "-I",
-                           os.path.join(REPO, "radiative3d_amd", "maps"), "-o", str(so), str(src)])
-    L = C.CDLL(str(so))
+    L = C.CDLL(host_build(d, "libmaps.so", WRAPPER, [os.path.join(REPO, "radiative3d_amd", "maps")]))
     L.maps_quads.restype = C.c_uint64
     L.maps_quads.argtypes = [C.c_uint32] * 4
     L.maps_run.restype = None

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from native_build import host_build
 from radiative3d_amd import _ffi
 from radiative3d_amd.model import range_bins, volume_desc
 from volume_views_cases import (OUT, SHAPES, azimuth_offsets, grid_desc, n_out_frames, project_numpy, random_grid,
@@ -95,11 +96,7 @@ extern "C" void views_project(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t n_
 @pytest.fixture(scope="module")
 def host_views(tmp_path_factory):
     d = tmp_path_factory.mktemp("views")
-    src, so = d / "wrap.cpp", d / "libviews.so"
-    src.write_text(WRAPPER)
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Werror", "-I",
-                           os.path.join(REPO, "radiative3d_amd", "views"), "-o", str(so), str(src)])
-    L = C.CDLL(str(so))
+    L = C.CDLL(host_build(d, "libviews.so", WRAPPER, [os.path.join(REPO, "radiative3d_amd", "views")]))
     L.views_plan.argtypes = [C.c_uint32] * 10 + [C.c_void_p]
     L.views_project.argtypes = [C.c_uint32] * 10 + [C.c_void_p] * 5
     L.views_project.restype = None

@@ -4,12 +4,12 @@ rule restated in numpy, the window sum in exact rationals with its rounding boun
 shapes the kernel is run on."""
 import ctypes as C
 import os
-import subprocess
 import tempfile
 from fractions import Fraction
 
 import numpy as np
 
+from native_build import host_build
 from radiative3d_amd import _ffi
 
 U = 2.0 ** -53
@@ -79,11 +79,8 @@ def host_windows():
     global _host, _keep
     if _host is None:
         _keep = tempfile.TemporaryDirectory(prefix="window_sums_")
-        src, so = os.path.join(_keep.name, "wrap.cpp"), os.path.join(_keep.name, "libwindows.so")
-        open(src, "w").write(WRAPPER)
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror", "-I",
-                               os.path.join(_ffi.REPO, "radiative3d_amd", "stats"), "-o", so, src])
-        L = C.CDLL(so)
+        L = C.CDLL(host_build(_keep.name, "libwindows.so", WRAPPER, [os.path.join(_ffi.REPO, "radiative3d_amd", "stats")],
+                              flags=("-O2", "-ffp-contract=off", "-fPIC", "-shared")))
         L.window_sums_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.window_sums_host.restype = None
