@@ -51,7 +51,9 @@ ENGINE_HDR := $(wildcard $(CSRC)/*.h) include/r3d.h
 #   views  the two video views of the scatter-event grid (r3d_volume_project, r3d_volume_range_bins)
 #   maps   the grid reduced along its frame axis: arrival-time, peak and total maps (r3d_volume_time_maps)
 #   arrays the travel-time image of a receiver array with jackknife errors (r3d_array_image, r3d_run_batched_array_image)
-ADDONS := stats views maps arrays
+#   precision  a run to a target standard error: the judge kernel and the rounds around it, on top of the stats add-on's
+#          C-ABI (r3d_batch_precision, r3d_run_to_precision)
+ADDONS := stats views maps arrays precision
 addon_src = $(wildcard radiative3d_amd/$(1)/*.hip)
 # (arrays/ takes the bin energy and the strand constants from stats/r3d_window_sums.h)
 addon_hdr = $(wildcard radiative3d_amd/$(1)/*.h) $(COMMON)/r3d_entry.h include/r3d.h $(if $(filter arrays,$(1)),radiative3d_amd/stats/r3d_window_sums.h)

@@ -883,6 +883,81 @@ int r3d_run_batched_array_image(r3d_engine* e, uint64_t n, uint64_t first_id, ui
                                 r3d_result* out, double* energy_se, double* counts_se, const r3d_array_image_spec* spec,
                                 r3d_array_image_result* res);
 
+/* ---- run to a target standard error: rounds of batches, judged on the device ------------
+ * How many histories a run needs is asked before every run; this call answers it by running in rounds and looking at the
+ * error bars where they lie.  radiative3d_amd/precision/r3d_precision.h has the criterion's arithmetic, built by the host too.
+ *     THE ESTIMATOR.  n_max histories in R rounds of m = n_max / R; round g runs the ids [first_id + g m, first_id +
+ *       (g + 1) m) as B batches, batch k the ids [first_id + g m + floor(k m / B), first_id + g m + floor((k + 1) m / B)),
+ *       into kept blocks that r3d_batch_partial reduces to (S_g, ss_g).  After G rounds r3d_batch_merge of the G pairs
+ *       gives T and se of N = G B batches over n = G m ids.  With n = G m, batch j = g B + k of r3d_node_run_batched's job
+ *       is [first_id + floor(j n / N), ...) = [first_id + g m + floor(k m / B), ...): the same cut, whatever G.  So a run
+ *       stopped after G rounds IS the job r3d_node_run_batched(n = G m, N = G B) runs on a node of G shards, same first_id
+ *       and seed: counts, scalars and counts_se to the bit, energies and energy_se by the same arithmetic in the same
+ *       order (to the bit on the reproducible build).  G = 1 is r3d_run_batched(m, B) to the bit of its arithmetic.
+ *     THE CRITERION (r3d_precision_spec).  An energy entry (s, b, k) -- seismometer, bin, component X, Y, Z, P, S -- is
+ *       SELECTED iff first <= s <= last, bin_begin <= b < bin_end, bit k of `mask` is set, the bin's total count
+ *       counts[s][b][0] + counts[s][b][1] >= min_count, and T > 0.  In range and mask with enough counts but T == 0: tallied
+ *       as n_zero, not selected.  A selected entry is WITHIN iff se <= rel_target * T: one fp64 multiply and one compare,
+ *       nothing to fuse.  worst = the max over the selected entries of se / T, an IEEE fp64 division (0 with none selected).
+ *       The run is MET iff n_selected >= 1 and (double)n_within >= coverage * (double)n_selected (r3d_precision.h
+ *       precision_met, the one place that evaluates it).  Everything here is an integer sum or a max of non-negative
+ *       doubles: the same bits for any launch geometry and any order.
+ *     THE MASK.  R3D_PRECISION_DEFAULT_MASK is P | S (components 3 and 4).  An axis normal to the motion -- Y of a P - SV
+ *       run -- holds rounding noise of relative error of order 1: selected, it would keep any run from ever being met.
+ *
+ * r3d_batch_precision: the judge, device level like r3d_batch_moments -- d_energy, d_energy_se [n_seis][n_bins][5] and
+ * d_counts [n_seis][n_bins][2] on `device`, only read.  One workgroup per selected receiver walks its contiguous rows;
+ * wave64 cross-lane reduction, then LDS across the waves.  WRITTEN, every row by one owner: d_per_receiver [last - first +
+ * 1][3] (selected, within, zero) and d_worst_per_receiver [last - first + 1]; then, by a second pass over those rows,
+ * d_totals [3] and d_worst [1].  No atomics.  Asynchronous on `stream`.  The shape is the call's n_seis, n_bins: the
+ * spec's n_seismometers, n_bins are not read.  REFUSED (non-zero, r3d_last_error, nothing enqueued; all checked before
+ * any HIP call): a null pointer, a size mismatch, first > last, last >= n_seis, an empty bin range or one past n_bins, a
+ * mask of 0 or with bits beyond the fifth, rel_target not finite or not > 0, coverage outside (0, 1].
+ *
+ * r3d_run_to_precision: the run.  After every round: r3d_batch_partial into slot g of [R][len] arrays on the device,
+ * r3d_batch_merge over the g + 1 slots into scratch, the judge behind it on the same stream, and the host reads the judge's
+ * four numbers -- the ONE synchronisation of a round.  It stops at the first round that is met, or after R rounds; n_max is
+ * never exceeded.  T and the scalars of the rounds run are ADDED into *out, energy_se / counts_se WRITTEN (either may be
+ * NULL), as r3d_run_batched does.  *report (its size set by the caller) is WRITTEN: rounds run, histories run, met, and
+ * per round the histories so far, n_selected, n_within, n_zero and worst; the last round's per-receiver rows go to the
+ * report's two optional arrays.  REFUSED (nothing run, *out, the se arrays and *report untouched): everything
+ * r3d_run_batched refuses with n = m (B < 2, B > 64, m < B, a pending carry chain, an event log, a production-finals
+ * buffer), R outside 1 .. R3D_PRECISION_MAX_ROUNDS, n_max not a multiple of R, a bad spec (as the judge's, against the
+ * spec's own n_seismometers x n_bins, which must be the model's), a null report or one of another size.  Out of scope: several devices, a criterion on window
+ * sums or image pixels, launching round g + 1 before round g is judged.                                              */
+#define R3D_PRECISION_MAX_ROUNDS 64
+#define R3D_PRECISION_DEFAULT_MASK 0x18u   /* P | S */
+typedef struct r3d_precision_spec {
+  uint32_t size;                    /* sizeof(r3d_precision_spec): a mismatch is refused       */
+  uint32_t first, last;             /* seismometers first .. last, inclusive                   */
+  uint32_t bin_begin, bin_end;      /* bins [bin_begin, bin_end)                               */
+  uint32_t mask;                    /* bit k: energy component k of X, Y, Z, P, S              */
+  uint32_t n_seismometers, n_bins;  /* the model's, as the sibling specs carry them      (run) */
+  uint64_t min_count;              /* a bin's n_P + n_S below this: not judged                */
+  double   rel_target;              /* se <= rel_target * T; finite, > 0                       */
+  double   coverage;                /* the share of the selected that must be within; (0, 1]   */
+} r3d_precision_spec;
+typedef struct r3d_precision_report {
+  uint32_t size;                    /* sizeof(r3d_precision_report), set by the caller         */
+  uint32_t rounds;                  /* rounds run, 1 .. R                                      */
+  uint32_t met;                     /* 1 if the last round run met the target                  */
+  uint32_t pad_;
+  uint64_t histories;               /* histories run: rounds * m                               */
+  uint64_t round_histories[R3D_PRECISION_MAX_ROUNDS];   /* so far, after round g               */
+  uint64_t n_selected[R3D_PRECISION_MAX_ROUNDS];
+  uint64_t n_within[R3D_PRECISION_MAX_ROUNDS];
+  uint64_t n_zero[R3D_PRECISION_MAX_ROUNDS];
+  double   worst[R3D_PRECISION_MAX_ROUNDS];
+  uint64_t* per_receiver;           /* [last - first + 1][3] of the last round; may be NULL    */
+  double*   worst_per_receiver;     /* [last - first + 1]    of the last round; may be NULL    */
+} r3d_precision_report;
+int r3d_batch_precision(int device, const double* d_energy, const double* d_energy_se, const uint64_t* d_counts,
+                        uint32_t n_seis, uint32_t n_bins, const r3d_precision_spec* spec, uint64_t* d_per_receiver,
+                        double* d_worst_per_receiver, uint64_t* d_totals, double* d_worst, void* stream);
+int r3d_run_to_precision(r3d_engine* e, uint64_t n_max, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                         uint32_t max_rounds, const r3d_precision_spec* spec, r3d_result* out, double* energy_se,
+                         double* counts_se, r3d_precision_report* report);
+
 /* Self-test hook: evaluates one of the kernel's own elementary functions
  * (radiative3d_amd/csrc/r3d_math.h -- the traversal uses these instead of the
  * device library's exp / log / atanh / asin / atan2 / sincos) on the device,

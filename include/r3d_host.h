@@ -192,6 +192,25 @@ int r3dh_ttimage_request(const r3dh_model* m, r3dh_ttimage_opts* rq);
 int r3dh_ttimage_plan(const r3dh_model* m, const r3dh_ttimage_opts* rq, double* distances, double* azimuths);
 int r3dh_write_ttimage(const r3dh_model* m, const r3dh_ttimage_opts* rq, const r3dh_ttimage_result* res, const char* path);
 
+/* --target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]] [--target-array=FIRST,LAST] [--target-components=LETTERS] in the
+ * model's arguments (the last two refused without the first; the first without --error-batches, with --job-error-batches,
+ * --lapse-windows, --ttimage or --reports, on more than one shard, and with a --num-phonons that is no multiple of ROUNDS
+ * or gives a round fewer histories than batches): a run to a target standard error (r3d.h r3d_run_to_precision).
+ * r3dh_precision_request: returns 1 and fills *spec (n_seismometers, n_bins and all bins the model's) and *max_rounds
+ * when the target was asked for, 0 otherwise; -1 (r3dh_last_error) if --target-array's LAST is not a seismometer of the
+ * model.  Either pointer may be NULL.
+ * r3dh_write_precision: precision.octv-style GNU/Octave text at 17 digits to `path`, from the spec, the batches of a
+ * round, the rounds allowed, the cap n_max and a run's report:  PrecisionRelTarget, PrecisionCoverage, PrecisionMinCount,
+ * PrecisionMaxRounds, PrecisionBatchesPerRound, PrecisionSeismometers [2] (first, last), PrecisionBins [2] (begin, end),
+ * PrecisionComponents (letters of XYZPS), NumPhononsCap, RoundHistories (= cap / rounds allowed), NumPhononsRun (what a
+ * script normalises by: out_mparams.octv holds the cap), RoundsRun, NumBatches (= RoundsRun x batches of a round, as in
+ * seis_NNN_err.octv), Met (0 / 1), PrecisionRounds [RoundsRun][6] (round from 1, histories so far, selected, within, zero,
+ * worst se / T) and, where the report has its two arrays, PrecisionReceivers [last - first + 1][5] (seismometer, selected,
+ * within, zero, worst, after the last round).  Returns 0 ok.                                                        */
+int r3dh_precision_request(const r3dh_model* m, r3d_precision_spec* spec, uint32_t* max_rounds);
+int r3dh_write_precision(const r3d_precision_spec* spec, uint32_t n_batches, uint32_t max_rounds, uint64_t n_max,
+                         const r3d_precision_report* report, const char* path);
+
 /* For a model built with --device-tables (scattering tables left to the engine):
  * record what r3d_engine_scatterer_stats() returned, so that the scatterer dump
  * and r3dh_scatterer_info show the engine's numbers.  Returns 0 ok.            */

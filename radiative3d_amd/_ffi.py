@@ -135,6 +135,26 @@ class ArrayImageResult(C.Structure):
                 ("curve", C.c_void_p), ("image_curve", C.c_void_p), ("image_curve_se", C.c_void_p)]
 
 
+R3D_PRECISION_MAX_ROUNDS = 64
+R3D_PRECISION_DEFAULT_MASK = 0x18   # P | S: an axis normal to the motion holds rounding noise and would never be met
+
+
+class PrecisionSpec(C.Structure):
+    """include/r3d.h r3d_precision_spec"""
+    _fields_ = [("size", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("bin_begin", C.c_uint32),
+                ("bin_end", C.c_uint32), ("mask", C.c_uint32), ("n_seismometers", C.c_uint32), ("n_bins", C.c_uint32),
+                ("min_count", C.c_uint64), ("rel_target", C.c_double), ("coverage", C.c_double)]
+
+
+class PrecisionReport(C.Structure):
+    """include/r3d.h r3d_precision_report"""
+    _fields_ = [("size", C.c_uint32), ("rounds", C.c_uint32), ("met", C.c_uint32), ("pad_", C.c_uint32),
+                ("histories", C.c_uint64), ("round_histories", C.c_uint64 * R3D_PRECISION_MAX_ROUNDS),
+                ("n_selected", C.c_uint64 * R3D_PRECISION_MAX_ROUNDS), ("n_within", C.c_uint64 * R3D_PRECISION_MAX_ROUNDS),
+                ("n_zero", C.c_uint64 * R3D_PRECISION_MAX_ROUNDS), ("worst", C.c_double * R3D_PRECISION_MAX_ROUNDS),
+                ("per_receiver", C.c_void_p), ("worst_per_receiver", C.c_void_p)]
+
+
 class TTImageOpts(C.Structure):
     """include/r3d_host.h r3dh_ttimage_opts"""
     _fields_ = [("size", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("gamma_log2", C.c_uint32),
@@ -281,6 +301,11 @@ def host_lib():
         L.r3dh_ttimage_plan.argtypes = [C.c_void_p, C.POINTER(TTImageOpts), _dp, _dp]
         L.r3dh_write_ttimage.restype = C.c_int
         L.r3dh_write_ttimage.argtypes = [C.c_void_p, C.POINTER(TTImageOpts), C.POINTER(TTImageResult), C.c_char_p]
+        L.r3dh_precision_request.restype = C.c_int
+        L.r3dh_precision_request.argtypes = [C.c_void_p, C.POINTER(PrecisionSpec), C.POINTER(C.c_uint32)]
+        L.r3dh_write_precision.restype = C.c_int
+        L.r3dh_write_precision.argtypes = [C.POINTER(PrecisionSpec), C.c_uint32, C.c_uint32, C.c_uint64,
+                                           C.POINTER(PrecisionReport), C.c_char_p]
         L.r3dh_seismometer_axes.restype = C.c_int
         L.r3dh_seismometer_axes.argtypes = [C.c_void_p, C.c_int]
         _host = L
@@ -476,6 +501,12 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_run_batched_windows.restype = C.c_int
         L.r3d_run_batched_windows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
                                               _dp, _dp, C.POINTER(WindowSpec), _dp, C.POINTER(C.c_uint64), _dp, _dp]
+        L.r3d_batch_precision.restype = C.c_int
+        L.r3d_batch_precision.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                          C.POINTER(PrecisionSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.r3d_run_to_precision.restype = C.c_int
+        L.r3d_run_to_precision.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                           C.POINTER(PrecisionSpec), C.POINTER(Result), _dp, _dp, C.POINTER(PrecisionReport)]
         L.r3d_last_error.restype = C.c_char_p
         L.r3d_version.restype = C.c_char_p
         _hip[key] = L

@@ -2,7 +2,7 @@
 // error text, the caller's device kept across the call, device scratch that frees itself, the refusals the calls on
 // the event grid share, and those of the batched runs with the way they learn their engine's device, the format of
 // the block their results come down in (ResultBlock) and the way a run is brought to the host (BatchedRun).  Host code
-// only, all inline.  An add-on (stats/, views/, maps/, arrays/) includes this and include/r3d.h and nothing from csrc/;
+// only, all inline.  An add-on (stats/, views/, maps/, arrays/, precision/) includes this and include/r3d.h and nothing from csrc/;
 // csrc/r3d_volume.hip, whose entry points are of the same kind, uses it too.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -193,6 +193,7 @@ class BatchedRun {
   int status() const { return rc; }   // of opening; non-zero: return it, nothing else is to be done
   int device() const { return dev; }
   hipStream_t stream() const { return s; }
+  void* base() const { return block.p; }   // the result block's device address (`result` has its five arrays)
   uint64_t* extra() const { return block.as<uint64_t>() + result.words(); }   // the device address behind the result block
   const uint64_t* host_extra() const { return host.data() + result.words(); }   // after close(): its `read` words
   // r3d_run_device_batched into the result block; the batches' blocks are kept where the pointers say (null: not kept)

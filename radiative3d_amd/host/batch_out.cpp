@@ -62,14 +62,38 @@ void run_image(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint
   for (int k = 0; k < 2; k++) p.fit[k] = res.fit[k], p.fit_se[k] = res.fit_se[k];
 }
 
+// --target-error: --num-phonons is the cap, run in rounds of the job's batches each and judged on the device after
+// every round (include/r3d.h r3d_run_to_precision); one line per round, and one that says whether the target was met.
+void run_precision(const BatchJob& job, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total, BatchProducts& p) {
+  const size_t A = (size_t)job.precision.last - job.precision.first + 1;
+  p.cap = n, p.receiver_rows.assign(3 * A, 0), p.receiver_worst.assign(A, 0.0);
+  p.report = r3d_precision_report{};
+  p.report.size = sizeof p.report;
+  p.report.per_receiver = p.receiver_rows.data(), p.report.worst_per_receiver = p.receiver_worst.data();
+  if (r3d_run_to_precision(e, n, 0, seed, job.batches, job.rounds, &job.precision, &total, p.energy_se.data(), p.counts_se.data(),
+                           &p.report))
+    throw Runtime(r3d_last_error());
+  const r3d_precision_report& r = p.report;
+  for (uint32_t g = 0; g < r.rounds; g++)
+    std::cout << "|  Round " << g + 1 << ": " << r.round_histories[g] << " histories, " << r.n_within[g] << " of " << r.n_selected[g]
+              << " judged entries within " << job.precision.rel_target << " (worst " << r.worst[g] << ", " << r.n_zero[g]
+              << " without energy)\n";
+  std::cout << "|  Target " << (r.met ? "met" : "NOT met") << " after " << r.rounds << " of " << job.rounds << " rounds: " << r.histories
+            << " of at most " << n << " histories run (precision.octv: NumPhononsRun)\n";
+}
+
 }  // namespace
 
 BatchJob make_batch_job(const MissionParams& mission, const Model& model) {
   BatchJob job;
   if (!mission.bRunSim || !(mission.ErrorBatches || mission.JobErrorBatches)) return job;
   job.dir = mission.OutputDir, job.batches = mission.ErrorBatches ? mission.ErrorBatches : mission.JobErrorBatches;
-  job.kind = !mission.ErrorBatches ? BatchJob::JOB_ERRORS : mission.bLapse ? BatchJob::LAPSE : mission.bTTImage ? BatchJob::IMAGE : BatchJob::ERRORS;
-  if (job.kind == BatchJob::LAPSE) {
+  job.kind = !mission.ErrorBatches ? BatchJob::JOB_ERRORS : mission.bLapse ? BatchJob::LAPSE : mission.bTTImage ? BatchJob::IMAGE
+             : mission.bTarget ? BatchJob::PRECISION : BatchJob::ERRORS;
+  if (job.kind == BatchJob::PRECISION) {
+    PrecisionRequest(model, mission, &job.precision);
+    job.rounds = mission.TargetRounds;
+  } else if (job.kind == BatchJob::LAPSE) {
     LapseRequest(model, mission, &job.lapse);
     const size_t S = (size_t)job.lapse.last - job.lapse.first + 1;
     job.lapse_distances.assign(S, 0.0), job.lapse_bins.assign(4 * S, 0), job.lapse_clipped.assign(2 * S, 0);
@@ -105,16 +129,29 @@ BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& d, r3d_no
   r3d_engine* e = r3d_node_engine(node, 0);
   if (job.kind == BatchJob::LAPSE) run_lapse(job, d, e, n, seed, total, p);
   else if (job.kind == BatchJob::IMAGE) run_image(job, d, e, n, seed, total, p);
+  else if (job.kind == BatchJob::PRECISION) run_precision(job, e, n, seed, total, p);
   else if (shards ? r3d_node_run_batched(node, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data())
                   : r3d_run_batched(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data()))
     throw Runtime(r3d_last_error());
   if (shards) std::cout << "|  Batches: " << job.batches << " over " << r3d_node_size(node) << " shards\n";
+  else if (job.kind == BatchJob::PRECISION)
+    std::cout << "|  Batches: " << batch_plan::batches_run(p.report.rounds, job.batches) << " (" << job.batches << " a round; standard "
+              << "errors from batch means)\n";
   else std::cout << "|  Batches: " << job.batches << " (standard errors from batch means)\n";
   return p;
 }
 
 void write_batch_outputs(const BatchJob& job, const Model& model, const BatchProducts& p) {
   if (job.kind == BatchJob::NONE) return;
+  if (job.kind == BatchJob::PRECISION) {   // NumBatches: those of the rounds run
+    OutputSeismometerErrors(model, p.energy_se.data(), p.counts_se.data(),
+                            (unsigned)batch_plan::batches_run(p.report.rounds, job.batches), job.dir);
+    const std::string fn = output_path(job.dir, "precision.octv");
+    std::ofstream f(fn.c_str());
+    OutputPrecision(job.precision, job.batches, job.rounds, p.cap, p.report, f);
+    if (!f) throw Runtime("cannot write " + fn);
+    return;
+  }
   OutputSeismometerErrors(model, p.energy_se.data(), p.counts_se.data(), job.batches, job.dir);
   if (job.kind != BatchJob::LAPSE && job.kind != BatchJob::IMAGE) return;
   const std::string fn = output_path(job.dir, job.kind == BatchJob::LAPSE ? "lapse.octv" : "ttimage.octv");

@@ -1,5 +1,6 @@
-// batch_out.hpp -- the batched-run stage of ./main: what --error-batches, --job-error-batches, --lapse-windows and
-// --ttimage run in place of the plain run, and what they write after it (seis_NNN_err.octv, lapse.octv, ttimage.octv).
+// batch_out.hpp -- the batched-run stage of ./main: what --error-batches, --job-error-batches, --lapse-windows, --ttimage
+// and --target-error run in place of the plain run, and what they write after it (seis_NNN_err.octv, lapse.octv,
+// ttimage.octv, precision.octv).
 // Compiled into ./main beside main.cpp (it calls r3d_run_batched* and r3d_node_run_batched of the engine's library, so
 // it is no part of libr3d_host.so); its row arithmetic is batch_plan.hpp.
 #ifndef R3DH_BATCH_OUT_HPP_
@@ -18,9 +19,10 @@ inline std::string output_path(const std::string& dir, const std::string& name) 
 
 // What the four options ask for, and where it goes.
 struct BatchJob {
-  // ERRORS: --error-batches alone; LAPSE, IMAGE: with --lapse-windows, --ttimage; JOB_ERRORS: --job-error-batches
-  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS } kind = NONE;
-  unsigned batches = 0;
+  // ERRORS: --error-batches alone; LAPSE, IMAGE, PRECISION: with --lapse-windows, --ttimage, --target-error;
+  // JOB_ERRORS: --job-error-batches
+  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION } kind = NONE;
+  unsigned batches = 0;   // (PRECISION: of a round)
   std::string dir;   // --output-dir
   // LAPSE: the request and the array's plan, [S] receivers (include/r3d_host.h r3dh_lapse_plan)
   r3dh_lapse_opts lapse{};
@@ -30,6 +32,9 @@ struct BatchJob {
   // IMAGE: the request and the array's plan, [A] receivers (include/r3d_host.h r3dh_ttimage_plan)
   r3dh_ttimage_opts tt{};
   std::vector<double> tt_distances, tt_azimuths;
+  // PRECISION: the criterion and the rounds allowed (include/r3d.h r3d_run_to_precision)
+  r3d_precision_spec precision{};
+  unsigned rounds = 0;
 };
 
 // What a batched run hands back beside its totals: every bin's standard error, then the kind's own arrays (the shapes
@@ -44,6 +49,11 @@ struct BatchProducts {
   std::vector<uint32_t> peak_bin, lit;
   uint32_t curve_made = 0;
   double fit[2] = {0, 0}, fit_se[2] = {0, 0};
+  // PRECISION: the cap, what was run, and the judge's rows of the last round (the report points into them)
+  uint64_t cap = 0;
+  r3d_precision_report report{};
+  std::vector<uint64_t> receiver_rows;
+  std::vector<double> receiver_worst;
 };
 
 // The job of a simulation run (`kind` stays NONE without one of the options).  The model is needed for the arrays:
@@ -59,7 +69,7 @@ void check_batch_job(const BatchJob& job, size_t n_shards, uint32_t report_mask)
 BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& model, r3d_node* node, uint64_t n, uint64_t seed,
                             r3d_result& total);
 
-// seis_NNN_err.octv, then lapse.octv or ttimage.octv, under the job's directory.  Throws Runtime.
+// seis_NNN_err.octv, then lapse.octv, ttimage.octv or precision.octv, under the job's directory.  Throws Runtime.
 void write_batch_outputs(const BatchJob& job, const Model& model, const BatchProducts& products);
 
 #endif

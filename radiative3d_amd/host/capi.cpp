@@ -238,6 +238,34 @@ int r3dh_write_ttimage(const r3dh_model* m, const r3dh_ttimage_opts* rq, const r
   return 1;
 }
 
+int r3dh_precision_request(const r3dh_model* m, r3d_precision_spec* spec, uint32_t* max_rounds) {
+  if (!m || !m->mission.bTarget) return 0;
+  try {
+    r3d_precision_spec made;
+    PrecisionRequest(*m->model, m->mission, &made);
+    if (spec) *spec = made;
+    if (max_rounds) *max_rounds = m->mission.TargetRounds;
+    return 1;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return -1;
+}
+
+int r3dh_write_precision(const r3d_precision_spec* spec, uint32_t n_batches, uint32_t max_rounds, uint64_t n_max,
+                         const r3d_precision_report* report, const char* path) {
+  if (!spec || !report || !path) return g_error = "r3dh_write_precision: null argument", 1;
+  try {
+    std::ofstream f(path);
+    OutputPrecision(*spec, n_batches, max_rounds, n_max, *report, f);
+    if (!f) throw Runtime(std::string("cannot write ") + path);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
 int r3dh_model_set_scatterer_stats(r3dh_model* m, int s, const double mfp[2], const double dipole[2]) {
   if (!m || !mfp || !dipole || s < 0 || s >= (int)m->model->Scatterers().size()) return 1;
   m->model->SetScattererStats(s, mfp, dipole);

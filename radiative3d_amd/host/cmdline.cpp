@@ -21,7 +21,8 @@ enum OptID {
   OPTX_DEVICES, OPTX_SCATGRID, OPTX_SCATGRID_FILE, OPTX_ERRBATCHES,
   OPTX_SCATVIEWS, OPTX_SCATVIEW_AZI, OPTX_NO_SCATGRID_FILE, OPTX_SCATMAPS, OPTX_JOBERRBATCHES,
   OPTX_LAPSE, OPTX_LAPSE_AXES, OPTX_LAPSE_GEOSPREAD, OPTX_LAPSE_RANGES, OPTX_LAPSE_ARRAY,
-  OPTX_TTIMAGE, OPTX_TTIMAGE_ARRAY, OPTX_TTIMAGE_AXES, OPTX_TTIMAGE_FIT, OPTX_TTIMAGE_NORMCURVE
+  OPTX_TTIMAGE, OPTX_TTIMAGE_ARRAY, OPTX_TTIMAGE_AXES, OPTX_TTIMAGE_FIT, OPTX_TTIMAGE_NORMCURVE,
+  OPTX_TARGET, OPTX_TARGET_ARRAY, OPTX_TARGET_COMPONENTS
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -59,7 +60,8 @@ const std::map<std::string, OptID>& option_table() {
       {"--lapse-windows", OPTX_LAPSE}, {"--lapse-axes", OPTX_LAPSE_AXES}, {"--lapse-geospread", OPTX_LAPSE_GEOSPREAD},
       {"--lapse-ranges", OPTX_LAPSE_RANGES}, {"--lapse-array", OPTX_LAPSE_ARRAY},
       {"--ttimage", OPTX_TTIMAGE}, {"--ttimage-array", OPTX_TTIMAGE_ARRAY}, {"--ttimage-axes", OPTX_TTIMAGE_AXES},
-      {"--ttimage-fit", OPTX_TTIMAGE_FIT}, {"--ttimage-normcurve", OPTX_TTIMAGE_NORMCURVE}};
+      {"--ttimage-fit", OPTX_TTIMAGE_FIT}, {"--ttimage-normcurve", OPTX_TTIMAGE_NORMCURVE},
+      {"--target-error", OPTX_TARGET}, {"--target-array", OPTX_TARGET_ARRAY}, {"--target-components", OPTX_TARGET_COMPONENTS}};
   return t;
 }
 
@@ -407,6 +409,48 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
         mission.bTTNormCurve = true;
         mission.TTCompanion = "--ttimage-normcurve";
         break;
+      case OPTX_TARGET: {
+        mission.TargetRel = o.real();
+        if (o.has()) mission.TargetCoverage = o.real();
+        const long c = o.has() ? o.integer() : (long)mission.TargetMinCount;
+        const long r = o.has() ? o.integer() : (long)mission.TargetRounds;
+        if (!(mission.TargetRel > 0) || !std::isfinite(mission.TargetRel))
+          throw Runtime("--target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]]: REL, the relative standard error aimed at, must be "
+                        "finite and > 0.");
+        if (!(mission.TargetCoverage > 0 && mission.TargetCoverage <= 1))
+          throw Runtime("--target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]]: COVERAGE, the share of the judged entries that must "
+                        "meet REL, must lie in (0, 1].");
+        if (c < 0)
+          throw Runtime("--target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]]: MINCOUNT, the arrivals a bin needs to be judged, must "
+                        "not be negative (got " + std::to_string(c) + ").");
+        if (r < 1 || r > 64)
+          throw Runtime("--target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]]: ROUNDS must be 1 .. 64 (got " + std::to_string(r) + ").");
+        mission.TargetMinCount = (unsigned long)c, mission.TargetRounds = (unsigned)r;
+        mission.bTarget = true;
+        break;
+      }
+      case OPTX_TARGET_ARRAY:
+        mission.TargetArray[0] = o.integer();
+        mission.TargetArray[1] = o.integer();
+        if (mission.TargetArray[0] < 0 || mission.TargetArray[1] < mission.TargetArray[0])
+          throw Runtime("--target-array=FIRST,LAST: seismometer indices with 0 <= FIRST <= LAST.");
+        mission.TargetCompanion = "--target-array";
+        break;
+      case OPTX_TARGET_COMPONENTS: {
+        const std::string letters = o.text();
+        unsigned mask = 0;
+        for (char ch : letters) {
+          const size_t k = std::string("XYZPS").find(ch);
+          if (k == std::string::npos)
+            throw Runtime("--target-components=LETTERS: letters of XYZPS, the energy components that are judged (got '" + letters +
+                          "').");
+          mask |= 1u << k;
+        }
+        if (!mask) throw Runtime("--target-components=LETTERS: at least one letter of XYZPS.");
+        mission.TargetMask = mask;
+        mission.TargetCompanion = "--target-components";
+        break;
+      }
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }
@@ -449,6 +493,36 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
                   "out of scope.");
   if (mission.bTTNormCurve && mission.TTFit[0] == 0)
     throw Runtime("--ttimage-normcurve needs --ttimage-fit=IBEGIN,IEND: the curve's range window comes from the fit's array.");
+  // a run to a target standard error is one device's batched run, in rounds
+  if (mission.TargetCompanion && !mission.bTarget)
+    throw Runtime(std::string(mission.TargetCompanion) + " needs --target-error: it only says which entries are judged.");
+  if (mission.bTarget) {
+    const unsigned long shards = mission.Devices.empty() ? (unsigned long)std::max(1, mission.Gpus) : mission.Devices.size();
+    if (mission.JobErrorBatches)
+      throw Runtime("--target-error cannot be combined with --job-error-batches: the rounds are judged where ONE device's "
+                    "batch blocks lie (r3d_run_to_precision).  Use --error-batches=B.");
+    if (!mission.ErrorBatches)
+      throw Runtime("--target-error needs --error-batches=B: every round runs as B batches, and the standard errors that are "
+                    "judged come from the batches of all rounds so far.");
+    if (mission.bLapse)
+      throw Runtime("--target-error cannot be combined with --lapse-windows (the window sums need one run's batch blocks, the "
+                    "rounds keep only their moments): out of scope.");
+    if (mission.bTTImage)
+      throw Runtime("--target-error cannot be combined with --ttimage (the image needs one run's batch blocks, the rounds keep "
+                    "only their moments): out of scope.");
+    if (ReportMaskFromKeywords(mission.Reports))
+      throw Runtime("--target-error cannot be combined with --reports (the event log's launches run one at a time).");
+    if (shards > 1)
+      throw Runtime("--target-error runs on one device: --gpus / --devices name " + std::to_string(shards) +
+                    " shards (a run in rounds over several devices is not built).");
+    const long n = par.NumPhonons, R = (long)mission.TargetRounds;
+    if (n < 0 || n % R)
+      throw Runtime("--target-error: --num-phonons (" + std::to_string(n) + "), the cap, must be a multiple of ROUNDS (" +
+                    std::to_string(R) + "): every round runs the same number of histories.");
+    if (n / R < (long)mission.ErrorBatches)
+      throw Runtime("--target-error: a round of --num-phonons / ROUNDS = " + std::to_string(n / R) + " histories is fewer than the " +
+                    std::to_string(mission.ErrorBatches) + " batches of --error-batches.");
+  }
   // the views and the maps are made from the grid: none of their options means anything without it
   if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile || mission.bScatterMaps))
     throw Runtime(std::string(mission.bScatterViews ? "--scatter-views" : mission.bViewAzimuth ? "--scatter-view-azimuth"

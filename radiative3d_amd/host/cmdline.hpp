@@ -7,7 +7,8 @@
 // (cmdline.cpp:343-390).  Engine-only additions: --seed, --gpus, --devices, --host-tables / --device-tables,
 // --scatter-grid / --scatter-grid-file (the scatter-event histogram of a video run, written as a file),
 // --error-batches / --job-error-batches (per-bin standard errors), --lapse-windows and its four companions (lapse-window
-// energies and coda ratios with batch errors), --ttimage and its four (the array's travel-time image with jackknife errors).
+// energies and coda ratios with batch errors), --ttimage and its four (the array's travel-time image with jackknife errors),
+// --target-error and its two (a run to a target standard error, in rounds judged on the GPU).
 #ifndef R3DH_CMDLINE_HPP_
 #define R3DH_CMDLINE_HPP_
 
@@ -74,6 +75,18 @@ struct MissionParams {
   double TTGamma = 2.0, TTNorm = 0.3, TTAxes[3] = {1.0, 1.0, 1.0}, TTNormCurve[2] = {0.0, 0.0};
   long TTArray[2] = {0, -1};              // LAST < 0: through the last receiver
   long TTFit[2] = {0, 0};                 // 0, 0: no fit
+  // --target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]]: run to a target standard error (include/r3d.h r3d_run_to_precision)
+  // -- --num-phonons is the cap, run in ROUNDS rounds of the B batches of --error-batches each and judged on the GPU after
+  // every round: the run stops when the share COVERAGE of the judged entries (bins with at least MINCOUNT arrivals) has
+  // se <= REL * T; precision.octv says what was run.  --target-array=FIRST,LAST the receivers judged (default all),
+  // --target-components=letters of XYZPS (default PS).  COVERAGE, MINCOUNT and ROUNDS default to 0.9, 16, 16: defaults,
+  // not measurements.
+  bool bTarget = false;
+  const char* TargetCompanion = nullptr;  // one of the two that was given (they are refused without --target-error)
+  double TargetRel = 0.0, TargetCoverage = 0.9;
+  unsigned long TargetMinCount = 16;
+  unsigned TargetRounds = 16, TargetMask = 0x18;   // P | S
+  long TargetArray[2] = {0, -1};          // LAST < 0: through the last receiver
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

@@ -58,6 +58,13 @@ void TTImageRequest(const Model& model, const MissionParams& mission, r3dh_ttima
 void TTImagePlan(const Model& model, const r3dh_ttimage_opts& rq, double* distances, double* azimuths);
 void OutputTTImage(const Model& model, const r3dh_ttimage_opts& rq, const r3dh_ttimage_result& res, std::ostream& out);
 
+// precision.octv of --target-error (include/r3d_host.h r3dh_write_precision has the file's items): the target, the
+// selection, what was run and the judge's tables (their rows are batch_plan.hpp's).  Needs no model.  PrecisionRequest
+// fills *spec from the mission (throws if --target-array names a receiver the model does not have).
+void PrecisionRequest(const Model& model, const MissionParams& mission, r3d_precision_spec* spec);
+void OutputPrecision(const r3d_precision_spec& spec, unsigned n_batches, unsigned max_rounds, uint64_t n_max,
+                     const r3d_precision_report& report, std::ostream& out);
+
 // --reports keywords (reference main.cpp:223-258) -> R3D_RPT_* mask.  `csv` is the keyword
 // list as given ("ALL_ON", "GEN,SCT,REF", "SCATTERS", ...); empty = none.  ApplyReportKeyword: `mask` after ONE
 // keyword of the list; both throw the one sentence that names the valid keywords for any other word.

@@ -4,14 +4,16 @@
 // ("@@ __PHASE__", "#  R3D_GRID:", "#  BEGIN SCATTERER DUMP:"), same output
 // files.  The N-phonon loop itself (Model::RunSimulation, model.cpp:602-633)
 // is one call into the engine's C-ABI.  What a run with --scatter-grid writes afterwards (the grid, its views, its maps)
-// is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches, --lapse-windows and --ttimage run
-// and write (the batched runs, seis_NNN_err.octv, lapse.octv, ttimage.octv) is the stage of batch_out.cpp.  This file
+// is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches, --lapse-windows, --ttimage and
+// --target-error run and write (the batched runs, seis_NNN_err.octv, lapse.octv, ttimage.octv, precision.octv) is the
+// stage of batch_out.cpp.  This file
 // makes both jobs, has them checked before the node is built, and calls each once to run and once to write.
 //
 // Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B`,
-// `--job-error-batches=N` (error bars of a job on any number of shards), `--lapse-windows` (lapse.octv) and `--ttimage`
-// (ttimage.octv) are accepted (the reference seeds from the clock,
-// is single-process, has no event histogram and no error bars); the `--reports` stream is written
+// `--job-error-batches=N` (error bars of a job on any number of shards), `--lapse-windows` (lapse.octv), `--ttimage`
+// (ttimage.octv) and `--target-error` (a run that stops when its error bars are good enough; precision.octv) are accepted
+// (the reference seeds from the clock, is single-process, has no event histogram and no error bars, and takes its phonon
+// count from a hand-tuned table); the `--reports` stream is written
 // after the run, grouped by history, where the reference writes its lines as they happen (the engine appends binary
 // records in HBM: include/r3d.h r3d_event); tables are built in HBM unless `--host-tables` is given.
 #include <cstdio>
@@ -241,7 +243,17 @@ int main(int argc, char* argv[]) {
               << "--ttimage-array=FIRST,LAST (default all)  --ttimage-axes=X,Y,Z (default 1,1,1)  --ttimage-fit=IBEGIN,IEND: the power\n"
               << "law Sum(E dt) = c X^q over the array's 1-based points IBEGIN .. IEND (normcurve_fitpowerlaw.m) with its jackknife, and\n"
               << "the image normalised by that curve  --ttimage-normcurve=C,Q (with --ttimage-fit): a curve given outright in its place.\n"
-              << "Not in one run with --lapse-windows or --job-error-batches (out of scope)\n\n";
+              << "Not in one run with --lapse-windows or --job-error-batches (out of scope)\n"
+              << "--target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]] (with --error-batches=B; one device): run to a target standard\n"
+              << "error -- --num-phonons is the cap (never exceeded, a multiple of ROUNDS), run in ROUNDS rounds of B batches each and\n"
+              << "judged on the GPU after every round; the run stops when the share COVERAGE of the judged entries (bins with at\n"
+              << "least MINCOUNT arrivals and energy) has se <= REL * T, or at the cap, which exits 0 with a line that says so.\n"
+              << "COVERAGE 0.9, MINCOUNT 16 and ROUNDS 16 are defaults, not measurements.  seis_NNN.octv and seis_NNN_err.octv as\n"
+              << "--error-batches writes them (NumBatches = rounds run x B), and precision.octv: the target, the rounds' table and\n"
+              << "NumPhononsRun -- what a script normalises by, since out_mparams.octv holds the cap.\n"
+              << "--target-array=FIRST,LAST (seismometer indices; default all)  --target-components=LETTERS of XYZPS (default PS:\n"
+              << "an axis normal to the motion holds rounding noise and would never be met).  Not in one run with --lapse-windows,\n"
+              << "--ttimage, --job-error-batches or --reports\n\n";
     return 0;
   }
   // A simulation run makes its tables where it uses them (seconds of host work and GBs of upload

@@ -246,6 +246,20 @@ class Model:
         return int(min_count.value)
 
     @property
+    def precision_request(self):
+        """What --target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]] and its companions (--target-array, --target-components)
+        asked for: None, or dict(first, last, mask, min_count, rel, coverage, rounds) -- Engine.run_to_precision's
+        arguments of the same names (include/r3d_host.h r3dh_precision_request)."""
+        spec, rounds = _ffi.PrecisionSpec(), C.c_uint32(0)
+        rc = self._lib.r3dh_precision_request(self._h, C.byref(spec), C.byref(rounds))
+        if rc < 0:
+            raise RuntimeError("precision_request failed: " + self._lib.r3dh_last_error().decode())
+        if rc == 0:
+            return None
+        return dict(first=int(spec.first), last=int(spec.last), mask=int(spec.mask), min_count=int(spec.min_count),
+                    rel=spec.rel_target, coverage=spec.coverage, rounds=int(rounds.value))
+
+    @property
     def lapse_request(self):
         """What --lapse-windows[=V,T0,B1,E1,B2,E2] and its companions (--lapse-axes, --lapse-geospread, --lapse-ranges,
         --lapse-array) asked for: None, or dict(first, last, phase_edge, windows, axes, geospread, ranges) -- the array's
@@ -669,6 +683,56 @@ def batch_merge(energy_sum, energy_ss, counts_sum, counts_ss, n_batches, scalars
     return energy, counts, scalars, energy_se, counts_se
 
 
+def precision_spec(n_seismometers, n_bins, first, last, bins=None, mask=_ffi.R3D_PRECISION_DEFAULT_MASK, min_count=16,
+                   rel=0.1, coverage=0.9):
+    """An r3d_precision_spec (include/r3d.h): the receivers first .. last (inclusive), the bins [bins[0], bins[1]) (None:
+    all), the component mask over X, Y, Z, P, S (default P | S: an axis normal to the motion holds rounding noise and
+    would keep any run from being met), and the target -- an entry of a bin with at least min_count arrivals is within
+    when se <= rel * T, the run is met when the share `coverage` of the selected entries is.  The defaults are
+    defaults, not measurements."""
+    lo, hi = (0, n_bins) if bins is None else bins
+    return _ffi.PrecisionSpec(C.sizeof(_ffi.PrecisionSpec), first, last, lo, hi, mask, n_seismometers, n_bins, min_count,
+                              rel, coverage)
+
+
+def precision_judge(energy, energy_se, counts, first, last, bins=None, mask=_ffi.R3D_PRECISION_DEFAULT_MASK, min_count=16,
+                    rel=0.1, coverage=0.9, outputs=None, stream=None):
+    """r3d_batch_precision on torch tensors of one device: energy, energy_se [S, n_bins, 5] float64 and counts
+    [S, n_bins, 2] of a 64-bit integer type, judged against precision_spec(...) where they lie.  Returns (per_receiver
+    [last - first + 1, 3] int64 -- selected, within, zero --, worst_per_receiver [last - first + 1], totals [3] int64,
+    worst [1]) on the device; `outputs` gives the four tensors instead (rows beyond the selected receivers are left
+    alone).  Asynchronous on `stream` (a raw hipStream_t; None: torch's current one)."""
+    import torch
+    lib = _ffi.hip_lib()
+    dev = energy.device
+    if energy.dim() != 3 or energy.shape[2] != _ffi.R3D_N_ENERGY or energy.dtype != torch.float64 or not energy.is_cuda:
+        raise ValueError("energy must be a float64 tensor [S, n_bins, 5] on a GPU")
+    S, nb = int(energy.shape[0]), int(energy.shape[1])
+    if energy_se.shape != energy.shape or energy_se.dtype != torch.float64 or energy_se.device != dev:
+        raise ValueError("energy_se must be shaped like energy, float64, on its GPU")
+    if tuple(counts.shape) != (S, nb, _ffi.R3D_N_COUNT) or counts.element_size() != 8 or counts.dtype.is_floating_point or \
+            counts.device != dev:
+        raise ValueError("counts must be a 64-bit integer tensor [S, n_bins, 2] on the energies' GPU")
+    if not (energy.is_contiguous() and energy_se.is_contiguous() and counts.is_contiguous()):
+        raise ValueError("the three arrays must be contiguous")
+    spec = precision_spec(S, nb, first, last, bins, mask, min_count, rel, coverage)
+    A = max(int(last) - int(first) + 1, 1)
+    if outputs is None:
+        outputs = (torch.zeros((A, 3), dtype=torch.int64, device=dev), torch.zeros(A, dtype=torch.float64, device=dev),
+                   torch.zeros(3, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.float64, device=dev))
+    rows, worst_rows, totals, worst = outputs
+    for t, n in ((rows, 3 * A), (worst_rows, A), (totals, 3), (worst, 1)):
+        if t.device != dev or not t.is_contiguous() or t.numel() < n or t.element_size() != 8:
+            raise ValueError("outputs must be contiguous 8-byte tensors of at least the selected receivers' size on the GPU")
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    if lib.r3d_batch_precision(dev.index or 0, energy.data_ptr(), energy_se.data_ptr(), counts.data_ptr(), S, nb,
+                               C.byref(spec), rows.data_ptr(), worst_rows.data_ptr(), totals.data_ptr(), worst.data_ptr(),
+                               stream):
+        raise RuntimeError("r3d_batch_precision failed: " + lib.r3d_last_error().decode())
+    return rows, worst_rows, totals, worst
+
+
 def run_model(model, n, first_id=0, seed=0x5EED, n_gpus=1, devices=None):
     """r3d_run_model: the whole seam in one call, sharded over devices 0 .. n_gpus-1 -- or, with
     `devices`, r3d_run_model_on: shard g on devices[g] (a device may be named more than once)."""
@@ -991,6 +1055,38 @@ class Engine:
         res.counts[:] = counts.cpu().numpy().view(np.uint64)
         res.set_scalars(scalars.cpu().numpy().view(np.uint64))
         return res, ese.cpu().numpy(), cse.cpu().numpy(), be.cpu().numpy(), bc.cpu().numpy().view(np.uint64)
+
+    def run_to_precision(self, n_max, n_batches, rounds, first, last, bins=None, mask=_ffi.R3D_PRECISION_DEFAULT_MASK,
+                         min_count=16, rel=0.1, coverage=0.9, first_id=0, seed=0x5EED, result=None):
+        """r3d_run_to_precision: at most n_max histories in `rounds` rounds of n_max / rounds, each n_batches batches,
+        judged on the GPU after every round against precision_spec(first, last, bins, mask, min_count, rel, coverage);
+        the run stops at the first round that is met.  Returns (Result, energy_se, counts_se, report): what
+        Node.run_batched gives for the rounds run as shards (the totals ADDED into `result` when one is given), and
+        report = {rounds, histories, met, round_histories, n_selected, n_within, n_zero, worst -- one entry per round
+        run --, per_receiver [last - first + 1, 3] (selected, within, zero) and worst_per_receiver of the last round}."""
+        m = self.model
+        res = result if result is not None else m.new_result()
+        shape = (m.n_seismometers, m.n_bins)
+        ese, cse = np.zeros(shape + (_ffi.R3D_N_ENERGY,)), np.zeros(shape + (_ffi.R3D_N_COUNT,))
+        spec = precision_spec(m.n_seismometers, m.n_bins, first, last, bins, mask, min_count, rel, coverage)
+        A = max(int(last) - int(first) + 1, 1)
+        rows, worst_rows = np.zeros((A, 3), dtype=np.uint64), np.zeros(A)
+        rep = _ffi.PrecisionReport()
+        rep.size = C.sizeof(rep)
+        rep.per_receiver, rep.worst_per_receiver = rows.ctypes.data, worst_rows.ctypes.data
+        c = res._as_c()
+        if self._lib.r3d_run_to_precision(self._e, n_max, first_id, seed, n_batches, rounds, C.byref(spec), C.byref(c),
+                                          ese.ctypes.data_as(_ffi._dp), cse.ctypes.data_as(_ffi._dp), C.byref(rep)):
+            raise RuntimeError("r3d_run_to_precision failed: " + self._lib.r3d_last_error().decode())
+        res._from_c(c)
+        G = rep.rounds
+        report = {"rounds": G, "histories": rep.histories, "met": bool(rep.met),
+                  "round_histories": np.array(rep.round_histories[:G], dtype=np.uint64),
+                  "n_selected": np.array(rep.n_selected[:G], dtype=np.uint64),
+                  "n_within": np.array(rep.n_within[:G], dtype=np.uint64),
+                  "n_zero": np.array(rep.n_zero[:G], dtype=np.uint64), "worst": np.array(rep.worst[:G], dtype=np.float64),
+                  "per_receiver": rows, "worst_per_receiver": worst_rows}
+        return res, ese, cse, report
 
     def run_batched_windows(self, n, n_batches, bins, weights, first_id=0, seed=0x5EED, keep_batch_windows=False):
         """run_batched that also sums lapse windows where the batch blocks lie (include/r3d.h r3d_run_batched_windows):
