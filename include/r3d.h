@@ -883,6 +883,77 @@ int r3d_run_batched_array_image(r3d_engine* e, uint64_t n, uint64_t first_id, ui
                                 r3d_result* out, double* energy_se, double* counts_se, const r3d_array_image_spec* spec,
                                 r3d_array_image_result* res);
 
+/* ---- the envelope shape per receiver with jackknife errors -----------------------------
+ * What an envelope study reads off a receiver's trace -- peak delay and envelope broadening, the observables the
+ * heterogeneity parameters (r3d_scatterer.het: nu, eps, a, kappa) are fitted to -- one number per receiver WITH an error
+ * bar: how late the envelope's peak comes behind a phase onset, how long it takes to fall to half of it, where its
+ * centroid lies and how wide it is, after the smoothing vis/seisplot/envcompare.m prepares an envelope with.  A peak
+ * position, a crossing and a ratio of moments are nonlinear functions of a whole row, so none of these errors follows
+ * from the per-bin errors: they are jackknives over the batch blocks where they lie.
+ * radiative3d_amd/shapes/r3d_envelope_shape.h has the arithmetic:
+ *     ROWS over a receiver's window of bins [b0, b1), n = b1 - b0 (r3d_window_bins makes it): per bin the weighted energy
+ *       e_j of batch j (the window sum's e_b; weights finite and >= 0), the total t and, for B >= 2, t_(j) = (L_j + R_j)
+ *       B/(B-1) from prefix and suffix sums (r3d_array_image's scans) -- never t - e_j.
+ *     SMOOTHING, `smooth` = m passes, each made from the whole pass before: S(v)[0] = 0.75 v[0] + 0.25 v[1], S(v)[n-1] =
+ *       0.75 v[n-1] + 0.25 v[n-2], otherwise S(v)[k] = (0.25 v[k-1] + 0.5 v[k]) + 0.25 v[k+1]; n == 1: S(v) = v.  u = S^m(row).
+ *     SIX NUMBERS of u (R3D_ENVELOPE_N_SHAPE), times in bins from the window's first bin:  0 E = rowsum(u) (the window
+ *       sum's strands and tree)  1 P = rowmax(u), kp the first bin that holds it  2 tp = kp + d, d the vertex of the
+ *       parabola through bins kp-1, kp, kp+1 (|d| <= 0.5; 0 at the window's ends)  3 tq = (kq - 1) + (u[kq-1] - h) /
+ *       (u[kq-1] - u[kq]) with h = 0.5 P and kq the smallest k > kp with u[k] <= h; none: NaN, the row is undecayed
+ *       4 the centroid c = rowsum(k u[k]) / E  5 the width sqrt(rowsum((k - c)^2 u[k]) / E), a second pass about c.
+ *     A row with P not > 0 or n == 0 is dead: E = P = +0.0, the other four NaN, lit = 0.  A window with b0 > b1 or b1 >
+ *       n_bins is never read through: dead, and counted in bad.
+ *     se, B >= 2: every number again from every t_(j), smoothed on its own with its own kp, kq and c; se = sqrt((B-1)/B
+ *       sum_j (v_(j) - mean)^2) as r3d_array_image takes it; NaN as soon as one value is NaN.  The se of tp and tq is only
+ *       as good as the peak is sharp and the crossing steep against the noise between batches (r3d_envelope_shape.h).
+ *     The same bits on every run, machine and launch geometry; the header derives the rounding bounds.
+ *
+ * r3d_envelope_shape: device level, like r3d_array_image -- B >= 1 batch-major blocks d_batch_energy [B][n_seis][n_bins][5]
+ * on `device`, only read; the array is the receivers first .. last, A of them; spec->d_bins [A][2] (b0, b1) on the device.
+ * WRITTEN, every entry by one work-item: d_shape [A][6]; d_shape_se [A][6]; d_envelope [A][n_bins] (u of the total row at
+ * the window's bins, +0.0 elsewhere) and d_envelope_se (its jackknife per bin, +0.0 elsewhere); d_peak_bin, d_half_bin [A]
+ * (absolute bins of kp and kq; 0xFFFFFFFF: dead / undecayed); d_lit [A] (u32; 1 where the row is alive); d_bad (one
+ * uint64).  Every output but d_shape may be NULL; an se needs B >= 2.  No atomics, fixed order, 64-bit offsets; the rows
+ * pass through scratch taken from and returned to the stream's memory pool.  Asynchronous on `stream`.  REFUSED (non-zero,
+ * r3d_last_error, nothing enqueued, no buffer touched; all checked before any HIP call): a null blocks, spec, bins or
+ * shape pointer, a size mismatch, n_batches == 0, B > 64, n_bins == 0, last < first, last >= n_seismometers, a weight
+ * that is negative or not finite, smooth > R3D_ENVELOPE_MAX_SMOOTH, an se array with B < 2.
+ *
+ * r3d_run_batched_envelope_shape: r3d_run_batched (same arguments, refusals, out / energy_se / counts_se) that keeps its
+ * batch blocks on the device, makes the shape there and reads back only the small arrays of *res, all WRITTEN.  For THIS
+ * call spec->d_bins is a HOST array, checked here: a pair with b0 > b1 or b1 > n_bins is refused, as is a spec whose
+ * n_seismometers / n_bins are not the model's, a null res or one of another size, a null shape or shape_se.  A refusal
+ * touches nothing.  Out of scope: combining this call in one run with r3d_run_batched_windows or
+ * r3d_run_batched_array_image, and a job sharded over several devices (r3d_node_run_batched has no shape call).        */
+#define R3D_ENVELOPE_MAX_SMOOTH 64
+#define R3D_ENVELOPE_N_SHAPE 6
+typedef struct r3d_envelope_spec {
+  uint32_t size;                    /* sizeof(r3d_envelope_spec): a mismatch is refused        */
+  uint32_t n_seismometers, n_bins;
+  uint32_t first, last;             /* the array: seismometers first .. last                   */
+  uint32_t smooth;                  /* three-point passes, 0 .. R3D_ENVELOPE_MAX_SMOOTH        */
+  uint32_t pad_;
+  const uint32_t* d_bins;           /* [A][2] b0, b1; device (the run: host)                   */
+  double   weight[R3D_N_ENERGY];
+} r3d_envelope_spec;
+typedef struct r3d_envelope_result {
+  uint32_t size;                    /* sizeof(r3d_envelope_result)                             */
+  uint32_t pad_;
+  double*   shape;                  /* [A][6]                                                  */
+  double*   shape_se;               /* [A][6]                                                  */
+  double*   envelope;               /* [A][n_bins]  may be NULL                                */
+  double*   envelope_se;            /* [A][n_bins]  may be NULL                                */
+  uint32_t* peak_bin;               /* [A]          may be NULL                                */
+  uint32_t* half_bin;               /* [A]          may be NULL                                */
+  uint32_t* lit;                    /* [A]          may be NULL                                */
+} r3d_envelope_result;
+int r3d_envelope_shape(int device, uint32_t n_batches, const double* d_batch_energy, const r3d_envelope_spec* spec,
+                       double* d_shape, double* d_shape_se, double* d_envelope, double* d_envelope_se, uint32_t* d_peak_bin,
+                       uint32_t* d_half_bin, uint32_t* d_lit, uint64_t* d_bad, void* stream);
+int r3d_run_batched_envelope_shape(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                                   r3d_result* out, double* energy_se, double* counts_se, const r3d_envelope_spec* spec,
+                                   r3d_envelope_result* res);
+
 /* ---- run to a target standard error: rounds of batches, judged on the device ------------
  * How many histories a run needs is asked before every run; this call answers it by running in rounds and looking at the
  * error bars where they lie.  radiative3d_amd/precision/r3d_precision.h has the criterion's arithmetic, built by the host too.

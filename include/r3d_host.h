@@ -192,6 +192,49 @@ int r3dh_ttimage_request(const r3dh_model* m, r3dh_ttimage_opts* rq);
 int r3dh_ttimage_plan(const r3dh_model* m, const r3dh_ttimage_opts* rq, double* distances, double* azimuths);
 int r3dh_write_ttimage(const r3dh_model* m, const r3dh_ttimage_opts* rq, const r3dh_ttimage_result* res, const char* path);
 
+/* --envelope-shape[=V,T0,O,E[,SMOOTH]] [--envelope-array=FIRST,LAST] [--envelope-axes=X,Y,Z] in the model's arguments (the
+ * last two refused without the first; the first without --error-batches and with --job-error-batches, --lapse-windows,
+ * --ttimage, --target-error or --reports): per receiver of an array the shape of its smoothed envelope behind a phase edge
+ * with jackknife errors from the batches (r3d.h r3d_run_batched_envelope_shape).  Defaults: the lapse option's phase edge
+ * 3.6, 0; the window from the edge to the end of the trace (window[1] = NaN says "to the end"); SMOOTH 8.
+ * r3dh_envshape_request: returns 1 and fills *rq when the shape was asked for, 0 otherwise; -1 (r3dh_last_error) if
+ * --envelope-array's LAST is not a seismometer of the model.
+ * r3dh_envshape_plan: for the A = last - first + 1 receivers of the array, distances [A] as r3dh_lapse_plan gives them,
+ * bins [A][2] (b0, b1 by r3d.h's bin rule r3d_window_bins from the edge and the window's O .. E; with E = NaN the rule's
+ * begin and b1 = n_bins) and clipped [A].  0 ok.
+ * r3dh_write_envshape: envshape.octv-style GNU/Octave text at 17 digits to `path`, rows the array's receivers in order,
+ * 0-based indices:  EnvSeismometers [A], EnvBatches, EnvDistances [A], EnvPhaseEdge [2], EnvWindow [2] (O, E; E NaN: to
+ * the end of the trace), EnvAxes [3], EnvSmooth, EnvNumBins, EnvBins [A][2], EnvClipped [A], EnvLit [A] (0: a window without
+ * energy), EnvUndecayed [A] (1: alive, but never down to half its peak behind it), EnvPeakBin / EnvHalfBin [A] (absolute
+ * bins; NaN: none), then the six numbers, each [A] with its _se: EnvEnergy (E times dt), EnvPeak (as it is), EnvPeakTime,
+ * EnvHalfTime, EnvCentroid (seconds behind the window's begin: (t + 0.5) dt, se times dt), EnvWidth (times dt); and
+ * EnvEnvelope / EnvEnvelope_se [A][n_bins], the smoothed envelope (+0.0 outside the window).  Returns 0 ok.            */
+typedef struct r3dh_envshape_opts {
+  uint32_t size;                 /* sizeof(r3dh_envshape_opts)                                   */
+  uint32_t first, last;          /* the array: seismometers first .. last                        */
+  uint32_t smooth;               /* three-point passes, 0 .. 64                                  */
+  double   phase_edge[2];        /* v, t0                                                         */
+  double   window[2];            /* o, e: seconds behind the edge; e = NaN: to the trace's end   */
+  double   axes[3];              /* weights of the trace's X, Y, Z                               */
+} r3dh_envshape_opts;
+typedef struct r3dh_envshape_result {
+  uint32_t size;                 /* sizeof(r3dh_envshape_result)                                 */
+  uint32_t n_batches;
+  const double*   distances;     /* [A]     r3dh_envshape_plan's                                 */
+  const uint32_t* bins;          /* [A][2]                                                       */
+  const int32_t*  clipped;       /* [A]                                                          */
+  const double*   shape;         /* [A][6]  in bins, as r3d_run_batched_envelope_shape gives it  */
+  const double*   shape_se;      /* [A][6]                                                       */
+  const double*   envelope;      /* [A][n_bins]                                                  */
+  const double*   envelope_se;   /* [A][n_bins]                                                  */
+  const uint32_t* peak_bin;      /* [A]                                                          */
+  const uint32_t* half_bin;      /* [A]                                                          */
+  const uint32_t* lit;           /* [A]                                                          */
+} r3dh_envshape_result;
+int r3dh_envshape_request(const r3dh_model* m, r3dh_envshape_opts* rq);
+int r3dh_envshape_plan(const r3dh_model* m, const r3dh_envshape_opts* rq, double* distances, uint32_t* bins, int32_t* clipped);
+int r3dh_write_envshape(const r3dh_model* m, const r3dh_envshape_opts* rq, const r3dh_envshape_result* res, const char* path);
+
 /* --target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]] [--target-array=FIRST,LAST] [--target-components=LETTERS] in the
  * model's arguments (the last two refused without the first; the first without --error-batches, with --job-error-batches,
  * --lapse-windows, --ttimage or --reports, on more than one shard, and with a --num-phonons that is no multiple of ROUNDS

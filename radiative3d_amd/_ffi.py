@@ -135,6 +135,23 @@ class ArrayImageResult(C.Structure):
                 ("curve", C.c_void_p), ("image_curve", C.c_void_p), ("image_curve_se", C.c_void_p)]
 
 
+R3D_ENVELOPE_MAX_SMOOTH, R3D_ENVELOPE_N_SHAPE = 64, 6
+
+
+class EnvelopeSpec(C.Structure):
+    """include/r3d.h r3d_envelope_spec"""
+    _fields_ = [("size", C.c_uint32), ("n_seismometers", C.c_uint32), ("n_bins", C.c_uint32), ("first", C.c_uint32),
+                ("last", C.c_uint32), ("smooth", C.c_uint32), ("pad_", C.c_uint32), ("d_bins", C.c_void_p),
+                ("weight", C.c_double * R3D_N_ENERGY)]
+
+
+class EnvelopeResult(C.Structure):
+    """include/r3d.h r3d_envelope_result"""
+    _fields_ = [("size", C.c_uint32), ("pad_", C.c_uint32), ("shape", C.c_void_p), ("shape_se", C.c_void_p),
+                ("envelope", C.c_void_p), ("envelope_se", C.c_void_p), ("peak_bin", C.c_void_p), ("half_bin", C.c_void_p),
+                ("lit", C.c_void_p)]
+
+
 R3D_PRECISION_MAX_ROUNDS = 64
 R3D_PRECISION_DEFAULT_MASK = 0x18   # P | S: an axis normal to the motion holds rounding noise and would never be met
 
@@ -183,6 +200,19 @@ class LapseResult(C.Structure):
     _fields_ = [("size", C.c_uint32), ("n_batches", C.c_uint32), ("distances", C.c_void_p), ("bins", C.c_void_p),
                 ("clipped", C.c_void_p), ("window_energy", C.c_void_p), ("window_se", C.c_void_p),
                 ("window_counts", C.c_void_p), ("batch_window_energy", C.c_void_p)]
+
+
+class EnvShapeOpts(C.Structure):
+    """include/r3d_host.h r3dh_envshape_opts"""
+    _fields_ = [("size", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("smooth", C.c_uint32),
+                ("phase_edge", C.c_double * 2), ("window", C.c_double * 2), ("axes", C.c_double * 3)]
+
+
+class EnvShapeResult(C.Structure):
+    """include/r3d_host.h r3dh_envshape_result"""
+    _fields_ = [("size", C.c_uint32), ("n_batches", C.c_uint32), ("distances", C.c_void_p), ("bins", C.c_void_p),
+                ("clipped", C.c_void_p), ("shape", C.c_void_p), ("shape_se", C.c_void_p), ("envelope", C.c_void_p),
+                ("envelope_se", C.c_void_p), ("peak_bin", C.c_void_p), ("half_bin", C.c_void_p), ("lit", C.c_void_p)]
 
 
 class MapsHeader(C.Structure):
@@ -301,6 +331,12 @@ def host_lib():
         L.r3dh_ttimage_plan.argtypes = [C.c_void_p, C.POINTER(TTImageOpts), _dp, _dp]
         L.r3dh_write_ttimage.restype = C.c_int
         L.r3dh_write_ttimage.argtypes = [C.c_void_p, C.POINTER(TTImageOpts), C.POINTER(TTImageResult), C.c_char_p]
+        L.r3dh_envshape_request.restype = C.c_int
+        L.r3dh_envshape_request.argtypes = [C.c_void_p, C.POINTER(EnvShapeOpts)]
+        L.r3dh_envshape_plan.restype = C.c_int
+        L.r3dh_envshape_plan.argtypes = [C.c_void_p, C.POINTER(EnvShapeOpts), _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+        L.r3dh_write_envshape.restype = C.c_int
+        L.r3dh_write_envshape.argtypes = [C.c_void_p, C.POINTER(EnvShapeOpts), C.POINTER(EnvShapeResult), C.c_char_p]
         L.r3dh_precision_request.restype = C.c_int
         L.r3dh_precision_request.argtypes = [C.c_void_p, C.POINTER(PrecisionSpec), C.POINTER(C.c_uint32)]
         L.r3dh_write_precision.restype = C.c_int
@@ -498,6 +534,12 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_run_batched_array_image.restype = C.c_int
         L.r3d_run_batched_array_image.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
                                                   _dp, _dp, C.POINTER(ArrayImageSpec), C.POINTER(ArrayImageResult)]
+        L.r3d_envelope_shape.restype = C.c_int
+        L.r3d_envelope_shape.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.POINTER(EnvelopeSpec)] + [C.c_void_p] * 9
+        L.r3d_run_batched_envelope_shape.restype = C.c_int
+        L.r3d_run_batched_envelope_shape.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                     C.POINTER(Result), _dp, _dp, C.POINTER(EnvelopeSpec),
+                                                     C.POINTER(EnvelopeResult)]
         L.r3d_run_batched_windows.restype = C.c_int
         L.r3d_run_batched_windows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
                                               _dp, _dp, C.POINTER(WindowSpec), _dp, C.POINTER(C.c_uint64), _dp, _dp]

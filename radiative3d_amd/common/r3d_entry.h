@@ -2,8 +2,8 @@
 // error text, the caller's device kept across the call, device scratch that frees itself, the refusals the calls on
 // the event grid share, and those of the batched runs with the way they learn their engine's device, the format of
 // the block their results come down in (ResultBlock) and the way a run is brought to the host (BatchedRun).  Host code
-// only, all inline.  An add-on (stats/, views/, maps/, arrays/, precision/) includes this and include/r3d.h and nothing from csrc/;
-// csrc/r3d_volume.hip, whose entry points are of the same kind, uses it too.
+// only, all inline.  An add-on (stats/, views/, maps/, arrays/, precision/, shapes/) includes this and include/r3d.h and
+// nothing from csrc/; csrc/r3d_volume.hip, whose entry points are of the same kind, uses it too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -76,7 +76,7 @@ inline const char* bad_frame_range(const r3d_volume_desc* v, uint32_t frame_begi
   return nullptr;
 }
 
-// ---- what the batched runs share (stats/ r3d_run_batched and its kin, arrays/ r3d_run_batched_array_image) ----
+// ---- what the batched runs share (stats/ r3d_run_batched and its kin, arrays/ r3d_run_batched_array_image, shapes/) ----
 constexpr uint32_t kMaxBatches = 64;   // launches of one engine in flight (include/r3d.h r3d_run_device)
 
 // The device a pointer of the caller's lives on (-1: not device memory).

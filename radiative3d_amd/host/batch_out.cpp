@@ -62,6 +62,28 @@ void run_image(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint
   for (int k = 0; k < 2; k++) p.fit[k] = res.fit[k], p.fit_se[k] = res.fit_se[k];
 }
 
+// --envelope-shape: the batched run with its batch blocks kept on the device and the shape of every array receiver's
+// smoothed envelope, with its jackknife, made there (include/r3d.h r3d_run_batched_envelope_shape).
+void run_shape(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total,
+               BatchProducts& p) {
+  const r3dh_envshape_opts& rq = job.env;
+  const size_t A = (size_t)rq.last - rq.first + 1, px = A * d.params.n_bins;
+  r3d_envelope_spec spec{};
+  spec.size = sizeof spec, spec.n_seismometers = (uint32_t)d.n_seismometers, spec.n_bins = d.params.n_bins;
+  spec.first = rq.first, spec.last = rq.last, spec.smooth = rq.smooth;
+  spec.d_bins = job.env_bins.data();   // (for this call: on the host)
+  for (int k = 0; k < 3; k++) spec.weight[k] = rq.axes[k];
+  p.shape.assign(A * R3D_ENVELOPE_N_SHAPE, 0.0), p.shape_se.assign(A * R3D_ENVELOPE_N_SHAPE, 0.0);
+  p.envelope.assign(px, 0.0), p.envelope_se.assign(px, 0.0);
+  p.env_peak_bin.assign(A, 0), p.env_half_bin.assign(A, 0), p.env_lit.assign(A, 0);
+  r3d_envelope_result res{};
+  res.size = sizeof res, res.shape = p.shape.data(), res.shape_se = p.shape_se.data();
+  res.envelope = p.envelope.data(), res.envelope_se = p.envelope_se.data();
+  res.peak_bin = p.env_peak_bin.data(), res.half_bin = p.env_half_bin.data(), res.lit = p.env_lit.data();
+  if (r3d_run_batched_envelope_shape(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data(), &spec, &res))
+    throw Runtime(r3d_last_error());
+}
+
 // --target-error: --num-phonons is the cap, run in rounds of the job's batches each and judged on the device after
 // every round (include/r3d.h r3d_run_to_precision); one line per round, and one that says whether the target was met.
 void run_precision(const BatchJob& job, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total, BatchProducts& p) {
@@ -89,7 +111,7 @@ BatchJob make_batch_job(const MissionParams& mission, const Model& model) {
   if (!mission.bRunSim || !(mission.ErrorBatches || mission.JobErrorBatches)) return job;
   job.dir = mission.OutputDir, job.batches = mission.ErrorBatches ? mission.ErrorBatches : mission.JobErrorBatches;
   job.kind = !mission.ErrorBatches ? BatchJob::JOB_ERRORS : mission.bLapse ? BatchJob::LAPSE : mission.bTTImage ? BatchJob::IMAGE
-             : mission.bTarget ? BatchJob::PRECISION : BatchJob::ERRORS;
+             : mission.bTarget ? BatchJob::PRECISION : mission.bEnvShape ? BatchJob::SHAPE : BatchJob::ERRORS;
   if (job.kind == BatchJob::PRECISION) {
     PrecisionRequest(model, mission, &job.precision);
     job.rounds = mission.TargetRounds;
@@ -103,6 +125,11 @@ BatchJob make_batch_job(const MissionParams& mission, const Model& model) {
     const size_t A = (size_t)job.tt.last - job.tt.first + 1;
     job.tt_distances.assign(A, 0.0), job.tt_azimuths.assign(A, 0.0);
     TTImagePlan(model, job.tt, job.tt_distances.data(), job.tt_azimuths.data());
+  } else if (job.kind == BatchJob::SHAPE) {
+    EnvShapeRequest(model, mission, &job.env);
+    const size_t A = (size_t)job.env.last - job.env.first + 1;
+    job.env_distances.assign(A, 0.0), job.env_bins.assign(2 * A, 0), job.env_clipped.assign(A, 0);
+    EnvShapePlan(model, job.env, job.env_distances.data(), job.env_bins.data(), job.env_clipped.data());
   }
   return job;
 }
@@ -130,6 +157,7 @@ BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& d, r3d_no
   if (job.kind == BatchJob::LAPSE) run_lapse(job, d, e, n, seed, total, p);
   else if (job.kind == BatchJob::IMAGE) run_image(job, d, e, n, seed, total, p);
   else if (job.kind == BatchJob::PRECISION) run_precision(job, e, n, seed, total, p);
+  else if (job.kind == BatchJob::SHAPE) run_shape(job, d, e, n, seed, total, p);
   else if (shards ? r3d_node_run_batched(node, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data())
                   : r3d_run_batched(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data()))
     throw Runtime(r3d_last_error());
@@ -153,10 +181,20 @@ void write_batch_outputs(const BatchJob& job, const Model& model, const BatchPro
     return;
   }
   OutputSeismometerErrors(model, p.energy_se.data(), p.counts_se.data(), job.batches, job.dir);
-  if (job.kind != BatchJob::LAPSE && job.kind != BatchJob::IMAGE) return;
-  const std::string fn = output_path(job.dir, job.kind == BatchJob::LAPSE ? "lapse.octv" : "ttimage.octv");
+  if (job.kind != BatchJob::LAPSE && job.kind != BatchJob::IMAGE && job.kind != BatchJob::SHAPE) return;
+  const std::string fn = output_path(job.dir, job.kind == BatchJob::LAPSE   ? "lapse.octv"
+                                              : job.kind == BatchJob::IMAGE ? "ttimage.octv"
+                                                                            : "envshape.octv");
   std::ofstream f(fn.c_str());
-  if (job.kind == BatchJob::LAPSE) {
+  if (job.kind == BatchJob::SHAPE) {
+    r3dh_envshape_result res{};
+    res.size = sizeof res, res.n_batches = job.batches;
+    res.distances = job.env_distances.data(), res.bins = job.env_bins.data(), res.clipped = job.env_clipped.data();
+    res.shape = p.shape.data(), res.shape_se = p.shape_se.data(), res.envelope = p.envelope.data();
+    res.envelope_se = p.envelope_se.data(), res.peak_bin = p.env_peak_bin.data(), res.half_bin = p.env_half_bin.data();
+    res.lit = p.env_lit.data();
+    OutputEnvShape(model, job.env, res, f);
+  } else if (job.kind == BatchJob::LAPSE) {
     r3dh_lapse_result res{};
     res.size = sizeof res, res.n_batches = job.batches;
     res.distances = job.lapse_distances.data(), res.bins = job.lapse_bins.data(), res.clipped = job.lapse_clipped.data();

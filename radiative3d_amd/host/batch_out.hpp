@@ -1,6 +1,6 @@
-// batch_out.hpp -- the batched-run stage of ./main: what --error-batches, --job-error-batches, --lapse-windows, --ttimage
-// and --target-error run in place of the plain run, and what they write after it (seis_NNN_err.octv, lapse.octv,
-// ttimage.octv, precision.octv).
+// batch_out.hpp -- the batched-run stage of ./main: what --error-batches, --job-error-batches, --lapse-windows, --ttimage,
+// --target-error and --envelope-shape run in place of the plain run, and what they write after it (seis_NNN_err.octv,
+// lapse.octv, ttimage.octv, precision.octv, envshape.octv).
 // Compiled into ./main beside main.cpp (it calls r3d_run_batched* and r3d_node_run_batched of the engine's library, so
 // it is no part of libr3d_host.so); its row arithmetic is batch_plan.hpp.
 #ifndef R3DH_BATCH_OUT_HPP_
@@ -17,11 +17,11 @@
 // A file of the run: `name` under --output-dir ("" = the current directory).
 inline std::string output_path(const std::string& dir, const std::string& name) { return dir.empty() ? name : dir + "/" + name; }
 
-// What the four options ask for, and where it goes.
+// What the options ask for, and where it goes.
 struct BatchJob {
-  // ERRORS: --error-batches alone; LAPSE, IMAGE, PRECISION: with --lapse-windows, --ttimage, --target-error;
-  // JOB_ERRORS: --job-error-batches
-  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION } kind = NONE;
+  // ERRORS: --error-batches alone; LAPSE, IMAGE, PRECISION, SHAPE: with --lapse-windows, --ttimage, --target-error,
+  // --envelope-shape; JOB_ERRORS: --job-error-batches
+  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION, SHAPE } kind = NONE;
   unsigned batches = 0;   // (PRECISION: of a round)
   std::string dir;   // --output-dir
   // LAPSE: the request and the array's plan, [S] receivers (include/r3d_host.h r3dh_lapse_plan)
@@ -35,10 +35,15 @@ struct BatchJob {
   // PRECISION: the criterion and the rounds allowed (include/r3d.h r3d_run_to_precision)
   r3d_precision_spec precision{};
   unsigned rounds = 0;
+  // SHAPE: the request and the array's plan, [A] receivers (include/r3d_host.h r3dh_envshape_plan)
+  r3dh_envshape_opts env{};
+  std::vector<double> env_distances;
+  std::vector<uint32_t> env_bins;
+  std::vector<int32_t> env_clipped;
 };
 
 // What a batched run hands back beside its totals: every bin's standard error, then the kind's own arrays (the shapes
-// are those of include/r3d_host.h r3dh_lapse_result, r3dh_ttimage_result).  Vectors and values only.
+// are those of include/r3d_host.h r3dh_lapse_result, r3dh_ttimage_result, r3dh_envshape_result).  Vectors and values only.
 struct BatchProducts {
   std::vector<double> energy_se, counts_se;
   // LAPSE
@@ -54,10 +59,13 @@ struct BatchProducts {
   r3d_precision_report report{};
   std::vector<uint64_t> receiver_rows;
   std::vector<double> receiver_worst;
+  // SHAPE
+  std::vector<double> shape, shape_se, envelope, envelope_se;
+  std::vector<uint32_t> env_peak_bin, env_half_bin, env_lit;
 };
 
 // The job of a simulation run (`kind` stays NONE without one of the options).  The model is needed for the arrays:
-// throws what LapseRequest / LapsePlan / TTImageRequest / TTImagePlan (dataout.hpp) throw.
+// throws what LapseRequest / LapsePlan / TTImageRequest / TTImagePlan / EnvShapeRequest / EnvShapePlan (dataout.hpp) throw.
 BatchJob make_batch_job(const MissionParams& mission, const Model& model);
 
 // What --error-batches cannot be combined with, told BEFORE the node is built.  Throws Runtime.
@@ -69,7 +77,8 @@ void check_batch_job(const BatchJob& job, size_t n_shards, uint32_t report_mask)
 BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& model, r3d_node* node, uint64_t n, uint64_t seed,
                             r3d_result& total);
 
-// seis_NNN_err.octv, then lapse.octv, ttimage.octv or precision.octv, under the job's directory.  Throws Runtime.
+// seis_NNN_err.octv, then lapse.octv, ttimage.octv, precision.octv or envshape.octv, under the job's directory.  Throws
+// Runtime.
 void write_batch_outputs(const BatchJob& job, const Model& model, const BatchProducts& products);
 
 #endif

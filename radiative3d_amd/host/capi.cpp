@@ -238,6 +238,46 @@ int r3dh_write_ttimage(const r3dh_model* m, const r3dh_ttimage_opts* rq, const r
   return 1;
 }
 
+int r3dh_envshape_request(const r3dh_model* m, r3dh_envshape_opts* rq) {
+  if (!m || !m->mission.bEnvShape) return 0;
+  if (!rq) return 1;
+  try {
+    EnvShapeRequest(*m->model, m->mission, rq);
+    return 1;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return -1;
+}
+
+int r3dh_envshape_plan(const r3dh_model* m, const r3dh_envshape_opts* rq, double* distances, uint32_t* bins, int32_t* clipped) {
+  if (!m || !rq || !distances || !bins || !clipped) return g_error = "r3dh_envshape_plan: null argument", 1;
+  try {
+    // (through the global coordinate system, as r3dh_lapse_plan)
+    EnvShapePlan(*m->model, *rq, distances, bins, clipped);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
+int r3dh_write_envshape(const r3dh_model* m, const r3dh_envshape_opts* rq, const r3dh_envshape_result* res, const char* path) {
+  if (!m || !rq || !res || !path) return g_error = "r3dh_write_envshape: null argument", 1;
+  if (!res->distances || !res->bins || !res->clipped || !res->shape || !res->shape_se || !res->envelope || !res->envelope_se ||
+      !res->peak_bin || !res->half_bin || !res->lit)
+    return g_error = "r3dh_write_envshape: null array in the result", 1;
+  try {
+    std::ofstream f(path);
+    OutputEnvShape(*m->model, *rq, *res, f);
+    if (!f) throw Runtime(std::string("cannot write ") + path);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
 int r3dh_precision_request(const r3dh_model* m, r3d_precision_spec* spec, uint32_t* max_rounds) {
   if (!m || !m->mission.bTarget) return 0;
   try {

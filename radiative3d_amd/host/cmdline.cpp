@@ -22,7 +22,8 @@ enum OptID {
   OPTX_SCATVIEWS, OPTX_SCATVIEW_AZI, OPTX_NO_SCATGRID_FILE, OPTX_SCATMAPS, OPTX_JOBERRBATCHES,
   OPTX_LAPSE, OPTX_LAPSE_AXES, OPTX_LAPSE_GEOSPREAD, OPTX_LAPSE_RANGES, OPTX_LAPSE_ARRAY,
   OPTX_TTIMAGE, OPTX_TTIMAGE_ARRAY, OPTX_TTIMAGE_AXES, OPTX_TTIMAGE_FIT, OPTX_TTIMAGE_NORMCURVE,
-  OPTX_TARGET, OPTX_TARGET_ARRAY, OPTX_TARGET_COMPONENTS
+  OPTX_TARGET, OPTX_TARGET_ARRAY, OPTX_TARGET_COMPONENTS,
+  OPTX_ENVSHAPE, OPTX_ENVSHAPE_ARRAY, OPTX_ENVSHAPE_AXES
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -61,7 +62,8 @@ const std::map<std::string, OptID>& option_table() {
       {"--lapse-ranges", OPTX_LAPSE_RANGES}, {"--lapse-array", OPTX_LAPSE_ARRAY},
       {"--ttimage", OPTX_TTIMAGE}, {"--ttimage-array", OPTX_TTIMAGE_ARRAY}, {"--ttimage-axes", OPTX_TTIMAGE_AXES},
       {"--ttimage-fit", OPTX_TTIMAGE_FIT}, {"--ttimage-normcurve", OPTX_TTIMAGE_NORMCURVE},
-      {"--target-error", OPTX_TARGET}, {"--target-array", OPTX_TARGET_ARRAY}, {"--target-components", OPTX_TARGET_COMPONENTS}};
+      {"--target-error", OPTX_TARGET}, {"--target-array", OPTX_TARGET_ARRAY}, {"--target-components", OPTX_TARGET_COMPONENTS},
+      {"--envelope-shape", OPTX_ENVSHAPE}, {"--envelope-array", OPTX_ENVSHAPE_ARRAY}, {"--envelope-axes", OPTX_ENVSHAPE_AXES}};
   return t;
 }
 
@@ -451,6 +453,39 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
         mission.TargetCompanion = "--target-components";
         break;
       }
+      case OPTX_ENVSHAPE: {
+        long smooth = (long)mission.EnvSmooth;
+        if (o.has()) {
+          for (int k = 0; k < 2; k++) mission.EnvEdge[k] = o.real();
+          for (int k = 0; k < 2; k++) mission.EnvWindow[k] = o.real();
+          if (o.has()) smooth = o.integer();
+        }
+        const double* w = mission.EnvWindow;
+        if (!(mission.EnvEdge[0] > 0) || !std::isfinite(mission.EnvEdge[0]) || !std::isfinite(mission.EnvEdge[1]) ||
+            !std::isfinite(w[0]) || (!std::isnan(w[1]) && (!std::isfinite(w[1]) || !(w[1] >= w[0]))))
+          throw Runtime("--envelope-shape[=V,T0,O,E[,SMOOTH]]: the phase velocity V must be positive, the window's end E not "
+                        "before its start O, and every number finite.");
+        if (smooth < 0 || smooth > 64)
+          throw Runtime("--envelope-shape[=V,T0,O,E[,SMOOTH]]: SMOOTH, the three-point smoothing passes, must be 0 .. 64 (got " +
+                        std::to_string(smooth) + ").");
+        mission.EnvSmooth = (unsigned)smooth;
+        mission.bEnvShape = true;
+        break;
+      }
+      case OPTX_ENVSHAPE_ARRAY:
+        mission.EnvArray[0] = o.integer();
+        mission.EnvArray[1] = o.integer();
+        if (mission.EnvArray[0] < 0 || mission.EnvArray[1] < mission.EnvArray[0])
+          throw Runtime("--envelope-array=FIRST,LAST: seismometer indices with 0 <= FIRST <= LAST.");
+        mission.EnvCompanion = "--envelope-array";
+        break;
+      case OPTX_ENVSHAPE_AXES:
+        for (int k = 0; k < 3; k++) mission.EnvAxes[k] = o.real();
+        for (int k = 0; k < 3; k++)
+          if (!std::isfinite(mission.EnvAxes[k]) || mission.EnvAxes[k] < 0)
+            throw Runtime("--envelope-axes=X,Y,Z: the weights must be finite and not negative (the envelope's energies must not be).");
+        mission.EnvCompanion = "--envelope-axes";
+        break;
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }
@@ -522,6 +557,26 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
     if (n / R < (long)mission.ErrorBatches)
       throw Runtime("--target-error: a round of --num-phonons / ROUNDS = " + std::to_string(n / R) + " histories is fewer than the " +
                     std::to_string(mission.ErrorBatches) + " batches of --error-batches.");
+  }
+  // the envelope shape's errors come from one device's batches, and it keeps the run's batch blocks for itself
+  if (mission.EnvCompanion && !mission.bEnvShape)
+    throw Runtime(std::string(mission.EnvCompanion) + " needs --envelope-shape: it only says how that shape is made.");
+  if (mission.bEnvShape) {
+    if (mission.JobErrorBatches)
+      throw Runtime("--envelope-shape cannot be combined with --job-error-batches: the shape is made where ONE device's batch "
+                    "blocks lie (r3d_run_batched_envelope_shape); a job sharded over devices has no shape call.  Use "
+                    "--error-batches=B.");
+    if (!mission.ErrorBatches)
+      throw Runtime("--envelope-shape needs --error-batches=B: the standard errors of the shape's numbers are jackknives over "
+                    "the B batches.");
+    if (mission.bLapse || mission.bTTImage)
+      throw Runtime(std::string("--envelope-shape cannot be combined with ") + (mission.bLapse ? "--lapse-windows" : "--ttimage") +
+                    " in one run (each keeps the run's batch blocks for itself): out of scope.");
+    if (mission.bTarget)
+      throw Runtime("--envelope-shape cannot be combined with --target-error (the shape needs one run's batch blocks, the "
+                    "rounds keep only their moments): out of scope.");
+    if (ReportMaskFromKeywords(mission.Reports))
+      throw Runtime("--envelope-shape cannot be combined with --reports (the event log's launches run one at a time).");
   }
   // the views and the maps are made from the grid: none of their options means anything without it
   if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile || mission.bScatterMaps))

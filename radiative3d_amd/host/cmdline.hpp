@@ -8,10 +8,12 @@
 // --scatter-grid / --scatter-grid-file (the scatter-event histogram of a video run, written as a file),
 // --error-batches / --job-error-batches (per-bin standard errors), --lapse-windows and its four companions (lapse-window
 // energies and coda ratios with batch errors), --ttimage and its four (the array's travel-time image with jackknife errors),
-// --target-error and its two (a run to a target standard error, in rounds judged on the GPU).
+// --target-error and its two (a run to a target standard error, in rounds judged on the GPU), --envelope-shape and its two
+// (peak delay, decay, centroid and width of every array receiver's envelope with jackknife errors).
 #ifndef R3DH_CMDLINE_HPP_
 #define R3DH_CMDLINE_HPP_
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -87,6 +89,17 @@ struct MissionParams {
   unsigned long TargetMinCount = 16;
   unsigned TargetRounds = 16, TargetMask = 0x18;   // P | S
   long TargetArray[2] = {0, -1};          // LAST < 0: through the last receiver
+  // --envelope-shape[=V,T0,O,E[,SMOOTH]]: per receiver of an array the shape of its smoothed envelope in the window from O to
+  // E seconds behind the phase edge (V km/s, T0 s) -- energy, peak, peak time, time of the fall to half the peak, centroid
+  // and width -- with jackknife errors from the batches of --error-batches (include/r3d.h r3d_run_batched_envelope_shape), as
+  // envshape.octv; SMOOTH passes of vis/seisplot/envcompare.m's three-point rule (its default 8).  Defaults: the lapse
+  // option's phase edge, and the window from the edge to the end of the trace (E = NaN says that).
+  // --envelope-array=FIRST,LAST the receivers (default all), --envelope-axes=X,Y,Z the weights of the three trace axes.
+  bool bEnvShape = false;
+  const char* EnvCompanion = nullptr;     // one of the two that was given (they are refused without --envelope-shape)
+  double EnvEdge[2] = {3.6, 0.0}, EnvWindow[2] = {0.0, std::nan("")}, EnvAxes[3] = {1.0, 1.0, 1.0};
+  unsigned EnvSmooth = 8;
+  long EnvArray[2] = {0, -1};             // LAST < 0: through the last receiver
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

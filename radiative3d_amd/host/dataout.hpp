@@ -58,6 +58,13 @@ void TTImageRequest(const Model& model, const MissionParams& mission, r3dh_ttima
 void TTImagePlan(const Model& model, const r3dh_ttimage_opts& rq, double* distances, double* azimuths);
 void OutputTTImage(const Model& model, const r3dh_ttimage_opts& rq, const r3dh_ttimage_result& res, std::ostream& out);
 
+// The envelope shape of --envelope-shape (include/r3d_host.h has the request, the plan, the file's items): EnvShapeRequest
+// fills *rq from the mission (throws if --envelope-array names a receiver the model does not have), EnvShapePlan the array's
+// distances, windows and clipped flags, OutputEnvShape writes the file's text.
+void EnvShapeRequest(const Model& model, const MissionParams& mission, r3dh_envshape_opts* rq);
+void EnvShapePlan(const Model& model, const r3dh_envshape_opts& rq, double* distances, uint32_t* bins, int32_t* clipped);
+void OutputEnvShape(const Model& model, const r3dh_envshape_opts& rq, const r3dh_envshape_result& res, std::ostream& out);
+
 // precision.octv of --target-error (include/r3d_host.h r3dh_write_precision has the file's items): the target, the
 // selection, what was run and the judge's tables (their rows are batch_plan.hpp's).  Needs no model.  PrecisionRequest
 // fills *spec from the mission (throws if --target-array names a receiver the model does not have).

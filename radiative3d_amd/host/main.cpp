@@ -4,14 +4,15 @@
 // ("@@ __PHASE__", "#  R3D_GRID:", "#  BEGIN SCATTERER DUMP:"), same output
 // files.  The N-phonon loop itself (Model::RunSimulation, model.cpp:602-633)
 // is one call into the engine's C-ABI.  What a run with --scatter-grid writes afterwards (the grid, its views, its maps)
-// is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches, --lapse-windows, --ttimage and
-// --target-error run and write (the batched runs, seis_NNN_err.octv, lapse.octv, ttimage.octv, precision.octv) is the
-// stage of batch_out.cpp.  This file
+// is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches, --lapse-windows, --ttimage,
+// --target-error and --envelope-shape run and write (the batched runs, seis_NNN_err.octv, lapse.octv, ttimage.octv,
+// precision.octv, envshape.octv) is the stage of batch_out.cpp.  This file
 // makes both jobs, has them checked before the node is built, and calls each once to run and once to write.
 //
 // Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B`,
 // `--job-error-batches=N` (error bars of a job on any number of shards), `--lapse-windows` (lapse.octv), `--ttimage`
-// (ttimage.octv) and `--target-error` (a run that stops when its error bars are good enough; precision.octv) are accepted
+// (ttimage.octv), `--target-error` (a run that stops when its error bars are good enough; precision.octv) and
+// `--envelope-shape` (envshape.octv) are accepted
 // (the reference seeds from the clock, is single-process, has no event histogram and no error bars, and takes its phonon
 // count from a hand-tuned table); the `--reports` stream is written
 // after the run, grouped by history, where the reference writes its lines as they happen (the engine appends binary
@@ -253,7 +254,13 @@ int main(int argc, char* argv[]) {
               << "NumPhononsRun -- what a script normalises by, since out_mparams.octv holds the cap.\n"
               << "--target-array=FIRST,LAST (seismometer indices; default all)  --target-components=LETTERS of XYZPS (default PS:\n"
               << "an axis normal to the motion holds rounding noise and would never be met).  Not in one run with --lapse-windows,\n"
-              << "--ttimage, --job-error-batches or --reports\n\n";
+              << "--ttimage, --job-error-batches or --reports\n"
+              << "--envelope-shape[=V,T0,O,E[,SMOOTH]] (with --error-batches; default 3.6,0 and the window from the phase edge to the end\n"
+              << "of the trace, SMOOTH 8): per receiver of an array the shape of its envelope in the window O .. E seconds behind the\n"
+              << "edge, after SMOOTH three-point passes (envcompare.m) -- energy, peak, peak time, the time of the fall to half the\n"
+              << "peak, centroid and width -- made on the GPU with jackknife standard errors, as envshape.octv;\n"
+              << "--envelope-array=FIRST,LAST (default all)  --envelope-axes=X,Y,Z (default 1,1,1).  Not in one run with\n"
+              << "--lapse-windows, --ttimage, --target-error, --job-error-batches or --reports (out of scope)\n\n";
     return 0;
   }
   // A simulation run makes its tables where it uses them (seconds of host work and GBs of upload

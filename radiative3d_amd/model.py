@@ -388,6 +388,63 @@ class Model:
         if self._lib.r3dh_write_ttimage(self._h, C.byref(rq), C.byref(res), str(path).encode()):
             raise RuntimeError("write_ttimage failed: " + self._lib.r3dh_last_error().decode())
 
+    @property
+    def envshape_request(self):
+        """What --envelope-shape[=V,T0,O,E[,SMOOTH]] and its companions (--envelope-array, --envelope-axes) asked for: None,
+        or dict(first, last, smooth, phase_edge, window, axes) -- the array's seismometers first .. last inclusive, window
+        (O, E) in seconds behind the edge with E = NaN for "to the end of the trace" (include/r3d_host.h
+        r3dh_envshape_opts)."""
+        rq = _ffi.EnvShapeOpts()
+        rc = self._lib.r3dh_envshape_request(self._h, C.byref(rq))
+        if rc < 0:
+            raise RuntimeError("envshape_request failed: " + self._lib.r3dh_last_error().decode())
+        if rc == 0:
+            return None
+        return dict(first=int(rq.first), last=int(rq.last), smooth=int(rq.smooth), phase_edge=tuple(rq.phase_edge),
+                    window=tuple(rq.window), axes=tuple(rq.axes))
+
+    @staticmethod
+    def _envshape_opts(request):
+        edge, window = request.get("phase_edge", (3.6, 0.0)), request.get("window", (0.0, math.nan))
+        return _ffi.EnvShapeOpts(size=C.sizeof(_ffi.EnvShapeOpts), first=int(request["first"]), last=int(request["last"]),
+                                 smooth=int(request.get("smooth", 8)), phase_edge=(C.c_double * 2)(*[float(v) for v in edge]),
+                                 window=(C.c_double * 2)(*[float(v) for v in window]),
+                                 axes=(C.c_double * 3)(*[float(v) for v in request.get("axes", (1, 1, 1))]))
+
+    def envshape_plan(self, request=None):
+        """(distances [A], bins [A, 2], clipped [A]) of the envelope array (`request`: a dict as envshape_request gives;
+        None: the model's own): every receiver's epicentral distance as vis/seisplot/range_km.m takes it from
+        seis_NNN.octv, and its window of bins b0, b1 (include/r3d.h r3d_window_bins; to the last bin where the window's E
+        is NaN)."""
+        request = request if request is not None else self.envshape_request
+        if request is None:
+            raise RuntimeError("the model's arguments hold no --envelope-shape")
+        rq = self._envshape_opts(request)
+        A = int(rq.last) - int(rq.first) + 1
+        if A < 1:
+            raise ValueError("envshape request: first > last")
+        dist, bins, clipped = np.zeros(A), np.zeros((A, 2), dtype=np.uint32), np.zeros(A, dtype=np.int32)
+        if self._lib.r3dh_envshape_plan(self._h, C.byref(rq), dist.ctypes.data_as(_ffi._dp),
+                                        bins.ctypes.data_as(C.POINTER(C.c_uint32)), clipped.ctypes.data_as(C.POINTER(C.c_int32))):
+            raise RuntimeError("envshape_plan failed: " + self._lib.r3dh_last_error().decode())
+        return dist, bins, clipped
+
+    def write_envshape(self, path, plan, shape, n_batches, request=None):
+        """Write envshape.octv (include/r3d_host.h r3dh_write_envshape) to `path`: plan = envshape_plan(request), shape the
+        dict Engine.run_batched_envelope_shape returned for the request's array."""
+        request = request if request is not None else self.envshape_request
+        if request is None:
+            raise RuntimeError("the model's arguments hold no --envelope-shape")
+        rq = self._envshape_opts(request)
+        keep = [np.ascontiguousarray(plan[0], dtype=np.float64), np.ascontiguousarray(plan[1], dtype=np.uint32),
+                np.ascontiguousarray(plan[2], dtype=np.int32)]
+        for name, kind in (("shape", np.float64), ("shape_se", np.float64), ("envelope", np.float64), ("envelope_se", np.float64),
+                           ("peak_bin", np.uint32), ("half_bin", np.uint32), ("lit", np.uint32)):
+            keep.append(np.ascontiguousarray(shape[name], dtype=kind))
+        res = _ffi.EnvShapeResult(C.sizeof(_ffi.EnvShapeResult), int(n_batches), *[a.ctypes.data for a in keep])
+        if self._lib.r3dh_write_envshape(self._h, C.byref(rq), C.byref(res), str(path).encode()):
+            raise RuntimeError("write_envshape failed: " + self._lib.r3dh_last_error().decode())
+
     def new_result(self):
         return Result(self.n_seismometers, self.n_bins)
 
@@ -598,6 +655,61 @@ def array_powerlaw(y, r_first, r_last, ibegin, iend):
                                         int(iend), fit, se, total.ctypes.data_as(_ffi._dp)):
         raise RuntimeError("r3d_array_powerlaw_jackknife failed: " + lib.r3d_last_error().decode())
     return fit[0], fit[1], se[0], se[1], total
+
+
+def envelope_spec(n_seismometers, n_bins, first, last, weights, smooth, bins_ptr):
+    """An r3d_envelope_spec (include/r3d.h): bins_ptr the address of the uint32 [A][2] b0, b1 pairs of the array's receivers
+    first .. last -- on the device for envelope_shape, on the host for Engine.run_batched_envelope_shape."""
+    w = [float(v) for v in weights]
+    if len(w) != _ffi.R3D_N_ENERGY:
+        raise ValueError("five component weights (X, Y, Z, P, S) are needed")
+    return _ffi.EnvelopeSpec(size=C.sizeof(_ffi.EnvelopeSpec), n_seismometers=int(n_seismometers), n_bins=int(n_bins),
+                             first=int(first), last=int(last), smooth=int(smooth), d_bins=bins_ptr,
+                             weight=(C.c_double * _ffi.R3D_N_ENERGY)(*w))
+
+
+def envelope_shape(batch_energy, bins, first, last, weights, smooth=8, with_se=None, with_envelope=True, stream=None):
+    """r3d_envelope_shape on torch tensors of one device: batch_energy [B, S, n_bins, 5] float64 are B batch blocks, the array
+    the receivers first .. last (A of them), bins [A, 2] int32 each receiver's window of bins b0, b1, weights the five
+    component weights (>= 0), smooth the three-point passes.  Returns a dict of tensors, all WRITTEN: shape [A, 6] (E, P, peak
+    time, half time, centroid, width; times in bins from the window's first bin), shape_se [A, 6] (with_se; default: B >=
+    2), envelope and envelope_se [A, n_bins] (with_envelope), peak_bin, half_bin and lit [A] (int32; -1: dead / undecayed),
+    bad [1] (int64: the windows that are not b0 <= b1 <= n_bins).  include/r3d.h has the arithmetic.  Asynchronous on
+    `stream` (a raw hipStream_t; None: torch's current one)."""
+    import torch
+    lib = _ffi.hip_lib()
+    if batch_energy.dim() != 4 or batch_energy.shape[3] != _ffi.R3D_N_ENERGY or batch_energy.dtype != torch.float64:
+        raise ValueError("batch_energy must be float64 [B, S, n_bins, 5]")
+    if not batch_energy.is_cuda or not batch_energy.is_contiguous():
+        raise ValueError("the blocks must be a contiguous tensor on a GPU")
+    B, S, n_bins = (int(v) for v in batch_energy.shape[:3])
+    dev = batch_energy.device
+    A = int(last) - int(first) + 1
+    if A < 1 or last >= S:
+        raise ValueError("the array first .. last must lie within the blocks' seismometers")
+    if tuple(bins.shape) != (A, 2) or bins.element_size() != 4 or bins.dtype.is_floating_point or bins.device != dev \
+            or not bins.is_contiguous():
+        raise ValueError("bins must be a contiguous 32-bit integer tensor [A, 2] on the blocks' GPU")
+    with_se = B >= 2 if with_se is None else with_se
+
+    def f64(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=dev)
+
+    def i32():
+        return torch.empty(A, dtype=torch.int32, device=dev)
+    out = dict(shape=f64(A, _ffi.R3D_ENVELOPE_N_SHAPE), shape_se=f64(A, _ffi.R3D_ENVELOPE_N_SHAPE) if with_se else None,
+               envelope=f64(A, n_bins) if with_envelope else None, envelope_se=f64(A, n_bins) if with_envelope and with_se else None,
+               peak_bin=i32(), half_bin=i32(), lit=i32(), bad=torch.zeros(1, dtype=torch.int64, device=dev))
+    spec = envelope_spec(S, n_bins, first, last, weights, smooth, bins.data_ptr())
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    ptr = {k: (v.data_ptr() if v is not None else None) for k, v in out.items()}
+    rc = lib.r3d_envelope_shape(dev.index or 0, B, batch_energy.data_ptr(), C.byref(spec), ptr["shape"], ptr["shape_se"],
+                                ptr["envelope"], ptr["envelope_se"], ptr["peak_bin"], ptr["half_bin"], ptr["lit"], ptr["bad"],
+                                stream)
+    if rc:
+        raise RuntimeError("r3d_envelope_shape failed: " + lib.r3d_last_error().decode())
+    return out
 
 
 def _check_blocks(blocks, lead, what):
@@ -1136,6 +1248,28 @@ class Engine:
         if has_fit:
             img.update(fit=tuple(out.fit), fit_se=tuple(out.fit_se), curve_made=bool(out.curve_made))
         return res, ese, cse, img
+
+    def run_batched_envelope_shape(self, n, n_batches, bins, first, last, weights, smooth=8, first_id=0, seed=0x5EED):
+        """run_batched that also makes the envelope shape of the receivers first .. last where the batch blocks lie
+        (include/r3d.h r3d_run_batched_envelope_shape): bins [A, 2] each receiver's window b0, b1 (host; Model.envshape_plan
+        makes them), weights the five component weights, smooth the three-point passes.  Returns (Result, energy_se,
+        counts_se, shape): a dict of shape, shape_se [A, 6], envelope, envelope_se [A, n_bins], peak_bin, half_bin, lit [A]
+        (uint32; 0xFFFFFFFF: dead / undecayed)."""
+        m = self.model
+        A = int(last) - int(first) + 1
+        if A < 1:
+            raise ValueError("the array needs first <= last")
+        b = np.ascontiguousarray(bins, dtype=np.uint32)
+        if b.shape != (A, 2):
+            raise ValueError("bins must be [A, 2]")
+        spec = envelope_spec(m.n_seismometers, m.n_bins, first, last, weights, smooth, b.ctypes.data)
+        shp = dict(shape=np.zeros((A, _ffi.R3D_ENVELOPE_N_SHAPE)), shape_se=np.zeros((A, _ffi.R3D_ENVELOPE_N_SHAPE)),
+                   envelope=np.zeros((A, m.n_bins)), envelope_se=np.zeros((A, m.n_bins)), peak_bin=np.zeros(A, dtype=np.uint32),
+                   half_bin=np.zeros(A, dtype=np.uint32), lit=np.zeros(A, dtype=np.uint32))
+        out = _ffi.EnvelopeResult(size=C.sizeof(_ffi.EnvelopeResult), **{k: v.ctypes.data for k, v in shp.items()})
+        res, ese, cse = _run_batched_to_host(self._lib, "r3d_run_batched_envelope_shape", self._e, m, n, first_id, seed,
+                                             n_batches, None, C.byref(spec), C.byref(out))
+        return res, ese, cse, shp
 
     def run_device(self, n, first_id, seed, d_energy, d_counts, d_scalars, stream=None, carry=None):
         """Asynchronous, device-resident accumulate (pointers are raw device
