@@ -55,12 +55,16 @@ ENGINE_HDR := $(wildcard $(CSRC)/*.h) include/r3d.h
 #          C-ABI (r3d_batch_precision, r3d_run_to_precision)
 #   shapes the envelope shape per receiver -- peak delay, decay to half, centroid, width -- with jackknife errors
 #          (r3d_envelope_shape, r3d_run_batched_envelope_shape)
-ADDONS := stats views maps arrays precision shapes
+#   fits   the envelope misfit against observed data -- scale, correlation, residual, lag -- with jackknife errors
+#          (r3d_envelope_misfit, r3d_run_batched_envelope_misfit)
+ADDONS := stats views maps arrays precision shapes fits
 addon_src = $(wildcard radiative3d_amd/$(1)/*.hip)
 # (arrays/ takes the bin energy and the strand constants from stats/r3d_window_sums.h; shapes/ those and the scans, the
-# running maximum and the jackknife from arrays/r3d_array_image.h)
+# running maximum and the jackknife from arrays/r3d_array_image.h; fits/ all of that and the smoothing rule from
+# shapes/r3d_envelope_shape.h)
 addon_hdr = $(wildcard radiative3d_amd/$(1)/*.h) $(COMMON)/r3d_entry.h include/r3d.h $(if $(filter arrays,$(1)),radiative3d_amd/stats/r3d_window_sums.h) \
-            $(if $(filter shapes,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h)
+            $(if $(filter shapes,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h) \
+            $(if $(filter fits,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h radiative3d_amd/shapes/r3d_envelope_shape.h)
 OBJDIR   := build/obj
 
 # (the default goal is the first target of the file: it has to come before the generated object rules)

@@ -954,6 +954,77 @@ int r3d_run_batched_envelope_shape(r3d_engine* e, uint64_t n, uint64_t first_id,
                                    r3d_result* out, double* energy_se, double* counts_se, const r3d_envelope_spec* spec,
                                    r3d_envelope_result* res);
 
+/* ---- the envelope misfit against observed data with jackknife errors ---------------------
+ * The step the envelope numbers above are for: given an OBSERVED envelope per array receiver, how far the synthetic one is
+ * from it -- what vis/seisplot/envcompare.m shows by eye (smoothed, peak-normalised, drawn over each other, a hand-picked
+ * rscale), as numbers with error bars a parameter study can minimise.  Products of sums, a quotient and an arg-max over
+ * lags are nonlinear in a whole row: the errors are jackknives over the batch blocks where they lie.
+ * radiative3d_amd/fits/r3d_envelope_misfit.h has the arithmetic:
+ *     ROWS over a receiver's window [b0, b1), n = b1 - b0: the total t and, for B >= 2, the t_(j), as r3d_envelope_shape makes
+ *       them; a = sqrt(row) if `amplitude`, else the row; u = S^smooth_syn(a) by the shape's three-point pass.  The observed
+ *       row o = S^smooth_obs(observed[i][b0 .. b1)), amplitudes ON THE RUN'S BINS (r3dh_observed_to_bins resamples a record),
+ *       made once per receiver and shared by all B + 1 rows.
+ *     SUMS by the window sum's strands and tree: Suu = sum u u, Soo = sum o o, X_L = sum over 0 <= k + L < n of u[k] o[k + L]
+ *       for L = -max_lag .. max_lag, the row sums and first moments of u and o, and the maxima P, Po.
+ *     SIX NUMBERS (R3D_MISFIT_N):  0 s = X_0 / Soo, the least-squares scale of o onto u  1 rho = X_0 / (sqrt(Suu) sqrt(Soo))
+ *       2 chi = sum (u - s o)^2 / Suu, a second pass, never 1 - rho^2  3 dpk = sum (u / P - o / Po)^2 / n, envcompare's
+ *       picture at rscale = 1  4 lag = the first L that holds the maximum of c_L = X_L / (sqrt(Suu) sqrt(Soo)); positive: the
+ *       observed envelope comes later  5 dc = the centroid of u minus the centroid of o, in bins.  The CURVE c_L is written
+ *       too, [2 max_lag + 1] per receiver.
+ *     DEAD (all six and the curve NaN, lit = 0): n == 0, P or Po not > 0, or an observed value inside the window that is
+ *       negative or not finite -- told by its bits and counted per receiver in bad_observed.  A window with b0 > b1 or b1 >
+ *       n_bins is never read through: dead, and counted in bad.
+ *     se, B >= 2: every number and every c_L again from every t_(j) against the same o; NaN as soon as one value is NaN.  The
+ *       se of the lag, an integer that jumps, says whether the batches agree on it, not how exact it is (the header).
+ *     The same bits on every run, machine and launch geometry; the header derives the rounding bounds.
+ *
+ * r3d_envelope_misfit: device level, like r3d_envelope_shape -- B >= 1 batch-major blocks d_batch_energy on `device`, only
+ * read; spec->d_bins [A][2] and spec->d_observed [A][n_bins] on the device.  WRITTEN, every entry by one work-item: d_misfit
+ * [A][6]; d_misfit_se [A][6]; d_xcorr and d_xcorr_se [A][2 max_lag + 1]; d_envelope [A][n_bins] (u of the total row at the
+ * window's bins, +0.0 elsewhere); d_lit [A] (u32); d_bad, d_bad_observed (one uint64 each).  Every output but d_misfit may
+ * be NULL; an se needs B >= 2.  No atomics, fixed order, 64-bit offsets; the rows pass through scratch taken from and
+ * returned to the stream's memory pool, the lag scan reads them from LDS.  Asynchronous on `stream`.  REFUSED (non-zero,
+ * r3d_last_error, nothing enqueued, no buffer touched; all checked before any HIP call): what r3d_envelope_shape refuses
+ * (either smooth count above R3D_ENVELOPE_MAX_SMOOTH), a null d_observed, max_lag > R3D_MISFIT_MAX_LAG, amplitude not 0 or 1.
+ *
+ * r3d_run_batched_envelope_misfit: r3d_run_batched (same arguments, refusals, out / energy_se / counts_se) that keeps its
+ * batch blocks on the device, makes the misfit there and reads back only the small arrays of *res, all WRITTEN.  For THIS
+ * call spec->d_bins and spec->d_observed are HOST arrays, checked here: a pair with b0 > b1 or b1 > n_bins is refused, and so
+ * is an observed value inside a window that is negative or not finite, a spec whose n_seismometers / n_bins are not the
+ * model's, a null res or one of another size, a null misfit or misfit_se.  A refusal touches nothing.  Out of scope: a job
+ * sharded over several devices (r3d_node_run_batched has no misfit call), and combining this call in one run with the
+ * windows, the array image or the envelope shape.                                                                        */
+#define R3D_MISFIT_N 6
+#define R3D_MISFIT_MAX_LAG 64
+typedef struct r3d_misfit_spec {
+  uint32_t size;                    /* sizeof(r3d_misfit_spec): a mismatch is refused          */
+  uint32_t n_seismometers, n_bins;
+  uint32_t first, last;             /* the array: seismometers first .. last                   */
+  uint32_t smooth_syn, smooth_obs;  /* three-point passes, 0 .. R3D_ENVELOPE_MAX_SMOOTH each   */
+  uint32_t max_lag;                 /* bins, 0 .. R3D_MISFIT_MAX_LAG                           */
+  uint32_t amplitude;               /* 1: u from the roots of the energies; 0: from them       */
+  uint32_t pad_;
+  const uint32_t* d_bins;           /* [A][2] b0, b1; device (the run: host)                   */
+  const double*   d_observed;       /* [A][n_bins] amplitudes; device (the run: host)          */
+  double   weight[R3D_N_ENERGY];
+} r3d_misfit_spec;
+typedef struct r3d_misfit_result {
+  uint32_t size;                    /* sizeof(r3d_misfit_result)                               */
+  uint32_t pad_;
+  double*   misfit;                 /* [A][6]                                                  */
+  double*   misfit_se;              /* [A][6]                                                  */
+  double*   xcorr;                  /* [A][2 max_lag + 1]  may be NULL                         */
+  double*   xcorr_se;               /* [A][2 max_lag + 1]  may be NULL                         */
+  double*   envelope;               /* [A][n_bins]         may be NULL                         */
+  uint32_t* lit;                    /* [A]                 may be NULL                         */
+} r3d_misfit_result;
+int r3d_envelope_misfit(int device, uint32_t n_batches, const double* d_batch_energy, const r3d_misfit_spec* spec,
+                        double* d_misfit, double* d_misfit_se, double* d_xcorr, double* d_xcorr_se, double* d_envelope,
+                        uint32_t* d_lit, uint64_t* d_bad, uint64_t* d_bad_observed, void* stream);
+int r3d_run_batched_envelope_misfit(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                                    r3d_result* out, double* energy_se, double* counts_se, const r3d_misfit_spec* spec,
+                                    r3d_misfit_result* res);
+
 /* ---- run to a target standard error: rounds of batches, judged on the device ------------
  * How many histories a run needs is asked before every run; this call answers it by running in rounds and looking at the
  * error bars where they lie.  radiative3d_amd/precision/r3d_precision.h has the criterion's arithmetic, built by the host too.

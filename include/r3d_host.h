@@ -235,6 +235,77 @@ int r3dh_envshape_request(const r3dh_model* m, r3dh_envshape_opts* rq);
 int r3dh_envshape_plan(const r3dh_model* m, const r3dh_envshape_opts* rq, double* distances, uint32_t* bins, int32_t* clipped);
 int r3dh_write_envshape(const r3dh_model* m, const r3dh_envshape_opts* rq, const r3dh_envshape_result* res, const char* path);
 
+/* --envelope-fit=FILE[,V,T0,O,E[,SMOOTH[,OBSSMOOTH[,MAXLAG_SECONDS]]]] [--envelope-fit-array=FIRST,LAST]
+ * [--envelope-fit-axes=X,Y,Z] [--envelope-fit-energy] in the model's arguments (the last three refused without the first; the
+ * first without --error-batches and with --job-error-batches, --lapse-windows, --ttimage, --target-error, --envelope-shape or
+ * --reports): per receiver of an array the misfit of its smoothed amplitude envelope against an observed one, with jackknife
+ * errors from the batches (r3d.h r3d_run_batched_envelope_misfit).  FILE is GNU/Octave text with ObsTimeWindow [1 x 2] (T0,
+ * T1 in seconds of the run's clock) and ObsEnvelope [n_samples x A], one column per array receiver, amplitudes (energies
+ * with --envelope-fit-energy: their roots are taken unless `amplitude` is 0).  Defaults as --envelope-shape's; OBSSMOOTH 0,
+ * MAXLAG_SECONDS 0.
+ * r3dh_observed_to_bins (plain arithmetic, no device, no model): an observed envelope of n_samples values, sample i (at
+ * samples[i * stride]) at the time T0 + i (T1 - T0) / (n_samples - 1), resampled by linear interpolation at the abscissae
+ * vis/seisplot/envcompare.m gives a trace of n_bins values, linspace(t_begin, t_end, n_bins): out[b] at t_begin + b (t_end -
+ * t_begin) / (n_bins - 1) (n_bins == 1: at t_end, as Octave's linspace).  Outside the observed span the value is +0.0;
+ * with n_samples == 1 the value sits at T0 and +0.0 is everywhere else.  Non-zero (nothing written): a null pointer,
+ * n_samples == 0, n_bins == 0, stride == 0, a time that is not finite, T1 < T0 (T1 == T0 only with one sample).
+ * r3dh_read_octave: the minimal GNU/Octave-text READER -- exactly the two forms this library's writer emits, `scalar` and
+ * `matrix` blocks.  Looks up the variable `name` in the file: *rows, *cols its shape (1, 1 for a scalar), and its values,
+ * row-major, in out[0 .. rows * cols) where capacity allows (out may be NULL with capacity 0 to ask for the shape).  Non-zero
+ * with r3dh_last_error naming the variable: a block of any other type anywhere in the file (`string`, ...), a matrix with
+ * fewer rows or values in a row than its header says, a value that is no number, a missing variable, too little capacity.
+ * r3dh_envfit_request: returns 1 and fills *rq when the misfit was asked for (rq->file points into the model), 0 otherwise;
+ * -1 (r3dh_last_error) if --envelope-fit-array's LAST is not a seismometer of the model.
+ * r3dh_envfit_plan: the envelope shape's window rule (r3dh_envshape_plan: distances [A], bins [A][2], clipped [A]) plus the
+ * observed rows: rq->file is read, column i resampled by r3dh_observed_to_bins onto the run's bins with t_begin = 0, t_end =
+ * n_bins dt (TimeWindow of seis_NNN.octv), roots taken where the file holds energies and amplitudes are compared, into
+ * observed [A][n_bins]; *max_lag = round(max_lag_seconds / dt) bins.  Non-zero: what the window rule refuses, a file that
+ * cannot be read or has not A columns, a lag beyond R3D_MISFIT_MAX_LAG bins.
+ * r3dh_write_envfit: envfit.octv-style GNU/Octave text at 17 digits to `path`, rows the array's receivers in order:
+ * FitSeismometers [A], FitBatches, FitDistances [A], FitPhaseEdge [2], FitWindow [2] (O, E; E NaN: to the end of the trace),
+ * FitAxes [3], FitSmooth [2] (synthetic, observed), FitAmplitude, FitEnergyFile, FitMaxLag (bins), FitMaxLagSeconds,
+ * FitNumBins, FitBins [A][2], FitClipped [A], FitLit [A], then the six numbers, each [A] with its _se: FitScale,
+ * FitCorrelation, FitResidual (chi), FitPeakDistance (dpk), FitLag (bins) and FitLagSeconds beside it, FitCentroidShift
+ * (dc times dt: seconds); FitLags [2 max_lag + 1] (seconds), FitXcorr / FitXcorr_se [A][2 max_lag + 1], FitEnvelope
+ * [A][n_bins] (the smoothed synthetic envelope, +0.0 outside the window) and FitObserved [A][n_bins] (the observed rows on the
+ * run's bins, before their smoothing).  Returns 0 ok.                                                                  */
+typedef struct r3dh_envfit_opts {
+  uint32_t size;                 /* sizeof(r3dh_envfit_opts)                                     */
+  uint32_t first, last;          /* the array: seismometers first .. last                        */
+  uint32_t smooth_syn, smooth_obs; /* three-point passes, 0 .. 64 each                           */
+  uint32_t amplitude;            /* 1: amplitudes are compared (the command line's); 0: energies */
+  uint32_t energy_file;          /* 1: the file holds energies                                   */
+  uint32_t pad_;
+  double   phase_edge[2];        /* v, t0                                                         */
+  double   window[2];            /* o, e: seconds behind the edge; e = NaN: to the trace's end   */
+  double   axes[3];              /* weights of the trace's X, Y, Z                               */
+  double   max_lag_seconds;      /* the largest lag tried, >= 0                                  */
+  const char* file;              /* the observed envelopes                                       */
+} r3dh_envfit_opts;
+typedef struct r3dh_envfit_result {
+  uint32_t size;                 /* sizeof(r3dh_envfit_result)                                   */
+  uint32_t n_batches;
+  uint32_t max_lag;              /* bins, r3dh_envfit_plan's                                     */
+  uint32_t pad_;
+  const double*   distances;     /* [A]     r3dh_envfit_plan's                                   */
+  const uint32_t* bins;          /* [A][2]                                                       */
+  const int32_t*  clipped;       /* [A]                                                          */
+  const double*   observed;      /* [A][n_bins]                                                  */
+  const double*   misfit;        /* [A][6]  as r3d_run_batched_envelope_misfit gives it          */
+  const double*   misfit_se;     /* [A][6]                                                       */
+  const double*   xcorr;         /* [A][2 max_lag + 1]                                           */
+  const double*   xcorr_se;      /* [A][2 max_lag + 1]                                           */
+  const double*   envelope;      /* [A][n_bins]                                                  */
+  const uint32_t* lit;           /* [A]                                                          */
+} r3dh_envfit_result;
+int r3dh_observed_to_bins(const double* samples, uint32_t n_samples, uint32_t stride, double t0, double t1, double t_begin,
+                          double t_end, uint32_t n_bins, double* out);
+int r3dh_read_octave(const char* path, const char* name, uint32_t* rows, uint32_t* cols, double* out, size_t capacity);
+int r3dh_envfit_request(const r3dh_model* m, r3dh_envfit_opts* rq);
+int r3dh_envfit_plan(const r3dh_model* m, const r3dh_envfit_opts* rq, double* distances, uint32_t* bins, int32_t* clipped,
+                     double* observed, uint32_t* max_lag);
+int r3dh_write_envfit(const r3dh_model* m, const r3dh_envfit_opts* rq, const r3dh_envfit_result* res, const char* path);
+
 /* --target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]] [--target-array=FIRST,LAST] [--target-components=LETTERS] in the
  * model's arguments (the last two refused without the first; the first without --error-batches, with --job-error-batches,
  * --lapse-windows, --ttimage or --reports, on more than one shard, and with a --num-phonons that is no multiple of ROUNDS

@@ -152,6 +152,23 @@ class EnvelopeResult(C.Structure):
                 ("lit", C.c_void_p)]
 
 
+R3D_MISFIT_N, R3D_MISFIT_MAX_LAG = 6, 64
+
+
+class MisfitSpec(C.Structure):
+    """include/r3d.h r3d_misfit_spec"""
+    _fields_ = [("size", C.c_uint32), ("n_seismometers", C.c_uint32), ("n_bins", C.c_uint32), ("first", C.c_uint32),
+                ("last", C.c_uint32), ("smooth_syn", C.c_uint32), ("smooth_obs", C.c_uint32), ("max_lag", C.c_uint32),
+                ("amplitude", C.c_uint32), ("pad_", C.c_uint32), ("d_bins", C.c_void_p), ("d_observed", C.c_void_p),
+                ("weight", C.c_double * R3D_N_ENERGY)]
+
+
+class MisfitResult(C.Structure):
+    """include/r3d.h r3d_misfit_result"""
+    _fields_ = [("size", C.c_uint32), ("pad_", C.c_uint32), ("misfit", C.c_void_p), ("misfit_se", C.c_void_p),
+                ("xcorr", C.c_void_p), ("xcorr_se", C.c_void_p), ("envelope", C.c_void_p), ("lit", C.c_void_p)]
+
+
 R3D_PRECISION_MAX_ROUNDS = 64
 R3D_PRECISION_DEFAULT_MASK = 0x18   # P | S: an axis normal to the motion holds rounding noise and would never be met
 
@@ -213,6 +230,22 @@ class EnvShapeResult(C.Structure):
     _fields_ = [("size", C.c_uint32), ("n_batches", C.c_uint32), ("distances", C.c_void_p), ("bins", C.c_void_p),
                 ("clipped", C.c_void_p), ("shape", C.c_void_p), ("shape_se", C.c_void_p), ("envelope", C.c_void_p),
                 ("envelope_se", C.c_void_p), ("peak_bin", C.c_void_p), ("half_bin", C.c_void_p), ("lit", C.c_void_p)]
+
+
+class EnvFitOpts(C.Structure):
+    """include/r3d_host.h r3dh_envfit_opts"""
+    _fields_ = [("size", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("smooth_syn", C.c_uint32),
+                ("smooth_obs", C.c_uint32), ("amplitude", C.c_uint32), ("energy_file", C.c_uint32), ("pad_", C.c_uint32),
+                ("phase_edge", C.c_double * 2), ("window", C.c_double * 2), ("axes", C.c_double * 3),
+                ("max_lag_seconds", C.c_double), ("file", C.c_char_p)]
+
+
+class EnvFitResult(C.Structure):
+    """include/r3d_host.h r3dh_envfit_result"""
+    _fields_ = [("size", C.c_uint32), ("n_batches", C.c_uint32), ("max_lag", C.c_uint32), ("pad_", C.c_uint32),
+                ("distances", C.c_void_p), ("bins", C.c_void_p), ("clipped", C.c_void_p), ("observed", C.c_void_p),
+                ("misfit", C.c_void_p), ("misfit_se", C.c_void_p), ("xcorr", C.c_void_p), ("xcorr_se", C.c_void_p),
+                ("envelope", C.c_void_p), ("lit", C.c_void_p)]
 
 
 class MapsHeader(C.Structure):
@@ -337,6 +370,17 @@ def host_lib():
         L.r3dh_envshape_plan.argtypes = [C.c_void_p, C.POINTER(EnvShapeOpts), _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
         L.r3dh_write_envshape.restype = C.c_int
         L.r3dh_write_envshape.argtypes = [C.c_void_p, C.POINTER(EnvShapeOpts), C.POINTER(EnvShapeResult), C.c_char_p]
+        L.r3dh_observed_to_bins.restype = C.c_int
+        L.r3dh_observed_to_bins.argtypes = [_dp, C.c_uint32, C.c_uint32] + [C.c_double] * 4 + [C.c_uint32, _dp]
+        L.r3dh_read_octave.restype = C.c_int
+        L.r3dh_read_octave.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _dp, C.c_size_t]
+        L.r3dh_envfit_request.restype = C.c_int
+        L.r3dh_envfit_request.argtypes = [C.c_void_p, C.POINTER(EnvFitOpts)]
+        L.r3dh_envfit_plan.restype = C.c_int
+        L.r3dh_envfit_plan.argtypes = [C.c_void_p, C.POINTER(EnvFitOpts), _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), _dp,
+                                       C.POINTER(C.c_uint32)]
+        L.r3dh_write_envfit.restype = C.c_int
+        L.r3dh_write_envfit.argtypes = [C.c_void_p, C.POINTER(EnvFitOpts), C.POINTER(EnvFitResult), C.c_char_p]
         L.r3dh_precision_request.restype = C.c_int
         L.r3dh_precision_request.argtypes = [C.c_void_p, C.POINTER(PrecisionSpec), C.POINTER(C.c_uint32)]
         L.r3dh_write_precision.restype = C.c_int
@@ -540,6 +584,12 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_run_batched_envelope_shape.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                                      C.POINTER(Result), _dp, _dp, C.POINTER(EnvelopeSpec),
                                                      C.POINTER(EnvelopeResult)]
+        L.r3d_envelope_misfit.restype = C.c_int
+        L.r3d_envelope_misfit.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.POINTER(MisfitSpec)] + [C.c_void_p] * 9
+        L.r3d_run_batched_envelope_misfit.restype = C.c_int
+        L.r3d_run_batched_envelope_misfit.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                      C.POINTER(Result), _dp, _dp, C.POINTER(MisfitSpec),
+                                                      C.POINTER(MisfitResult)]
         L.r3d_run_batched_windows.restype = C.c_int
         L.r3d_run_batched_windows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
                                               _dp, _dp, C.POINTER(WindowSpec), _dp, C.POINTER(C.c_uint64), _dp, _dp]

@@ -2,7 +2,7 @@
 // error text, the caller's device kept across the call, device scratch that frees itself, the refusals the calls on
 // the event grid share, and those of the batched runs with the way they learn their engine's device, the format of
 // the block their results come down in (ResultBlock) and the way a run is brought to the host (BatchedRun).  Host code
-// only, all inline.  An add-on (stats/, views/, maps/, arrays/, precision/, shapes/) includes this and include/r3d.h and
+// only, all inline.  An add-on (stats/, views/, maps/, arrays/, precision/, shapes/, fits/) includes this and include/r3d.h and
 // nothing from csrc/; csrc/r3d_volume.hip, whose entry points are of the same kind, uses it too.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -84,6 +84,27 @@ void run_shape(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint
     throw Runtime(r3d_last_error());
 }
 
+// --envelope-fit: the batched run with its batch blocks kept on the device and the misfit of every array receiver's smoothed
+// envelope against the observed one, with its jackknife, made there (include/r3d.h r3d_run_batched_envelope_misfit).
+void run_fit(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total,
+             BatchProducts& p) {
+  const r3dh_envfit_opts& rq = job.fit;
+  const size_t A = (size_t)rq.last - rq.first + 1, px = A * d.params.n_bins, nx = A * (2 * (size_t)job.fit_max_lag + 1);
+  r3d_misfit_spec spec{};
+  spec.size = sizeof spec, spec.n_seismometers = (uint32_t)d.n_seismometers, spec.n_bins = d.params.n_bins;
+  spec.first = rq.first, spec.last = rq.last, spec.smooth_syn = rq.smooth_syn, spec.smooth_obs = rq.smooth_obs;
+  spec.max_lag = job.fit_max_lag, spec.amplitude = rq.amplitude;
+  spec.d_bins = job.env_bins.data(), spec.d_observed = job.fit_observed.data();   // (for this call: on the host)
+  for (int k = 0; k < 3; k++) spec.weight[k] = rq.axes[k];
+  p.misfit.assign(A * R3D_MISFIT_N, 0.0), p.misfit_se.assign(A * R3D_MISFIT_N, 0.0), p.xcorr.assign(nx, 0.0), p.xcorr_se.assign(nx, 0.0);
+  p.envelope.assign(px, 0.0), p.env_lit.assign(A, 0);
+  r3d_misfit_result res{};
+  res.size = sizeof res, res.misfit = p.misfit.data(), res.misfit_se = p.misfit_se.data(), res.xcorr = p.xcorr.data();
+  res.xcorr_se = p.xcorr_se.data(), res.envelope = p.envelope.data(), res.lit = p.env_lit.data();
+  if (r3d_run_batched_envelope_misfit(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data(), &spec, &res))
+    throw Runtime(r3d_last_error());
+}
+
 // --target-error: --num-phonons is the cap, run in rounds of the job's batches each and judged on the device after
 // every round (include/r3d.h r3d_run_to_precision); one line per round, and one that says whether the target was met.
 void run_precision(const BatchJob& job, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total, BatchProducts& p) {
@@ -111,7 +132,7 @@ BatchJob make_batch_job(const MissionParams& mission, const Model& model) {
   if (!mission.bRunSim || !(mission.ErrorBatches || mission.JobErrorBatches)) return job;
   job.dir = mission.OutputDir, job.batches = mission.ErrorBatches ? mission.ErrorBatches : mission.JobErrorBatches;
   job.kind = !mission.ErrorBatches ? BatchJob::JOB_ERRORS : mission.bLapse ? BatchJob::LAPSE : mission.bTTImage ? BatchJob::IMAGE
-             : mission.bTarget ? BatchJob::PRECISION : mission.bEnvShape ? BatchJob::SHAPE : BatchJob::ERRORS;
+             : mission.bTarget ? BatchJob::PRECISION : mission.bEnvShape ? BatchJob::SHAPE : mission.bEnvFit ? BatchJob::FIT : BatchJob::ERRORS;
   if (job.kind == BatchJob::PRECISION) {
     PrecisionRequest(model, mission, &job.precision);
     job.rounds = mission.TargetRounds;
@@ -130,6 +151,13 @@ BatchJob make_batch_job(const MissionParams& mission, const Model& model) {
     const size_t A = (size_t)job.env.last - job.env.first + 1;
     job.env_distances.assign(A, 0.0), job.env_bins.assign(2 * A, 0), job.env_clipped.assign(A, 0);
     EnvShapePlan(model, job.env, job.env_distances.data(), job.env_bins.data(), job.env_clipped.data());
+  } else if (job.kind == BatchJob::FIT) {
+    EnvFitRequest(model, mission, &job.fit);
+    const size_t A = (size_t)job.fit.last - job.fit.first + 1;
+    job.env_distances.assign(A, 0.0), job.env_bins.assign(2 * A, 0), job.env_clipped.assign(A, 0);
+    job.fit_observed.assign(A * model.Desc().params.n_bins, 0.0);
+    EnvFitPlan(model, job.fit, job.env_distances.data(), job.env_bins.data(), job.env_clipped.data(), job.fit_observed.data(),
+               &job.fit_max_lag);
   }
   return job;
 }
@@ -158,6 +186,7 @@ BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& d, r3d_no
   else if (job.kind == BatchJob::IMAGE) run_image(job, d, e, n, seed, total, p);
   else if (job.kind == BatchJob::PRECISION) run_precision(job, e, n, seed, total, p);
   else if (job.kind == BatchJob::SHAPE) run_shape(job, d, e, n, seed, total, p);
+  else if (job.kind == BatchJob::FIT) run_fit(job, d, e, n, seed, total, p);
   else if (shards ? r3d_node_run_batched(node, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data())
                   : r3d_run_batched(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data()))
     throw Runtime(r3d_last_error());
@@ -181,12 +210,20 @@ void write_batch_outputs(const BatchJob& job, const Model& model, const BatchPro
     return;
   }
   OutputSeismometerErrors(model, p.energy_se.data(), p.counts_se.data(), job.batches, job.dir);
-  if (job.kind != BatchJob::LAPSE && job.kind != BatchJob::IMAGE && job.kind != BatchJob::SHAPE) return;
+  if (job.kind != BatchJob::LAPSE && job.kind != BatchJob::IMAGE && job.kind != BatchJob::SHAPE && job.kind != BatchJob::FIT) return;
   const std::string fn = output_path(job.dir, job.kind == BatchJob::LAPSE   ? "lapse.octv"
                                               : job.kind == BatchJob::IMAGE ? "ttimage.octv"
-                                                                            : "envshape.octv");
+                                              : job.kind == BatchJob::SHAPE ? "envshape.octv"
+                                                                            : "envfit.octv");
   std::ofstream f(fn.c_str());
-  if (job.kind == BatchJob::SHAPE) {
+  if (job.kind == BatchJob::FIT) {
+    r3dh_envfit_result res{};
+    res.size = sizeof res, res.n_batches = job.batches, res.max_lag = job.fit_max_lag;
+    res.distances = job.env_distances.data(), res.bins = job.env_bins.data(), res.clipped = job.env_clipped.data();
+    res.observed = job.fit_observed.data(), res.misfit = p.misfit.data(), res.misfit_se = p.misfit_se.data();
+    res.xcorr = p.xcorr.data(), res.xcorr_se = p.xcorr_se.data(), res.envelope = p.envelope.data(), res.lit = p.env_lit.data();
+    OutputEnvFit(model, job.fit, res, f);
+  } else if (job.kind == BatchJob::SHAPE) {
     r3dh_envshape_result res{};
     res.size = sizeof res, res.n_batches = job.batches;
     res.distances = job.env_distances.data(), res.bins = job.env_bins.data(), res.clipped = job.env_clipped.data();

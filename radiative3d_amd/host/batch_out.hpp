@@ -1,6 +1,6 @@
 // batch_out.hpp -- the batched-run stage of ./main: what --error-batches, --job-error-batches, --lapse-windows, --ttimage,
-// --target-error and --envelope-shape run in place of the plain run, and what they write after it (seis_NNN_err.octv,
-// lapse.octv, ttimage.octv, precision.octv, envshape.octv).
+// --target-error, --envelope-shape and --envelope-fit run in place of the plain run, and what they write after it
+// (seis_NNN_err.octv, lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv).
 // Compiled into ./main beside main.cpp (it calls r3d_run_batched* and r3d_node_run_batched of the engine's library, so
 // it is no part of libr3d_host.so); its row arithmetic is batch_plan.hpp.
 #ifndef R3DH_BATCH_OUT_HPP_
@@ -19,9 +19,9 @@ inline std::string output_path(const std::string& dir, const std::string& name) 
 
 // What the options ask for, and where it goes.
 struct BatchJob {
-  // ERRORS: --error-batches alone; LAPSE, IMAGE, PRECISION, SHAPE: with --lapse-windows, --ttimage, --target-error,
-  // --envelope-shape; JOB_ERRORS: --job-error-batches
-  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION, SHAPE } kind = NONE;
+  // ERRORS: --error-batches alone; LAPSE, IMAGE, PRECISION, SHAPE, FIT: with --lapse-windows, --ttimage, --target-error,
+  // --envelope-shape, --envelope-fit; JOB_ERRORS: --job-error-batches
+  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION, SHAPE, FIT } kind = NONE;
   unsigned batches = 0;   // (PRECISION: of a round)
   std::string dir;   // --output-dir
   // LAPSE: the request and the array's plan, [S] receivers (include/r3d_host.h r3dh_lapse_plan)
@@ -40,10 +40,16 @@ struct BatchJob {
   std::vector<double> env_distances;
   std::vector<uint32_t> env_bins;
   std::vector<int32_t> env_clipped;
+  // FIT: the request and the array's plan, [A] receivers; the windows live in env_distances, env_bins, env_clipped
+  // (include/r3d_host.h r3dh_envfit_plan)
+  r3dh_envfit_opts fit{};              // (fit.file points into the mission the job was made from)
+  std::vector<double> fit_observed;    // [A][n_bins]
+  uint32_t fit_max_lag = 0;
 };
 
 // What a batched run hands back beside its totals: every bin's standard error, then the kind's own arrays (the shapes
-// are those of include/r3d_host.h r3dh_lapse_result, r3dh_ttimage_result, r3dh_envshape_result).  Vectors and values only.
+// are those of include/r3d_host.h r3dh_lapse_result, r3dh_ttimage_result, r3dh_envshape_result, r3dh_envfit_result).  Vectors
+// and values only.
 struct BatchProducts {
   std::vector<double> energy_se, counts_se;
   // LAPSE
@@ -62,10 +68,13 @@ struct BatchProducts {
   // SHAPE
   std::vector<double> shape, shape_se, envelope, envelope_se;
   std::vector<uint32_t> env_peak_bin, env_half_bin, env_lit;
+  // FIT (its envelope and lit: SHAPE's)
+  std::vector<double> misfit, misfit_se, xcorr, xcorr_se;
 };
 
 // The job of a simulation run (`kind` stays NONE without one of the options).  The model is needed for the arrays:
-// throws what LapseRequest / LapsePlan / TTImageRequest / TTImagePlan / EnvShapeRequest / EnvShapePlan (dataout.hpp) throw.
+// throws what LapseRequest / LapsePlan / TTImageRequest / TTImagePlan / EnvShapeRequest / EnvShapePlan / EnvFitRequest /
+// EnvFitPlan (dataout.hpp) throw.
 BatchJob make_batch_job(const MissionParams& mission, const Model& model);
 
 // What --error-batches cannot be combined with, told BEFORE the node is built.  Throws Runtime.
@@ -77,8 +86,8 @@ void check_batch_job(const BatchJob& job, size_t n_shards, uint32_t report_mask)
 BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& model, r3d_node* node, uint64_t n, uint64_t seed,
                             r3d_result& total);
 
-// seis_NNN_err.octv, then lapse.octv, ttimage.octv, precision.octv or envshape.octv, under the job's directory.  Throws
-// Runtime.
+// seis_NNN_err.octv, then lapse.octv, ttimage.octv, precision.octv, envshape.octv or envfit.octv, under the job's directory.
+// Throws Runtime.
 void write_batch_outputs(const BatchJob& job, const Model& model, const BatchProducts& products);
 
 #endif

@@ -278,6 +278,75 @@ int r3dh_write_envshape(const r3dh_model* m, const r3dh_envshape_opts* rq, const
   return 1;
 }
 
+int r3dh_observed_to_bins(const double* samples, uint32_t n_samples, uint32_t stride, double t0, double t1, double t_begin,
+                          double t_end, uint32_t n_bins, double* out) {
+  if (ObservedToBins(samples, n_samples, stride, t0, t1, t_begin, t_end, n_bins, out)) return 0;
+  return g_error = "r3dh_observed_to_bins: a null pointer, no sample, no bin, no stride, a time that is not finite, or T1 < T0 "
+                   "(T1 == T0 only with one sample)", 1;
+}
+
+int r3dh_read_octave(const char* path, const char* name, uint32_t* rows, uint32_t* cols, double* out, size_t capacity) {
+  if (!path || !name || !rows || !cols) return g_error = "r3dh_read_octave: null argument", 1;
+  try {
+    std::ifstream f(path);
+    if (!f) throw Runtime(std::string("cannot read ") + path);
+    for (const OctaveItem& item : ReadOctaveText(f)) {
+      if (item.name != name) continue;
+      *rows = (uint32_t)item.rows, *cols = (uint32_t)item.cols;
+      if (!out && capacity == 0) return 0;
+      if (!out || capacity < item.values.size())
+        throw Runtime("Octave text: variable '" + item.name + "' holds " + std::to_string(item.values.size()) + " values, more than the " +
+                      std::to_string(capacity) + " there is room for");
+      for (size_t k = 0; k < item.values.size(); k++) out[k] = item.values[k];
+      return 0;
+    }
+    throw Runtime(std::string("Octave text: ") + path + " holds no variable '" + name + "'");
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
+int r3dh_envfit_request(const r3dh_model* m, r3dh_envfit_opts* rq) {
+  if (!m || !m->mission.bEnvFit) return 0;
+  if (!rq) return 1;
+  try {
+    EnvFitRequest(*m->model, m->mission, rq);
+    return 1;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return -1;
+}
+
+int r3dh_envfit_plan(const r3dh_model* m, const r3dh_envfit_opts* rq, double* distances, uint32_t* bins, int32_t* clipped,
+                     double* observed, uint32_t* max_lag) {
+  if (!m || !rq || !distances || !bins || !clipped || !observed || !max_lag) return g_error = "r3dh_envfit_plan: null argument", 1;
+  try {
+    EnvFitPlan(*m->model, *rq, distances, bins, clipped, observed, max_lag);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
+int r3dh_write_envfit(const r3dh_model* m, const r3dh_envfit_opts* rq, const r3dh_envfit_result* res, const char* path) {
+  if (!m || !rq || !res || !path) return g_error = "r3dh_write_envfit: null argument", 1;
+  if (!res->distances || !res->bins || !res->clipped || !res->observed || !res->misfit || !res->misfit_se || !res->xcorr ||
+      !res->xcorr_se || !res->envelope || !res->lit)
+    return g_error = "r3dh_write_envfit: null array in the result", 1;
+  try {
+    std::ofstream f(path);
+    OutputEnvFit(*m->model, *rq, *res, f);
+    if (!f) throw Runtime(std::string("cannot write ") + path);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
 int r3dh_precision_request(const r3dh_model* m, r3d_precision_spec* spec, uint32_t* max_rounds) {
   if (!m || !m->mission.bTarget) return 0;
   try {

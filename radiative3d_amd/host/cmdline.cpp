@@ -23,7 +23,8 @@ enum OptID {
   OPTX_LAPSE, OPTX_LAPSE_AXES, OPTX_LAPSE_GEOSPREAD, OPTX_LAPSE_RANGES, OPTX_LAPSE_ARRAY,
   OPTX_TTIMAGE, OPTX_TTIMAGE_ARRAY, OPTX_TTIMAGE_AXES, OPTX_TTIMAGE_FIT, OPTX_TTIMAGE_NORMCURVE,
   OPTX_TARGET, OPTX_TARGET_ARRAY, OPTX_TARGET_COMPONENTS,
-  OPTX_ENVSHAPE, OPTX_ENVSHAPE_ARRAY, OPTX_ENVSHAPE_AXES
+  OPTX_ENVSHAPE, OPTX_ENVSHAPE_ARRAY, OPTX_ENVSHAPE_AXES,
+  OPTX_ENVFIT, OPTX_ENVFIT_ARRAY, OPTX_ENVFIT_AXES, OPTX_ENVFIT_ENERGY
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -63,7 +64,9 @@ const std::map<std::string, OptID>& option_table() {
       {"--ttimage", OPTX_TTIMAGE}, {"--ttimage-array", OPTX_TTIMAGE_ARRAY}, {"--ttimage-axes", OPTX_TTIMAGE_AXES},
       {"--ttimage-fit", OPTX_TTIMAGE_FIT}, {"--ttimage-normcurve", OPTX_TTIMAGE_NORMCURVE},
       {"--target-error", OPTX_TARGET}, {"--target-array", OPTX_TARGET_ARRAY}, {"--target-components", OPTX_TARGET_COMPONENTS},
-      {"--envelope-shape", OPTX_ENVSHAPE}, {"--envelope-array", OPTX_ENVSHAPE_ARRAY}, {"--envelope-axes", OPTX_ENVSHAPE_AXES}};
+      {"--envelope-shape", OPTX_ENVSHAPE}, {"--envelope-array", OPTX_ENVSHAPE_ARRAY}, {"--envelope-axes", OPTX_ENVSHAPE_AXES},
+      {"--envelope-fit", OPTX_ENVFIT}, {"--envelope-fit-array", OPTX_ENVFIT_ARRAY}, {"--envelope-fit-axes", OPTX_ENVFIT_AXES},
+      {"--envelope-fit-energy", OPTX_ENVFIT_ENERGY}};
   return t;
 }
 
@@ -486,6 +489,50 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
             throw Runtime("--envelope-axes=X,Y,Z: the weights must be finite and not negative (the envelope's energies must not be).");
         mission.EnvCompanion = "--envelope-axes";
         break;
+      case OPTX_ENVFIT: {
+        static const char* const form = "--envelope-fit=FILE[,V,T0,O,E[,SMOOTH[,OBSSMOOTH[,MAXLAG_SECONDS]]]]: ";
+        mission.FitFile = o.text();
+        long smooth = (long)mission.FitSmooth, obs_smooth = (long)mission.FitObsSmooth;
+        if (o.has()) {
+          for (int k = 0; k < 2; k++) mission.FitEdge[k] = o.real();
+          for (int k = 0; k < 2; k++) mission.FitWindow[k] = o.real();
+          if (o.has()) smooth = o.integer();
+          if (o.has()) obs_smooth = o.integer();
+          if (o.has()) mission.FitMaxLagSeconds = o.real();
+        }
+        const double* w = mission.FitWindow;
+        if (mission.FitFile.empty()) throw Runtime(std::string(form) + "FILE, the observed envelopes, must be named.");
+        if (!(mission.FitEdge[0] > 0) || !std::isfinite(mission.FitEdge[0]) || !std::isfinite(mission.FitEdge[1]) ||
+            !std::isfinite(w[0]) || (!std::isnan(w[1]) && (!std::isfinite(w[1]) || !(w[1] >= w[0]))))
+          throw Runtime(std::string(form) + "the phase velocity V must be positive, the window's end E not before its start O, "
+                        "and every number finite.");
+        if (smooth < 0 || smooth > 64 || obs_smooth < 0 || obs_smooth > 64)
+          throw Runtime(std::string(form) + "SMOOTH and OBSSMOOTH, the three-point smoothing passes over the synthetic and the "
+                        "observed envelope, must be 0 .. 64 (got " + std::to_string(smooth) + " and " + std::to_string(obs_smooth) + ").");
+        if (!(mission.FitMaxLagSeconds >= 0) || !std::isfinite(mission.FitMaxLagSeconds))
+          throw Runtime(std::string(form) + "MAXLAG_SECONDS, the largest lag that is tried, must be finite and not negative.");
+        mission.FitSmooth = (unsigned)smooth, mission.FitObsSmooth = (unsigned)obs_smooth;
+        mission.bEnvFit = true;
+        break;
+      }
+      case OPTX_ENVFIT_ARRAY:
+        mission.FitArray[0] = o.integer();
+        mission.FitArray[1] = o.integer();
+        if (mission.FitArray[0] < 0 || mission.FitArray[1] < mission.FitArray[0])
+          throw Runtime("--envelope-fit-array=FIRST,LAST: seismometer indices with 0 <= FIRST <= LAST.");
+        mission.FitCompanion = "--envelope-fit-array";
+        break;
+      case OPTX_ENVFIT_AXES:
+        for (int k = 0; k < 3; k++) mission.FitAxes[k] = o.real();
+        for (int k = 0; k < 3; k++)
+          if (!std::isfinite(mission.FitAxes[k]) || mission.FitAxes[k] < 0)
+            throw Runtime("--envelope-fit-axes=X,Y,Z: the weights must be finite and not negative (roots are taken of the weighted energy).");
+        mission.FitCompanion = "--envelope-fit-axes";
+        break;
+      case OPTX_ENVFIT_ENERGY:
+        mission.bEnvFitEnergy = true;
+        mission.FitCompanion = "--envelope-fit-energy";
+        break;
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }
@@ -577,6 +624,27 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
                     "rounds keep only their moments): out of scope.");
     if (ReportMaskFromKeywords(mission.Reports))
       throw Runtime("--envelope-shape cannot be combined with --reports (the event log's launches run one at a time).");
+  }
+  // the envelope misfit's errors come from one device's batches, and it keeps the run's batch blocks for itself
+  if (mission.FitCompanion && !mission.bEnvFit)
+    throw Runtime(std::string(mission.FitCompanion) + " needs --envelope-fit: it only says how that misfit is made.");
+  if (mission.bEnvFit) {
+    if (mission.JobErrorBatches)
+      throw Runtime("--envelope-fit cannot be combined with --job-error-batches: the misfit is made where ONE device's batch "
+                    "blocks lie (r3d_run_batched_envelope_misfit); a job sharded over devices has no misfit call.  Use "
+                    "--error-batches=B.");
+    if (!mission.ErrorBatches)
+      throw Runtime("--envelope-fit needs --error-batches=B: the standard errors of the misfit's numbers are jackknives over "
+                    "the B batches.");
+    if (mission.bLapse || mission.bTTImage || mission.bEnvShape)
+      throw Runtime(std::string("--envelope-fit cannot be combined with ") +
+                    (mission.bLapse ? "--lapse-windows" : mission.bTTImage ? "--ttimage" : "--envelope-shape") +
+                    " in one run (each keeps the run's batch blocks for itself): out of scope.");
+    if (mission.bTarget)
+      throw Runtime("--envelope-fit cannot be combined with --target-error (the misfit needs one run's batch blocks, the "
+                    "rounds keep only their moments): out of scope.");
+    if (ReportMaskFromKeywords(mission.Reports))
+      throw Runtime("--envelope-fit cannot be combined with --reports (the event log's launches run one at a time).");
   }
   // the views and the maps are made from the grid: none of their options means anything without it
   if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile || mission.bScatterMaps))

@@ -9,7 +9,8 @@
 // --error-batches / --job-error-batches (per-bin standard errors), --lapse-windows and its four companions (lapse-window
 // energies and coda ratios with batch errors), --ttimage and its four (the array's travel-time image with jackknife errors),
 // --target-error and its two (a run to a target standard error, in rounds judged on the GPU), --envelope-shape and its two
-// (peak delay, decay, centroid and width of every array receiver's envelope with jackknife errors).
+// (peak delay, decay, centroid and width of every array receiver's envelope with jackknife errors), --envelope-fit and its three
+// (the misfit of every array receiver's envelope against an observed one, with jackknife errors).
 #ifndef R3DH_CMDLINE_HPP_
 #define R3DH_CMDLINE_HPP_
 
@@ -100,6 +101,19 @@ struct MissionParams {
   double EnvEdge[2] = {3.6, 0.0}, EnvWindow[2] = {0.0, std::nan("")}, EnvAxes[3] = {1.0, 1.0, 1.0};
   unsigned EnvSmooth = 8;
   long EnvArray[2] = {0, -1};             // LAST < 0: through the last receiver
+  // --envelope-fit=FILE[,V,T0,O,E[,SMOOTH[,OBSSMOOTH[,MAXLAG_SECONDS]]]]: per receiver of an array the misfit of its smoothed
+  // amplitude envelope against the observed one FILE holds (GNU/Octave text: ObsTimeWindow [1 x 2], ObsEnvelope [n_samples x
+  // A], one column per array receiver) in the window from O to E seconds behind the phase edge -- scale, correlation,
+  // residual, peak-normalised distance, best lag within MAXLAG_SECONDS and centroid shift -- with jackknife errors from the
+  // batches of --error-batches (include/r3d.h r3d_run_batched_envelope_misfit), as envfit.octv.  Defaults as
+  // --envelope-shape's; OBSSMOOTH 0 (envcompare.m's), MAXLAG_SECONDS 0.  --envelope-fit-array=FIRST,LAST the receivers
+  // (default all), --envelope-fit-axes=X,Y,Z the weights of the three trace axes, --envelope-fit-energy: FILE holds energies.
+  bool bEnvFit = false, bEnvFitEnergy = false;
+  const char* FitCompanion = nullptr;     // one of the three that was given (they are refused without --envelope-fit)
+  Text FitFile;
+  double FitEdge[2] = {3.6, 0.0}, FitWindow[2] = {0.0, std::nan("")}, FitAxes[3] = {1.0, 1.0, 1.0}, FitMaxLagSeconds = 0.0;
+  unsigned FitSmooth = 8, FitObsSmooth = 0;
+  long FitArray[2] = {0, -1};             // LAST < 0: through the last receiver
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

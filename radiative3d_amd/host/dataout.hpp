@@ -12,8 +12,10 @@
 #ifndef R3DH_DATAOUT_HPP_
 #define R3DH_DATAOUT_HPP_
 
+#include <istream>
 #include <ostream>
 #include <string>
+#include <vector>
 
 #include "../../include/r3d_host.h"   // r3dh_view_header, r3dh_maps_header
 #include "model.hpp"
@@ -64,6 +66,25 @@ void OutputTTImage(const Model& model, const r3dh_ttimage_opts& rq, const r3dh_t
 void EnvShapeRequest(const Model& model, const MissionParams& mission, r3dh_envshape_opts* rq);
 void EnvShapePlan(const Model& model, const r3dh_envshape_opts& rq, double* distances, uint32_t* bins, int32_t* clipped);
 void OutputEnvShape(const Model& model, const r3dh_envshape_opts& rq, const r3dh_envshape_result& res, std::ostream& out);
+
+// The envelope misfit of --envelope-fit (include/r3d_host.h has the request, the plan, the file's items and the two plain
+// pieces).  ObservedToBins: r3dh_observed_to_bins' arithmetic (false, nothing written, for what it has no answer for).
+// OctaveItem / ReadOctaveText: the reader of the writer's own `scalar` and `matrix` blocks; throws, naming the variable, for
+// anything else.  EnvFitRequest fills *rq from the mission (throws if --envelope-fit-array names a receiver the model does
+// not have); EnvFitPlan the array's distances, windows, clipped flags, observed rows on the run's bins and the lag in bins;
+// OutputEnvFit writes the file's text.
+bool ObservedToBins(const double* samples, uint32_t n_samples, uint32_t stride, double t0, double t1, double t_begin, double t_end,
+                    uint32_t n_bins, double* out);
+struct OctaveItem {
+  std::string name;
+  size_t rows = 0, cols = 0;
+  std::vector<double> values;   // row-major
+};
+std::vector<OctaveItem> ReadOctaveText(std::istream& in);
+void EnvFitRequest(const Model& model, const MissionParams& mission, r3dh_envfit_opts* rq);
+void EnvFitPlan(const Model& model, const r3dh_envfit_opts& rq, double* distances, uint32_t* bins, int32_t* clipped, double* observed,
+                uint32_t* max_lag);
+void OutputEnvFit(const Model& model, const r3dh_envfit_opts& rq, const r3dh_envfit_result& res, std::ostream& out);
 
 // precision.octv of --target-error (include/r3d_host.h r3dh_write_precision has the file's items): the target, the
 // selection, what was run and the judge's tables (their rows are batch_plan.hpp's).  Needs no model.  PrecisionRequest

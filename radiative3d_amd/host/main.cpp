@@ -5,14 +5,14 @@
 // files.  The N-phonon loop itself (Model::RunSimulation, model.cpp:602-633)
 // is one call into the engine's C-ABI.  What a run with --scatter-grid writes afterwards (the grid, its views, its maps)
 // is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches, --lapse-windows, --ttimage,
-// --target-error and --envelope-shape run and write (the batched runs, seis_NNN_err.octv, lapse.octv, ttimage.octv,
-// precision.octv, envshape.octv) is the stage of batch_out.cpp.  This file
+// --target-error, --envelope-shape and --envelope-fit run and write (the batched runs, seis_NNN_err.octv, lapse.octv,
+// ttimage.octv, precision.octv, envshape.octv, envfit.octv) is the stage of batch_out.cpp.  This file
 // makes both jobs, has them checked before the node is built, and calls each once to run and once to write.
 //
 // Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B`,
 // `--job-error-batches=N` (error bars of a job on any number of shards), `--lapse-windows` (lapse.octv), `--ttimage`
 // (ttimage.octv), `--target-error` (a run that stops when its error bars are good enough; precision.octv) and
-// `--envelope-shape` (envshape.octv) are accepted
+// `--envelope-shape` (envshape.octv) and `--envelope-fit` (the misfit against observed envelopes; envfit.octv) are accepted
 // (the reference seeds from the clock, is single-process, has no event histogram and no error bars, and takes its phonon
 // count from a hand-tuned table); the `--reports` stream is written
 // after the run, grouped by history, where the reference writes its lines as they happen (the engine appends binary
@@ -260,7 +260,17 @@ int main(int argc, char* argv[]) {
               << "edge, after SMOOTH three-point passes (envcompare.m) -- energy, peak, peak time, the time of the fall to half the\n"
               << "peak, centroid and width -- made on the GPU with jackknife standard errors, as envshape.octv;\n"
               << "--envelope-array=FIRST,LAST (default all)  --envelope-axes=X,Y,Z (default 1,1,1).  Not in one run with\n"
-              << "--lapse-windows, --ttimage, --target-error, --job-error-batches or --reports (out of scope)\n\n";
+              << "--lapse-windows, --ttimage, --target-error, --job-error-batches or --reports (out of scope)\n"
+              << "--envelope-fit=FILE[,V,T0,O,E[,SMOOTH[,OBSSMOOTH[,MAXLAG_SECONDS]]]] (with --error-batches; window and SMOOTH as\n"
+              << "--envelope-shape, OBSSMOOTH 0, MAXLAG_SECONDS 0): per receiver of an array the misfit of its smoothed amplitude\n"
+              << "envelope against the observed one of FILE (GNU/Octave text: ObsTimeWindow [1 x 2], ObsEnvelope [n_samples x A], one\n"
+              << "column per receiver, resampled onto the run's bins) -- the least-squares scale, the correlation, the residual, the\n"
+              << "distance of the peak-normalised curves (envcompare.m), the best lag within MAXLAG_SECONDS and the centroid shift --\n"
+              << "made on the GPU with jackknife standard errors, as envfit.octv;\n"
+              << "--envelope-fit-array=FIRST,LAST (default all)  --envelope-fit-axes=X,Y,Z (default 1,1,1)  --envelope-fit-energy: FILE\n"
+              << "holds energies, not amplitudes.  (The names share no prefix rule with --envelope-array / --envelope-axes: options\n"
+              << "are matched whole.)  Not in one run with --lapse-windows, --ttimage, --target-error, --envelope-shape,\n"
+              << "--job-error-batches or --reports (out of scope)\n\n";
     return 0;
   }
   // A simulation run makes its tables where it uses them (seconds of host work and GBs of upload

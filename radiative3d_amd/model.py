@@ -445,6 +445,71 @@ class Model:
         if self._lib.r3dh_write_envshape(self._h, C.byref(rq), C.byref(res), str(path).encode()):
             raise RuntimeError("write_envshape failed: " + self._lib.r3dh_last_error().decode())
 
+    @property
+    def envfit_request(self):
+        """What --envelope-fit=FILE[,V,T0,O,E[,SMOOTH[,OBSSMOOTH[,MAXLAG_SECONDS]]]] and its companions (--envelope-fit-array,
+        --envelope-fit-axes, --envelope-fit-energy) asked for: None, or dict(file, first, last, smooth_syn, smooth_obs,
+        amplitude, energy_file, phase_edge, window, axes, max_lag_seconds) (include/r3d_host.h r3dh_envfit_opts)."""
+        rq = _ffi.EnvFitOpts()
+        rc = self._lib.r3dh_envfit_request(self._h, C.byref(rq))
+        if rc < 0:
+            raise RuntimeError("envfit_request failed: " + self._lib.r3dh_last_error().decode())
+        if rc == 0:
+            return None
+        return dict(file=rq.file.decode(), first=int(rq.first), last=int(rq.last), smooth_syn=int(rq.smooth_syn),
+                    smooth_obs=int(rq.smooth_obs), amplitude=int(rq.amplitude), energy_file=int(rq.energy_file),
+                    phase_edge=tuple(rq.phase_edge), window=tuple(rq.window), axes=tuple(rq.axes),
+                    max_lag_seconds=float(rq.max_lag_seconds))
+
+    @staticmethod
+    def _envfit_opts(request):
+        edge, window = request.get("phase_edge", (3.6, 0.0)), request.get("window", (0.0, math.nan))
+        return _ffi.EnvFitOpts(size=C.sizeof(_ffi.EnvFitOpts), first=int(request["first"]), last=int(request["last"]),
+                               smooth_syn=int(request.get("smooth_syn", 8)), smooth_obs=int(request.get("smooth_obs", 0)),
+                               amplitude=int(request.get("amplitude", 1)), energy_file=int(request.get("energy_file", 0)),
+                               phase_edge=(C.c_double * 2)(*[float(v) for v in edge]),
+                               window=(C.c_double * 2)(*[float(v) for v in window]),
+                               axes=(C.c_double * 3)(*[float(v) for v in request.get("axes", (1, 1, 1))]),
+                               max_lag_seconds=float(request.get("max_lag_seconds", 0.0)), file=str(request["file"]).encode())
+
+    def envfit_plan(self, request=None):
+        """(distances [A], bins [A, 2], clipped [A], observed [A, n_bins], max_lag) of the fit's array (`request`: a dict as
+        envfit_request gives; None: the model's own): the envelope shape's window rule (envshape_plan), the observed
+        envelopes of the request's file resampled onto the run's bins (observed_to_bins; their roots where the file holds
+        energies and amplitudes are compared) and the largest lag in bins."""
+        request = request if request is not None else self.envfit_request
+        if request is None:
+            raise RuntimeError("the model's arguments hold no --envelope-fit")
+        rq = self._envfit_opts(request)
+        A = int(rq.last) - int(rq.first) + 1
+        if A < 1:
+            raise ValueError("envfit request: first > last")
+        dist, bins, clipped = np.zeros(A), np.zeros((A, 2), dtype=np.uint32), np.zeros(A, dtype=np.int32)
+        observed, max_lag = np.zeros((A, self.n_bins)), C.c_uint32(0)
+        if self._lib.r3dh_envfit_plan(self._h, C.byref(rq), dist.ctypes.data_as(_ffi._dp), bins.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                      clipped.ctypes.data_as(C.POINTER(C.c_int32)), observed.ctypes.data_as(_ffi._dp),
+                                      C.byref(max_lag)):
+            raise RuntimeError("envfit_plan failed: " + self._lib.r3dh_last_error().decode())
+        return dist, bins, clipped, observed, int(max_lag.value)
+
+    def write_envfit(self, path, plan, fit, n_batches, request=None):
+        """Write envfit.octv (include/r3d_host.h r3dh_write_envfit) to `path`: plan = envfit_plan(request), fit the dict
+        Engine.run_batched_envelope_misfit returned for the request's array and the plan's lag."""
+        request = request if request is not None else self.envfit_request
+        if request is None:
+            raise RuntimeError("the model's arguments hold no --envelope-fit")
+        rq = self._envfit_opts(request)
+        keep = [np.ascontiguousarray(plan[0], dtype=np.float64), np.ascontiguousarray(plan[1], dtype=np.uint32),
+                np.ascontiguousarray(plan[2], dtype=np.int32), np.ascontiguousarray(plan[3], dtype=np.float64)]
+        for name in ("misfit", "misfit_se", "xcorr", "xcorr_se", "envelope"):
+            keep.append(np.ascontiguousarray(fit[name], dtype=np.float64))
+        keep.append(np.ascontiguousarray(fit["lit"], dtype=np.uint32))
+        if keep[6].shape[-1] != 2 * int(plan[4]) + 1:
+            raise ValueError("the fit's xcorr has not the plan's 2 max_lag + 1 lags")
+        res = _ffi.EnvFitResult(C.sizeof(_ffi.EnvFitResult), int(n_batches), int(plan[4]), 0, *[a.ctypes.data for a in keep])
+        if self._lib.r3dh_write_envfit(self._h, C.byref(rq), C.byref(res), str(path).encode()):
+            raise RuntimeError("write_envfit failed: " + self._lib.r3dh_last_error().decode())
+
     def new_result(self):
         return Result(self.n_seismometers, self.n_bins)
 
@@ -709,6 +774,97 @@ def envelope_shape(batch_energy, bins, first, last, weights, smooth=8, with_se=N
                                 stream)
     if rc:
         raise RuntimeError("r3d_envelope_shape failed: " + lib.r3d_last_error().decode())
+    return out
+
+
+def observed_to_bins(samples, t0, t1, t_begin, t_end, n_bins):
+    """r3dh_observed_to_bins (include/r3d_host.h): the observed envelope `samples` (sample i at t0 + i (t1 - t0) / (n - 1))
+    resampled by linear interpolation at linspace(t_begin, t_end, n_bins); +0.0 outside the observed span."""
+    lib = _ffi.host_lib()
+    v = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)
+    out = np.full(max(int(n_bins), 0), -7.0)
+    if lib.r3dh_observed_to_bins(v.ctypes.data_as(_ffi._dp), v.size, 1, float(t0), float(t1), float(t_begin), float(t_end),
+                                 int(n_bins), out.ctypes.data_as(_ffi._dp)):
+        raise RuntimeError(lib.r3dh_last_error().decode())
+    return out
+
+
+def read_octave(path, name):
+    """r3dh_read_octave (include/r3d_host.h): the variable `name` of a GNU/Octave text file of `scalar` and `matrix` blocks,
+    as a float64 array [rows, cols]."""
+    lib = _ffi.host_lib()
+    rows, cols = C.c_uint32(0), C.c_uint32(0)
+    if lib.r3dh_read_octave(str(path).encode(), name.encode(), C.byref(rows), C.byref(cols), None, 0):
+        raise RuntimeError(lib.r3dh_last_error().decode())
+    out = np.zeros((rows.value, cols.value))
+    if lib.r3dh_read_octave(str(path).encode(), name.encode(), C.byref(rows), C.byref(cols), out.ctypes.data_as(_ffi._dp), out.size):
+        raise RuntimeError(lib.r3dh_last_error().decode())
+    return out
+
+
+def misfit_spec(n_seismometers, n_bins, first, last, weights, bins_ptr, observed_ptr, smooth_syn=8, smooth_obs=0, max_lag=0,
+                amplitude=1):
+    """An r3d_misfit_spec (include/r3d.h): bins_ptr the address of the uint32 [A][2] b0, b1 pairs of the array's receivers
+    first .. last, observed_ptr that of the float64 [A][n_bins] observed amplitudes on the run's bins -- both on the device
+    for envelope_misfit, on the host for Engine.run_batched_envelope_misfit."""
+    w = [float(v) for v in weights]
+    if len(w) != _ffi.R3D_N_ENERGY:
+        raise ValueError("five component weights (X, Y, Z, P, S) are needed")
+    return _ffi.MisfitSpec(size=C.sizeof(_ffi.MisfitSpec), n_seismometers=int(n_seismometers), n_bins=int(n_bins),
+                           first=int(first), last=int(last), smooth_syn=int(smooth_syn), smooth_obs=int(smooth_obs),
+                           max_lag=int(max_lag), amplitude=int(amplitude), d_bins=bins_ptr, d_observed=observed_ptr,
+                           weight=(C.c_double * _ffi.R3D_N_ENERGY)(*w))
+
+
+def envelope_misfit(batch_energy, bins, observed, first, last, weights, smooth_syn=8, smooth_obs=0, max_lag=0, amplitude=1,
+                    with_se=None, with_xcorr=True, with_envelope=True, stream=None):
+    """r3d_envelope_misfit on torch tensors of one device: batch_energy [B, S, n_bins, 5] float64 are B batch blocks, the array
+    the receivers first .. last (A of them), bins [A, 2] int32 each receiver's window of bins b0, b1, observed [A, n_bins]
+    float64 the observed envelope on the run's bins (amplitudes), weights the five component weights (>= 0), smooth_syn /
+    smooth_obs the three-point passes over either row, max_lag the largest lag in bins, amplitude 1 to compare the roots of
+    the energies.  Returns a dict of tensors, all WRITTEN: misfit [A, 6] (scale, rho, chi, peak-normalised distance, lag
+    in bins, centroid distance in bins), misfit_se [A, 6] (with_se; default: B >= 2), xcorr and xcorr_se [A, 2 max_lag + 1]
+    (with_xcorr), envelope [A, n_bins] (with_envelope), lit [A] (int32), bad and bad_observed [1] (int64).  include/r3d.h
+    has the arithmetic.  Asynchronous on `stream` (a raw hipStream_t; None: torch's current one)."""
+    import torch
+    lib = _ffi.hip_lib()
+    if batch_energy.dim() != 4 or batch_energy.shape[3] != _ffi.R3D_N_ENERGY or batch_energy.dtype != torch.float64:
+        raise ValueError("batch_energy must be float64 [B, S, n_bins, 5]")
+    if not batch_energy.is_cuda or not batch_energy.is_contiguous():
+        raise ValueError("the blocks must be a contiguous tensor on a GPU")
+    B, S, n_bins = (int(v) for v in batch_energy.shape[:3])
+    dev = batch_energy.device
+    A = int(last) - int(first) + 1
+    if A < 1 or last >= S:
+        raise ValueError("the array first .. last must lie within the blocks' seismometers")
+    if tuple(bins.shape) != (A, 2) or bins.element_size() != 4 or bins.dtype.is_floating_point or bins.device != dev \
+            or not bins.is_contiguous():
+        raise ValueError("bins must be a contiguous 32-bit integer tensor [A, 2] on the blocks' GPU")
+    if tuple(observed.shape) != (A, n_bins) or observed.dtype != torch.float64 or observed.device != dev \
+            or not observed.is_contiguous():
+        raise ValueError("observed must be a contiguous float64 tensor [A, n_bins] on the blocks' GPU")
+    with_se = B >= 2 if with_se is None else with_se
+    n_lags = 2 * int(max_lag) + 1
+
+    def f64(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=dev)
+
+    def i64():
+        return torch.zeros(1, dtype=torch.int64, device=dev)
+    out = dict(misfit=f64(A, _ffi.R3D_MISFIT_N), misfit_se=f64(A, _ffi.R3D_MISFIT_N) if with_se else None,
+               xcorr=f64(A, n_lags) if with_xcorr else None, xcorr_se=f64(A, n_lags) if with_xcorr and with_se else None,
+               envelope=f64(A, n_bins) if with_envelope else None, lit=torch.empty(A, dtype=torch.int32, device=dev),
+               bad=i64(), bad_observed=i64())
+    spec = misfit_spec(S, n_bins, first, last, weights, bins.data_ptr(), observed.data_ptr(), smooth_syn, smooth_obs, max_lag,
+                       amplitude)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    ptr = {k: (v.data_ptr() if v is not None else None) for k, v in out.items()}
+    rc = lib.r3d_envelope_misfit(dev.index or 0, B, batch_energy.data_ptr(), C.byref(spec), ptr["misfit"], ptr["misfit_se"],
+                                 ptr["xcorr"], ptr["xcorr_se"], ptr["envelope"], ptr["lit"], ptr["bad"], ptr["bad_observed"],
+                                 stream)
+    if rc:
+        raise RuntimeError("r3d_envelope_misfit failed: " + lib.r3d_last_error().decode())
     return out
 
 
@@ -1270,6 +1426,31 @@ class Engine:
         res, ese, cse = _run_batched_to_host(self._lib, "r3d_run_batched_envelope_shape", self._e, m, n, first_id, seed,
                                              n_batches, None, C.byref(spec), C.byref(out))
         return res, ese, cse, shp
+
+    def run_batched_envelope_misfit(self, n, n_batches, bins, observed, first, last, weights, smooth_syn=8, smooth_obs=0,
+                                    max_lag=0, amplitude=1, first_id=0, seed=0x5EED):
+        """run_batched that also makes the envelope misfit of the receivers first .. last against `observed` where the batch
+        blocks lie (include/r3d.h r3d_run_batched_envelope_misfit): bins [A, 2] each receiver's window b0, b1 and observed
+        [A, n_bins] the observed amplitudes on the run's bins (host; Model.envfit_plan makes both).  Returns (Result,
+        energy_se, counts_se, fit): a dict of misfit, misfit_se [A, 6], xcorr, xcorr_se [A, 2 max_lag + 1], envelope [A,
+        n_bins] and lit [A] (uint32)."""
+        m = self.model
+        A = int(last) - int(first) + 1
+        if A < 1:
+            raise ValueError("the array needs first <= last")
+        b = np.ascontiguousarray(bins, dtype=np.uint32)
+        o = np.ascontiguousarray(observed, dtype=np.float64)
+        if b.shape != (A, 2) or o.shape != (A, m.n_bins):
+            raise ValueError("bins must be [A, 2] and observed [A, n_bins]")
+        spec = misfit_spec(m.n_seismometers, m.n_bins, first, last, weights, b.ctypes.data, o.ctypes.data, smooth_syn, smooth_obs,
+                           max_lag, amplitude)
+        n_lags = 2 * int(max_lag) + 1
+        fit = dict(misfit=np.zeros((A, _ffi.R3D_MISFIT_N)), misfit_se=np.zeros((A, _ffi.R3D_MISFIT_N)), xcorr=np.zeros((A, n_lags)),
+                   xcorr_se=np.zeros((A, n_lags)), envelope=np.zeros((A, m.n_bins)), lit=np.zeros(A, dtype=np.uint32))
+        out = _ffi.MisfitResult(size=C.sizeof(_ffi.MisfitResult), **{k: v.ctypes.data for k, v in fit.items()})
+        res, ese, cse = _run_batched_to_host(self._lib, "r3d_run_batched_envelope_misfit", self._e, m, n, first_id, seed,
+                                             n_batches, None, C.byref(spec), C.byref(out))
+        return res, ese, cse, fit
 
     def run_device(self, n, first_id, seed, d_energy, d_counts, d_scalars, stream=None, carry=None):
         """Asynchronous, device-resident accumulate (pointers are raw device
