@@ -60,11 +60,11 @@ ENGINE_HDR := $(wildcard $(CSRC)/*.h) include/r3d.h
 ADDONS := stats views maps arrays precision shapes fits
 addon_src = $(wildcard radiative3d_amd/$(1)/*.hip)
 # (arrays/ takes the bin energy and the strand constants from stats/r3d_window_sums.h; shapes/ those and the scans, the
-# running maximum and the jackknife from arrays/r3d_array_image.h; fits/ all of that and the smoothing rule from
-# shapes/r3d_envelope_shape.h)
+# running maximum and the jackknife from arrays/r3d_array_image.h; fits/ all of that and every header of shapes/: the rows
+# of a receiver with their smoothing rule, r3d_envelope_rows.h, and the shape's arithmetic)
 addon_hdr = $(wildcard radiative3d_amd/$(1)/*.h) $(COMMON)/r3d_entry.h include/r3d.h $(if $(filter arrays,$(1)),radiative3d_amd/stats/r3d_window_sums.h) \
             $(if $(filter shapes,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h) \
-            $(if $(filter fits,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h radiative3d_amd/shapes/r3d_envelope_shape.h)
+            $(if $(filter fits,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h $(wildcard radiative3d_amd/shapes/*.h))
 OBJDIR   := build/obj
 
 # (the default goal is the first target of the file: it has to come before the generated object rules)

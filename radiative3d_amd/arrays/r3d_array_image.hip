@@ -167,17 +167,7 @@ __global__ __launch_bounds__(kImageBlock) void array_bad_kernel(const double* __
 
 // What r3d_array_image and r3d_run_batched_array_image refuse on the spec alone (0: nothing; else the message is set).
 int check_array_spec(const char* who, const r3d_array_image_spec* a) {
-  if (!a) return refuse(who, "null array spec");
-  if (a->size != sizeof(r3d_array_image_spec))
-    return refuse(who, "r3d_array_image_spec.size is " + std::to_string(a->size) + ", this library's is " +
-                           std::to_string(sizeof(r3d_array_image_spec)));
-  if (a->n_bins == 0) return refuse(who, "n_bins must be at least 1");
-  if (a->last < a->first || a->last >= a->n_seismometers)
-    return refuse(who, "the array " + std::to_string(a->first) + " .. " + std::to_string(a->last) + " is not within the " +
-                           std::to_string(a->n_seismometers) + " seismometers");
-  for (int k = 0; k < R3D_N_ENERGY; k++)
-    if (!std::isfinite(a->weight[k]) || a->weight[k] < 0.0)
-      return refuse(who, "weight " + std::to_string(k) + " is negative or not finite (roots are taken of the weighted energy)");
+  if (check_receiver_array_spec(who, a, "array", "r3d_array_image_spec", "roots are taken of the weighted energy")) return 1;
   if (a->gamma_log2 > kArrayMaxGammaLog2) return refuse(who, "gamma_log2 must be 0, 1 or 2 (gamma 1, 2 or 4)");
   return 0;
 }

@@ -1,12 +1,13 @@
 // r3d_entry.h -- what an entry point of the C-ABI that lives OUTSIDE the engine needs around its launch: the engine's
 // error text, the caller's device kept across the call, device scratch that frees itself, the refusals the calls on
-// the event grid share, and those of the batched runs with the way they learn their engine's device, the format of
+// the event grid share, those the specs of the receiver-array add-ons share, and those of the batched runs with the way they learn their engine's device, the format of
 // the block their results come down in (ResultBlock) and the way a run is brought to the host (BatchedRun).  Host code
 // only, all inline.  An add-on (stats/, views/, maps/, arrays/, precision/, shapes/, fits/) includes this and include/r3d.h and
 // nothing from csrc/; csrc/r3d_volume.hip, whose entry points are of the same kind, uses it too.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <optional>
 #include <string>
@@ -74,6 +75,24 @@ inline const char* bad_frame_range(const r3d_volume_desc* v, uint32_t frame_begi
   if (frame_begin > frame_end) return "frame_end before frame_begin";
   if (frame_end > v->n_frames) return "frame_end beyond the grid's frames";
   return nullptr;
+}
+
+// What the calls on a receiver array (arrays/, shapes/, fits/) refuse on the fields their specs share -- size, n_bins, first,
+// last, n_seismometers, weight[] -- (0: nothing; else the message is set).  `what`: the spec in the message's words; `type`:
+// its struct; `why_weights`: why this call cannot take a negative weight.
+template <class Spec>
+int check_receiver_array_spec(const char* who, const Spec* a, const char* what, const char* type, const char* why_weights) {
+  if (!a) return refuse(who, std::string("null ") + what + " spec");
+  if (a->size != sizeof(Spec))
+    return refuse(who, std::string(type) + ".size is " + std::to_string(a->size) + ", this library's is " + std::to_string(sizeof(Spec)));
+  if (a->n_bins == 0) return refuse(who, "n_bins must be at least 1");
+  if (a->last < a->first || a->last >= a->n_seismometers)
+    return refuse(who, "the array " + std::to_string(a->first) + " .. " + std::to_string(a->last) + " is not within the " +
+                           std::to_string(a->n_seismometers) + " seismometers");
+  for (int k = 0; k < R3D_N_ENERGY; k++)
+    if (!std::isfinite(a->weight[k]) || a->weight[k] < 0.0)
+      return refuse(who, "weight " + std::to_string(k) + " is negative or not finite (" + why_weights + ")");
+  return 0;
 }
 
 // ---- what the batched runs share (stats/ r3d_run_batched and its kin, arrays/ r3d_run_batched_array_image, shapes/) ----

@@ -13,8 +13,8 @@
 // kEnvelopeMaxSmooth; max_lag = Lmax, 0 .. kMisfitMaxLag.
 //
 // ROWS.  Per window bin k, e_j = window_bin_energy(x_j[s][b0 + k], w), and array_leave_one_out gives the total t[k] and, for
-// B >= 2, the B rows t_(j)[k] -- exactly as ../shapes/r3d_envelope_shape.h makes them.  a = sqrt(row) if amplitude is set
-// (IEEE), else the row; u = S^ms(a) by envelope_smooth_at.  The observed row is o = S^mo(obs[i][b0 .. b1)), made once per
+// B >= 2, the B rows t_(j)[k] -- by the code that makes the shape's, ../shapes/r3d_envelope_rows.h.  a = sqrt(row) if
+// amplitude is set (IEEE), else the row (envelope_row_value); u = S^ms(a) by envelope_smooth_at.  The observed row is o = S^mo(obs[i][b0 .. b1)), made once per
 // receiver and shared by all B + 1 rows.
 //
 // REDUCTIONS, all by array_row_reduce's 64 strands and tree over a row of n values (a term that does not exist is +0.0):
@@ -109,9 +109,6 @@ R3D_STATS_HD inline bool misfit_observed_bad(double v) {
   const uint64_t mag = b & 0x7FFFFFFFFFFFFFFFull;
   return mag >= 0x7FF0000000000000ull || ((b >> 63) != 0 && mag != 0);
 }
-
-// a of a value of t or t_(j).
-R3D_STATS_HD inline double misfit_amplitude(double t, uint32_t amplitude) { return amplitude ? sqrt(t) : t; }
 
 // The terms of Suu / Soo, of X_L (uk = u[k]; o the whole observed row), of R and of dpk.
 R3D_STATS_HD inline double misfit_square_term(double v) {
@@ -243,30 +240,14 @@ template <int G>
 inline void envelope_misfit(const MisfitProblem& a, double* misfit, double* misfit_se, double* xcorr, double* xcorr_se,
                             double* envelope, uint32_t* lit, uint64_t* bad, uint64_t* bad_observed) {
   const uint32_t B = a.n_batches, nb = a.n_bins, A = a.last - a.first + 1, n_lags = 2 * a.max_lag + 1, nv = kMisfitN + n_lags;
-  const uint64_t block = (uint64_t)a.n_seismometers * nb * kWindowComponents;
   const uint32_t rows = B >= 2 ? B + 1 : 1;            // t_(0) .. t_(B-1), then t
-  std::vector<double> U((size_t)rows * nb), V((size_t)rows * nb), O(nb), O2(nb), tmp(nb), L(B), e(B), val((size_t)rows * nv);
+  std::vector<double> U((size_t)rows * nb), V((size_t)rows * nb), O(nb), O2(nb), tmp(nb), val((size_t)rows * nv);
   uint64_t n_bad = 0, n_bad_observed = 0;
   for (uint32_t i = 0; i < A; i++) {
-    uint32_t b0 = a.bins[2 * i], b1 = a.bins[2 * i + 1];
-    if (!envelope_window_ok(b0, b1, nb)) n_bad++, b0 = b1 = 0;
+    uint32_t b0, b1;
+    const double* const cur = envelope_rows_host(a.x, B, a.n_seismometers, nb, a.first + i, a.weight, a.bins + 2 * (size_t)i,
+                                                 a.amplitude, a.smooth_syn, rows, U.data(), V.data(), &b0, &b1, &n_bad);
     const uint32_t n = b1 - b0;
-    const uint64_t seis = ((uint64_t)a.first + i) * nb * kWindowComponents;
-    double* cur = U.data();
-    double* next = V.data();
-    for (uint32_t k = 0; k < n; k++) {
-      for (uint32_t j = 0; j < B; j++)
-        e[j] = window_bin_energy(a.x + j * block + seis + ((uint64_t)b0 + k) * kWindowComponents, a.weight);
-      cur[(size_t)(rows - 1) * nb + k] = misfit_amplitude(array_leave_one_out(e.data(), L.data(), 1, B), a.amplitude);
-      if (B >= 2)
-        for (uint32_t j = 0; j < B; j++) cur[(size_t)j * nb + k] = misfit_amplitude(e[j], a.amplitude);
-    }
-    for (uint32_t pass = 0; pass < a.smooth_syn; pass++) {
-      for (uint32_t r = 0; r < rows; r++)
-        for (uint32_t k = 0; k < n; k++) next[(size_t)r * nb + k] = envelope_smooth_at(cur + (size_t)r * nb, n, k);
-      double* const swap = cur;
-      cur = next, next = swap;
-    }
     double* o = O.data();
     double* o_next = O2.data();
     bool observed_bad = false;

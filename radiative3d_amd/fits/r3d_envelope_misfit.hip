@@ -8,9 +8,9 @@
 // This file stands ON TOP of the engine and of the stats add-on's C-ABI: it calls only what include/r3d.h declares.
 //
 // WHERE THE ROWS ARE KEPT.  The rows of one receiver -- the total, for an se the B leave-one-out rows, and the observed
-// row -- are built and smoothed in DEVICE SCRATCH exactly as r3d_envelope_shape.hip does it (two copies per workgroup, one
-// barrier per pass; one path for every window length).  THE LAG SCAN, (rows) x (2 Lmax + 1) row reductions per receiver, is
-// the hot part: up to 65 x 129 sums of n products.  For it the observed row and ONE synthetic row per wave lie in LDS
+// row -- are built and smoothed in DEVICE SCRATCH by the code the envelope shape runs, ../shapes/r3d_envelope_rows.h (two
+// copies per workgroup, one barrier per pass; one path for every window length; r3d_envelope_shape.hip prices it).  THE
+// LAG SCAN, (rows) x (2 Lmax + 1) row reductions per receiver, is the hot part: up to 65 x 129 sums of n products.  For it the observed row and ONE synthetic row per wave lie in LDS
 // (five rows of kFitLdsBins doubles, in the space the scan's tile used before), lane l on the bins l, l + 64, ...: a lane
 // IS strand l of every X_L, reads its own u[k] and the neighbouring o[k + L] (consecutive lanes, consecutive doubles: no
 // bank conflict), and forms kFitLagTile lags at once from one read of u[k] -- four independent sums in flight, whose four
@@ -18,7 +18,6 @@
 // window longer than kFitLdsBins reads the same rows from the scratch instead (L1 / L2): the same operations, slower.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -29,16 +28,11 @@
 namespace r3d {
 namespace {
 
-constexpr int kFitBlock = 256;                         // four waves: wave w serves the rows w, w + 4, ...
-constexpr int kFitWaves = kFitBlock / 64;
-constexpr int kFitRows = kEnvelopeMaxBatches + 1;      // t_(0) .. t_(B-1) at their j, t at B
-constexpr int kFitOwnRows = (kFitRows + kFitWaves - 1) / kFitWaves;
-constexpr uint32_t kFitMaxGroups = 512;                // workgroups of one launch (and sets of scratch rows)
 constexpr uint32_t kFitLdsBins = 1600;                 // the longest window whose rows the lag scan keeps in LDS
 constexpr int kFitLagTile = 4;                         // lags formed at once, and reduced by ONE tree (fit_tree4)
 constexpr uint32_t kFitValues = kMisfitN + kMisfitMaxLags;   // a row's six numbers and its curve, in the scratch
-constexpr uint32_t kFitTileDoubles = (kFitRows + kEnvelopeMaxBatches) * 64;   // the scan's tile: T [65][64], L [64][64]
-static_assert((kFitWaves + 1) * kFitLdsBins <= kFitTileDoubles, "the lag scan's rows live where the scan's tile was");
+constexpr uint32_t kFitTileDoubles = (kRowsMax + kEnvelopeMaxBatches) * 64;   // the scan's tile: T [65][64], L [64][64]
+static_assert((kRowsWaves + 1) * kFitLdsBins <= kFitTileDoubles, "the lag scan's rows live where the scan's tile was");
 static_assert(kFitLagTile == 4, "fit_tree4 takes the trees of four sums");
 
 struct FitArgs {
@@ -57,16 +51,7 @@ struct FitArgs {
   double w[kWindowComponents];
 };
 
-// The tree's six levels of a sum across the lanes: lane l takes lane l + h's, for l < h; lane 0 holds the row sum.
-__device__ inline double fit_tree(double s) {
-#pragma unroll
-  for (int h = 32; h >= 1; h /= 2) s = s + __shfl_down(s, h, 64);
-  return s;
-}
-// ... and that sum in every lane.
-__device__ inline double fit_rowsum(double s) { return __shfl(fit_tree(s), 0, 64); }
-
-// The trees of FOUR row sums at once, in 6 exchanges where four trees take 24: the tree's level h only ever adds lane l + h's
+// wave_sum's trees of FOUR row sums at once, in 6 exchanges where four trees take 24: level h only ever adds lane l + h's
 // value to lane l's for l < h, so the lanes at and above h are free to do the same level for ANOTHER sum.  At h = 32 the
 // lower half of the wave folds p0 (and p2) while the upper half folds p1 (and p3) -- each lane hands its partner l ^ 32 the
 // value the partner's sum needs --, at h = 16 the lanes with bit 4 clear fold the first pair and those with it set the
@@ -98,19 +83,9 @@ __device__ inline double fit_lane(double v, int lane) {
   return v;
 }
 
-// rowmax across the lanes, in every lane.  None of the six numbers needs the bin that holds it, so the merge is on the
-// value alone: the value array_max_merge leaves.
-__device__ inline double fit_rowmax(double m) {
-#pragma unroll
-  for (int h = 32; h >= 1; h /= 2) {
-    const double m2 = __shfl_down(m, h, 64);
-    if (m2 > m) m = m2;
-  }
-  return __shfl(m, 0, 64);
-}
-
 // One wave makes the six numbers and the curve of the row u against o (both of n values, in LDS or in the scratch) and
-// lane 0 leaves them in val[0 .. 6 + n_lags).  Every branch here is taken by the whole wave or by none of it.
+// lane 0 leaves them in val[0 .. 6 + n_lags).  Every branch here is taken by the whole wave or by none of it.  (None of
+// the six numbers needs the bin that holds a maximum: wave_max_all, on the value alone.)
 __device__ __forceinline__ void fit_row(const double* u, const double* o, uint32_t n, uint32_t max_lag, const MisfitObserved ob,
                                         uint32_t l, double* val) {
   R3D_STATS_NO_CONTRACT
@@ -122,8 +97,8 @@ __device__ __forceinline__ void fit_row(const double* u, const double* o, uint32
     suu += misfit_square_term(v), eu += v, m1 += envelope_m1_term(k, v);
     array_max_take(&top, &top_at, v, k);
   }
-  suu = fit_rowsum(suu), eu = fit_rowsum(eu), m1 = fit_rowsum(m1);
-  const double P = fit_rowmax(top);
+  suu = wave_sum_all(suu), eu = wave_sum_all(eu), m1 = wave_sum_all(m1);
+  const double P = wave_max_all(top);
   if (ob.dead || !(P > 0.0)) {
     if (l == 0) misfit_dead_row(val, val + kMisfitN, n_lags);
     return;
@@ -160,27 +135,27 @@ __device__ __forceinline__ void fit_row(const double* u, const double* o, uint32
     const double uk = u[k], ok = o[k];
     R += misfit_residual_term(uk, ok, s), D += misfit_peak_term(uk, P, ok, ob.Po);
   }
-  R = fit_tree(R), D = fit_tree(D);
+  R = wave_sum(R), D = wave_sum(D);
   if (l == 0) misfit_six(ob, suu, eu, m1, X0, s, R, D, n, lag, val);
 }
 
 // One workgroup per receiver of the array at a time (receivers i, i + groups, ...), lane l of every wave on the window's bins
 // l, l + 64, ...
-//   1. The observed window into the scratch (its bad values flagged by their bits); then, a tile of 64 window bins at a time,
-//      the batches' e_j into LDS, wave 0 scans every bin's column into t and the t_(j), and the waves copy their rows -- or
-//      the roots of them -- into the scratch.  Every bin of the window is read from HBM once.
-//   2. The passes: a wave smooths its rows, and wave 0 the observed row, from one copy of the scratch into the other.
+//   1. The observed window into the scratch (its bad values flagged by their bits); then the rows -- or the roots of them
+//      -- into the scratch, a tile of 64 window bins at a time (../shapes/r3d_envelope_rows.h rows_build_tile).
+//   2. The passes: a wave smooths its rows (rows_smooth_pass), and wave 0 the observed row, from one copy of the scratch
+//      into the other, under one barrier.
 //   3. Wave 0 reduces the observed row; all copy it into LDS where it fits; then a wave makes the six numbers and the curve
 //      of each of its rows (fit_row), its row copied into its own LDS slot first where it fits.
 //   4. Work-items 0 .. 6 + n_lags write the total row's values and take the jackknife of theirs over the leave-one-out rows;
 //      all write the receiver's envelope row.
 // Every output has one writer; no update of memory shared between workgroups; fixed order; 64-bit offsets.
-__global__ __launch_bounds__(kFitBlock) void envelope_misfit_kernel(const FitArgs a) {
+__global__ __launch_bounds__(kRowsBlock) void envelope_misfit_kernel(const FitArgs a) {
   R3D_STATS_NO_CONTRACT
   __shared__ double BUF[kFitTileDoubles];
   __shared__ double OB[4];
-  double(*const T)[64] = reinterpret_cast<double(*)[64]>(BUF);                     // [kFitRows][64]
-  double(*const Lsum)[64] = reinterpret_cast<double(*)[64]>(BUF + kFitRows * 64);  // [kEnvelopeMaxBatches][64]
+  double(*const T)[64] = reinterpret_cast<double(*)[64]>(BUF);                     // [kRowsMax][64]
+  double(*const Lsum)[64] = reinterpret_cast<double(*)[64]>(BUF + kRowsMax * 64);  // [kEnvelopeMaxBatches][64]
   const uint32_t w = threadIdx.x / 64, l = threadIdx.x % 64, B = a.n_batches, nb = a.n_bins;
   const bool loo = a.rows > 1;                                     // (without an se only the total row is needed)
   const uint32_t n_lags = 2 * a.max_lag + 1, obs_slot = a.rows;
@@ -192,55 +167,27 @@ __global__ __launch_bounds__(kFitBlock) void envelope_misfit_kernel(const FitArg
 
   for (uint32_t i = blockIdx.x; i < a.n_array; i += gridDim.x) {
     uint32_t b0 = a.bins[2 * (uint64_t)i], b1 = a.bins[2 * (uint64_t)i + 1];
-    if (!envelope_window_ok(b0, b1, nb)) b0 = b1 = 0;              // (never read through: dead; misfit_count_kernel counts it)
+    if (!envelope_window_ok(b0, b1, nb)) b0 = b1 = 0;              // (never read through: dead; envelope_count_kernel counts it)
     const uint32_t n = b1 - b0;
     const double* const trace = a.x + ((uint64_t)a.first + i) * nb * kWindowComponents;
 
     // 1. the observed window, and the rows tile by tile
     int bad_here = 0;
-    for (uint32_t k = threadIdx.x; k < n; k += kFitBlock) {
+    for (uint32_t k = threadIdx.x; k < n; k += kRowsBlock) {
       const double v = a.observed[(uint64_t)i * nb + b0 + k];
       bad_here |= misfit_observed_bad(v);
       mine[(uint64_t)obs_slot * nb + k] = v;
     }
     const bool observed_bad = __syncthreads_or(bad_here) != 0;
     if (threadIdx.x == 0) a.flags[i] = observed_bad;
-    for (uint32_t base = 0; base < n; base += 64) {
-      const uint32_t k = base + l;
-      const bool in = k < n;
-#pragma unroll
-      for (int o = 0; o < kFitOwnRows; o++) {
-        const uint32_t j = w + kFitWaves * o;
-        if (j < B) T[j][l] = in ? window_bin_energy(trace + j * block + ((uint64_t)b0 + k) * kWindowComponents, a.w) : 0.0;
-      }
-      __syncthreads();
-      if (w == 0) {
-        const double t = array_leave_one_out(&T[0][l], &Lsum[0][l], 64, B);
-        T[B][l] = t;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int o = 0; o < kFitOwnRows; o++) {
-        const uint32_t r = w + kFitWaves * o;
-        if (in && (r == B || (loo && r < B))) mine[(uint64_t)(loo ? r : 0) * nb + k] = misfit_amplitude(T[r][l], a.amplitude);
-      }
-      __syncthreads();
-    }
+    for (uint32_t base = 0; base < n; base += 64)
+      rows_build_tile(T, Lsum, mine, nb, a.amplitude, trace, block, a.w, B, loo, b0, n, base);
 
     // 2. the passes
     for (uint32_t pass = 0; pass < passes; pass++) {
       const double* const src = mine + (pass & 1) * copy;
       double* const dst = mine + ((pass + 1) & 1) * copy;
-      if (pass < a.smooth_syn) {
-#pragma unroll 1
-        for (int o = 0; o < kFitOwnRows; o++) {
-          const uint32_t r = w + kFitWaves * o;
-          if (r == B || (loo && r < B)) {
-            const uint64_t at = (uint64_t)(loo ? r : 0) * nb;
-            for (uint32_t k = l; k < n; k += 64) dst[at + k] = envelope_smooth_at(src + at, n, k);
-          }
-        }
-      }
+      if (pass < a.smooth_syn) rows_smooth_pass(src, dst, nb, n, B, loo);
       if (pass < a.smooth_obs && w == 0) {
         const uint64_t at = (uint64_t)obs_slot * nb;
         for (uint32_t k = l; k < n; k += 64) dst[at + k] = envelope_smooth_at(src + at, n, k);
@@ -260,20 +207,20 @@ __global__ __launch_bounds__(kFitBlock) void envelope_misfit_kernel(const FitArg
         soo += misfit_square_term(v), eo += v, m1 += envelope_m1_term(k, v);
         array_max_take(&top, &top_at, v, k);
       }
-      soo = fit_tree(soo), eo = fit_tree(eo), m1 = fit_tree(m1), top = fit_rowmax(top);
+      soo = wave_sum(soo), eo = wave_sum(eo), m1 = wave_sum(m1), top = wave_max_all(top);
       if (l == 0) OB[0] = soo, OB[1] = top, OB[2] = m1, OB[3] = eo;
     }
     if (in_lds)
-      for (uint32_t k = threadIdx.x; k < n; k += kFitBlock) BUF[k] = obs[k];       // (the tile is done with: step 1's last barrier)
+      for (uint32_t k = threadIdx.x; k < n; k += kRowsBlock) BUF[k] = obs[k];      // (the tile is done with: step 1's last barrier)
     __syncthreads();
     MisfitObserved ob;
     ob.Soo = OB[0], ob.Po = OB[1], ob.M1o = OB[2], ob.Eo = OB[3];
     ob.dead = misfit_receiver_dead(n, observed_bad, ob.Po);
 #pragma unroll 1
-    for (int o = 0; o < kFitOwnRows; o++) {
-      const uint32_t r = w + kFitWaves * o;
-      if (!(r == B || (loo && r < B))) continue;
-      const uint32_t slot = loo ? r : 0;
+    for (int o = 0; o < kRowsOwn; o++) {
+      const uint32_t r = w + kRowsWaves * o;
+      if (!rows_made(r, B, loo)) continue;
+      const uint32_t slot = rows_slot(r, loo);
       const double* const u = rows + (uint64_t)slot * nb;
       double* const val = values + (uint64_t)slot * kFitValues;
       if (in_lds) {
@@ -287,8 +234,8 @@ __global__ __launch_bounds__(kFitBlock) void envelope_misfit_kernel(const FitArg
     __syncthreads();
 
     // 4. what is written
-    const double* const total = values + (uint64_t)(loo ? B : 0) * kFitValues;
-    for (uint32_t q = threadIdx.x; q < kMisfitN + n_lags; q += kFitBlock) {
+    const double* const total = values + (uint64_t)rows_slot(B, loo) * kFitValues;
+    for (uint32_t q = threadIdx.x; q < kMisfitN + n_lags; q += kRowsBlock) {
       const bool six = q < kMisfitN;
       double* const out = six ? a.misfit : a.xcorr;
       double* const out_se = six ? a.misfit_se : a.xcorr_se;
@@ -303,48 +250,15 @@ __global__ __launch_bounds__(kFitBlock) void envelope_misfit_kernel(const FitArg
       if (a.lit) a.lit[i] = (lag_bits & 0x7FFFFFFFFFFFFFFFull) <= 0x7FF0000000000000ull;   // (a living row's lag is a number)
     }
     if (a.envelope)
-      for (uint32_t b = threadIdx.x; b < nb; b += kFitBlock)
-        a.envelope[(uint64_t)i * nb + b] = b >= b0 && b < b1 ? rows[(uint64_t)(loo ? B : 0) * nb + (b - b0)] : 0.0;
+      for (uint32_t b = threadIdx.x; b < nb; b += kRowsBlock)
+        a.envelope[(uint64_t)i * nb + b] = b >= b0 && b < b1 ? rows[(uint64_t)rows_slot(B, loo) * nb + (b - b0)] : 0.0;
     __syncthreads();                                               // (the LDS and the scratch are the next receiver's now)
-  }
-}
-
-// The windows that are not b0 <= b1 <= n_bins and the receivers flagged for a bad observed value, counted by ONE workgroup
-// and written by one work-item each.
-__global__ __launch_bounds__(kFitBlock) void misfit_count_kernel(const uint32_t* __restrict__ bins, const uint32_t* __restrict__ flags,
-                                                                uint32_t n_array, uint32_t n_bins, uint64_t* __restrict__ bad,
-                                                                uint64_t* __restrict__ bad_observed) {
-  __shared__ unsigned long long part[2][kFitWaves];
-  unsigned long long n = 0, m = 0;
-  for (uint32_t i = threadIdx.x; i < n_array; i += kFitBlock) {
-    n += !envelope_window_ok(bins[2 * (uint64_t)i], bins[2 * (uint64_t)i + 1], n_bins);
-    m += flags[i] != 0;
-  }
-#pragma unroll
-  for (int h = 32; h >= 1; h /= 2) n += __shfl_down(n, h, 64), m += __shfl_down(m, h, 64);
-  if (threadIdx.x % 64 == 0) part[0][threadIdx.x / 64] = n, part[1][threadIdx.x / 64] = m;
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    unsigned long long total = 0;
-    for (int k = 0; k < kFitWaves; k++) total += part[threadIdx.x][k];
-    uint64_t* const out = threadIdx.x == 0 ? bad : bad_observed;
-    if (out) *out = total;
   }
 }
 
 // What both calls refuse on the spec alone (0: nothing; else the message is set).
 int check_misfit_spec(const char* who, const r3d_misfit_spec* a) {
-  if (!a) return refuse(who, "null misfit spec");
-  if (a->size != sizeof(r3d_misfit_spec))
-    return refuse(who, "r3d_misfit_spec.size is " + std::to_string(a->size) + ", this library's is " +
-                           std::to_string(sizeof(r3d_misfit_spec)));
-  if (a->n_bins == 0) return refuse(who, "n_bins must be at least 1");
-  if (a->last < a->first || a->last >= a->n_seismometers)
-    return refuse(who, "the array " + std::to_string(a->first) + " .. " + std::to_string(a->last) + " is not within the " +
-                           std::to_string(a->n_seismometers) + " seismometers");
-  for (int k = 0; k < R3D_N_ENERGY; k++)
-    if (!std::isfinite(a->weight[k]) || a->weight[k] < 0.0)
-      return refuse(who, "weight " + std::to_string(k) + " is negative or not finite (the rounding bounds need non-negative terms)");
+  if (check_receiver_array_spec(who, a, "misfit", "r3d_misfit_spec", "the rounding bounds need non-negative terms")) return 1;
   if (a->smooth_syn > R3D_ENVELOPE_MAX_SMOOTH || a->smooth_obs > R3D_ENVELOPE_MAX_SMOOTH)
     return refuse(who, "at most R3D_ENVELOPE_MAX_SMOOTH (64) smoothing passes, got " + std::to_string(a->smooth_syn) + " and " +
                            std::to_string(a->smooth_obs));
@@ -360,28 +274,23 @@ int enqueue_envelope_misfit(const char* who, uint32_t n_batches, const double* d
                             const uint32_t* d_bins, const double* d_observed, double* d_misfit, double* d_misfit_se,
                             double* d_xcorr, double* d_xcorr_se, double* d_envelope, uint32_t* d_lit, uint64_t* d_bad,
                             uint64_t* d_bad_observed, hipStream_t s) {
+  RowsLaunch go(n_batches, d_misfit_se || d_xcorr_se, spec->last - spec->first + 1);
   FitArgs a;
   a.x = d_batch_energy, a.bins = d_bins, a.observed = d_observed, a.misfit = d_misfit, a.misfit_se = d_misfit_se;
   a.xcorr = d_xcorr, a.xcorr_se = d_xcorr_se, a.envelope = d_envelope, a.lit = d_lit;
   a.n_batches = n_batches, a.n_seis = spec->n_seismometers, a.n_bins = spec->n_bins, a.first = spec->first;
   a.n_array = spec->last - spec->first + 1, a.smooth_syn = spec->smooth_syn, a.smooth_obs = spec->smooth_obs;
-  a.max_lag = spec->max_lag, a.amplitude = spec->amplitude;
-  a.rows = n_batches >= 2 && (d_misfit_se || d_xcorr_se) ? n_batches + 1 : 1;
+  a.max_lag = spec->max_lag, a.amplitude = spec->amplitude, a.rows = go.rows;
   for (int k = 0; k < kWindowComponents; k++) a.w[k] = spec->weight[k];
-  const uint32_t groups = a.n_array < kFitMaxGroups ? a.n_array : kFitMaxGroups;
   const size_t per_group = 2 * ((size_t)a.rows + 1) * a.n_bins + (size_t)a.rows * kFitValues;
   const size_t flag_words = ((size_t)a.n_array + 1) / 2;
-  void* scratch = nullptr;
-  if (hipError_t err = hipMallocAsync(&scratch, ((size_t)groups * per_group + flag_words) * sizeof(double), s); err != hipSuccess)
-    return refuse(who, err, "scratch for the rows");
-  a.scratch = static_cast<double*>(scratch);
-  a.flags = reinterpret_cast<uint32_t*>(a.scratch + (size_t)groups * per_group);
-  envelope_misfit_kernel<<<dim3(groups), dim3(kFitBlock), 0, s>>>(a);
+  if (go.take(who, (size_t)go.groups * per_group + flag_words, s)) return 1;
+  a.scratch = static_cast<double*>(go.scratch);
+  a.flags = reinterpret_cast<uint32_t*>(a.scratch + (size_t)go.groups * per_group);
+  envelope_misfit_kernel<<<dim3(go.groups), dim3(kRowsBlock), 0, s>>>(a);
   if (d_bad || d_bad_observed)
-    misfit_count_kernel<<<dim3(1), dim3(kFitBlock), 0, s>>>(d_bins, a.flags, a.n_array, a.n_bins, d_bad, d_bad_observed);
-  hipError_t err = hipGetLastError();
-  if (hipError_t f = hipFreeAsync(scratch, s); f != hipSuccess && err == hipSuccess) err = f;
-  return err == hipSuccess ? 0 : refuse(who, err);
+    envelope_count_kernel<<<dim3(1), dim3(kRowsBlock), 0, s>>>(d_bins, a.flags, a.n_array, a.n_bins, d_bad, d_bad_observed);
+  return go.give(who, s);
 }
 
 }  // namespace

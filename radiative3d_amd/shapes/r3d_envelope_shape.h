@@ -13,7 +13,8 @@
 //
 // ROWS.  Per window bin k, e_j = window_bin_energy(x_j[s][b0 + k], w) (../stats/r3d_window_sums.h), and
 // array_leave_one_out (../arrays/r3d_array_image.h) gives the total t[k] and, for B >= 2, the B rows t_(j)[k] = (L_j + R_j)
-// B / (B - 1) without batch j -- never t - e_j.
+// B / (B - 1) without batch j -- never t - e_j.  The rows and their passes are made by r3d_envelope_rows.h, for this add-on
+// and for ../fits/ alike.
 //
 // SMOOTHING (the reference's three-point rule, restated).  One pass S over a row v of n values, made from the WHOLE
 // previous row:
@@ -82,10 +83,10 @@
 
 #include "../arrays/r3d_array_image.h"
 #include "../stats/r3d_window_sums.h"
+#include "r3d_envelope_rows.h"
 
 namespace r3d {
 
-constexpr uint32_t kEnvelopeMaxBatches = 64;
 constexpr uint32_t kEnvelopeMaxSmooth = 64;   // (include/r3d.h R3D_ENVELOPE_MAX_SMOOTH)
 constexpr uint32_t kEnvelopeNShape = 6;       // (include/r3d.h R3D_ENVELOPE_N_SHAPE)
 constexpr int kEnvelopeE = 0, kEnvelopeP = 1, kEnvelopePeakTime = 2, kEnvelopeHalfTime = 3, kEnvelopeCentroid = 4,
@@ -100,18 +101,6 @@ R3D_STATS_HD inline double envelope_canon(double v) {
   if ((b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) b = 0x7FF8000000000000ull;   // (double)NAN
   __builtin_memcpy(&v, &b, sizeof b);
   return v;
-}
-
-// A window the blocks hold: 0 <= b0 <= b1 <= n_bins.
-R3D_STATS_HD inline bool envelope_window_ok(uint32_t b0, uint32_t b1, uint32_t n_bins) { return b0 <= b1 && b1 <= n_bins; }
-
-// S(v)[k] of the row v[0 .. n), k < n.
-R3D_STATS_HD inline double envelope_smooth_at(const double* v, uint32_t n, uint32_t k) {
-  R3D_STATS_NO_CONTRACT
-  if (n < 2) return v[k];
-  if (k == 0) return 0.75 * v[0] + 0.25 * v[1];
-  if (k == n - 1) return 0.75 * v[n - 1] + 0.25 * v[n - 2];
-  return (0.25 * v[k - 1] + 0.5 * v[k]) + 0.25 * v[k + 1];
 }
 
 // tp of the row u[0 .. n) whose maximum P > 0 is first held by bin kp.
@@ -199,30 +188,14 @@ template <int G>
 inline void envelope_shape(const EnvelopeProblem& a, double* shape, double* shape_se, double* envelope, double* envelope_se,
                            uint32_t* peak_bin, uint32_t* half_bin, uint32_t* lit, uint64_t* bad) {
   const uint32_t B = a.n_batches, nb = a.n_bins, A = a.last - a.first + 1;
-  const uint64_t block = (uint64_t)a.n_seismometers * nb * kWindowComponents;
   const uint32_t rows = B >= 2 ? B + 1 : 1;            // t_(0) .. t_(B-1), then t
-  std::vector<double> U((size_t)rows * nb), V((size_t)rows * nb), tmp(nb), L(B), e(B), six((size_t)rows * 6), v(B);
+  std::vector<double> U((size_t)rows * nb), V((size_t)rows * nb), tmp(nb), six((size_t)rows * 6), v(B);
   uint64_t n_bad = 0;
   for (uint32_t i = 0; i < A; i++) {
-    uint32_t b0 = a.bins[2 * i], b1 = a.bins[2 * i + 1];
-    if (!envelope_window_ok(b0, b1, nb)) n_bad++, b0 = b1 = 0;
+    uint32_t b0, b1;
+    const double* const cur = envelope_rows_host(a.x, B, a.n_seismometers, nb, a.first + i, a.weight, a.bins + 2 * (size_t)i, 0,
+                                                 a.smooth, rows, U.data(), V.data(), &b0, &b1, &n_bad);
     const uint32_t n = b1 - b0;
-    const uint64_t seis = ((uint64_t)a.first + i) * nb * kWindowComponents;
-    double* cur = U.data();
-    double* next = V.data();
-    for (uint32_t k = 0; k < n; k++) {
-      for (uint32_t j = 0; j < B; j++)
-        e[j] = window_bin_energy(a.x + j * block + seis + ((uint64_t)b0 + k) * kWindowComponents, a.weight);
-      cur[(size_t)(rows - 1) * nb + k] = array_leave_one_out(e.data(), L.data(), 1, B);
-      if (B >= 2)
-        for (uint32_t j = 0; j < B; j++) cur[(size_t)j * nb + k] = e[j];
-    }
-    for (uint32_t pass = 0; pass < a.smooth; pass++) {
-      for (uint32_t r = 0; r < rows; r++)
-        for (uint32_t k = 0; k < n; k++) next[(size_t)r * nb + k] = envelope_smooth_at(cur + (size_t)r * nb, n, k);
-      double* const swap = cur;
-      cur = next, next = swap;
-    }
     uint32_t kp = kEnvelopeNoBin, kq = kEnvelopeNoBin, kpj, kqj;
     for (uint32_t r = 0; r < rows; r++)
       envelope_row_shape<G>(cur + (size_t)r * nb, n, &six[(size_t)r * 6], r == rows - 1 ? &kp : &kpj, r == rows - 1 ? &kq : &kqj,

@@ -6,11 +6,12 @@
 //
 // This file stands ON TOP of the engine and of the stats add-on's C-ABI: it calls only what include/r3d.h declares.
 //
-// HOW THE m PASSES ARE STAGED, and what that costs.  The rows of one receiver -- the total and, for an se, the B
-// leave-one-out rows, up to 65 rows of n doubles -- go through DEVICE SCRATCH throughout: two copies per workgroup, read
-// and written alternately, one barrier per pass.  One path serves every window length up to n_bins; nothing depends on
-// what fits on chip (65 rows of the workloads' 400 to 3000 bins are 0.2 to 1.6 MB, beyond the 160 KB of LDS in any case;
-// only the 64-bin tile in which the batches' columns are scanned lives there).  The price: every pass moves 16 bytes per
+// HOW THE m PASSES ARE STAGED (by r3d_envelope_rows.h, for this kernel and the envelope misfit's alike), and what that
+// costs.  The rows of one receiver -- the total and, for an se, the B leave-one-out rows, up to 65 rows of n doubles --
+// go through DEVICE SCRATCH throughout: two copies per workgroup, read and written alternately, one barrier per pass.
+// One path serves every window length up to n_bins; nothing depends on what fits on chip (65 rows of the workloads' 400
+// to 3000 bins are 0.2 to 1.6 MB, beyond the 160 KB of LDS in any case; only the 64-bin tile in which the batches'
+// columns are scanned lives there).  The price: every pass moves 16 bytes per
 // row value through L2 instead of LDS -- per receiver 2 m rows n 8 bytes, with B = 16, n = 400, m = 8 about 0.9 MB against
 // the 0.26 MB of blocks it reads from HBM once -- and the scratch itself, min(A, 512) x 2 x rows x n_bins doubles, taken
 // from and given back to the stream's pool around the launch.  A row is owned by one wave from the scan to its six
@@ -18,7 +19,6 @@
 // traffic by the number of passes fused per tile and pay for it with m halo bins on either side of every tile, redone.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -28,12 +28,6 @@
 
 namespace r3d {
 namespace {
-
-constexpr int kShapeBlock = 256;                       // four waves: wave w serves the rows w, w + 4, ...
-constexpr int kShapeWaves = kShapeBlock / 64;
-constexpr int kShapeRows = kEnvelopeMaxBatches + 1;    // t_(0) .. t_(B-1) at their j, t at B
-constexpr int kShapeOwnRows = (kShapeRows + kShapeWaves - 1) / kShapeWaves;
-constexpr uint32_t kShapeMaxGroups = 512;              // workgroups of one launch (and sets of scratch rows)
 
 struct ShapeArgs {
   const double* x;         // [B][n_seis][n_bins][5]
@@ -50,30 +44,21 @@ struct ShapeArgs {
   double w[kWindowComponents];
 };
 
-// The tree's six levels of a sum across the lanes: lane l takes lane l + h's, for l < h (what the lanes above hold is not
-// used); lane 0 holds the row sum.
-__device__ inline double shape_tree(double s) {
-#pragma unroll
-  for (int h = 32; h >= 1; h /= 2) s = s + __shfl_down(s, h, 64);
-  return s;
-}
-
 // One workgroup per receiver of the array at a time (receivers i, i + groups, ...), lane l of every wave on the window's bins
 // l, l + 64, ...: a lane IS strand l of every row sum.
-//   1. A tile of 64 window bins at a time: the four waves put the batches' e_j into LDS (wave w the batches w, w + 4, ...;
-//      the lanes of a wave read 64 consecutive bins of one block), wave 0 scans every bin's column into t and the t_(j),
-//      and the waves copy their rows into the workgroup's scratch.  Every bin of the window is read from HBM once.
-//   2. m passes: a wave smooths its rows from one copy of the scratch into the other; a barrier between passes.
+//   1. The rows into the workgroup's scratch, a tile of 64 window bins at a time (r3d_envelope_rows.h rows_build_tile).
+//   2. m passes: a wave smooths its rows from one copy of the scratch into the other (rows_smooth_pass); a barrier between
+//      passes.
 //   3. A wave makes the six numbers of each of its rows (two sweeps over the row: E, P, kp, kq and M1, then M2 about c)
 //      and leaves them in LDS.
 //   4. Work-items 0 .. 5 write the total row's numbers and take the jackknife of theirs over the leave-one-out rows; all
 //      write the receiver's envelope row and its jackknife, bin by bin.
 // Every output has one writer; no atomics; fixed order; 64-bit offsets.
-__global__ __launch_bounds__(kShapeBlock) void envelope_shape_kernel(const ShapeArgs a) {
+__global__ __launch_bounds__(kRowsBlock) void envelope_shape_kernel(const ShapeArgs a) {
   R3D_STATS_NO_CONTRACT
-  __shared__ double T[kShapeRows][64];
+  __shared__ double T[kRowsMax][64];
   __shared__ double L[kEnvelopeMaxBatches][64];
-  __shared__ double SIX[kShapeRows][kEnvelopeNShape];
+  __shared__ double SIX[kRowsMax][kEnvelopeNShape];
   __shared__ uint32_t KP, KQ;
   const uint32_t w = threadIdx.x / 64, l = threadIdx.x % 64, B = a.n_batches, nb = a.n_bins;
   const bool loo = a.rows > 1;                                     // (without an se only the total row is needed)
@@ -83,55 +68,26 @@ __global__ __launch_bounds__(kShapeBlock) void envelope_shape_kernel(const Shape
 
   for (uint32_t i = blockIdx.x; i < a.n_array; i += gridDim.x) {
     uint32_t b0 = a.bins[2 * (uint64_t)i], b1 = a.bins[2 * (uint64_t)i + 1];
-    if (!envelope_window_ok(b0, b1, nb)) b0 = b1 = 0;              // (never read through: dead; shape_bad_kernel counts it)
+    if (!envelope_window_ok(b0, b1, nb)) b0 = b1 = 0;              // (never read through: dead; envelope_count_kernel counts it)
     const uint32_t n = b1 - b0;
     const double* const trace = a.x + ((uint64_t)a.first + i) * nb * kWindowComponents;
 
     // 1. the rows, tile by tile
-    for (uint32_t base = 0; base < n; base += 64) {
-      const uint32_t k = base + l;
-      const bool in = k < n;
-#pragma unroll
-      for (int o = 0; o < kShapeOwnRows; o++) {
-        const uint32_t j = w + kShapeWaves * o;
-        if (j < B) T[j][l] = in ? window_bin_energy(trace + j * block + ((uint64_t)b0 + k) * kWindowComponents, a.w) : 0.0;
-      }
-      __syncthreads();
-      if (w == 0) {
-        const double t = array_leave_one_out(&T[0][l], &L[0][l], 64, B);
-        T[B][l] = t;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int o = 0; o < kShapeOwnRows; o++) {
-        const uint32_t r = w + kShapeWaves * o;
-        if (in && (r == B || (loo && r < B))) mine[(uint64_t)(loo ? r : 0) * nb + k] = T[r][l];
-      }
-      __syncthreads();
-    }
+    for (uint32_t base = 0; base < n; base += 64) rows_build_tile(T, L, mine, nb, 0, trace, block, a.w, B, loo, b0, n, base);
 
     // 2. the passes
     for (uint32_t pass = 0; pass < a.smooth; pass++) {
-      const double* const src = mine + (pass & 1) * copy;
-      double* const dst = mine + ((pass + 1) & 1) * copy;
-#pragma unroll 1
-      for (int o = 0; o < kShapeOwnRows; o++) {
-        const uint32_t r = w + kShapeWaves * o;
-        if (r == B || (loo && r < B)) {
-          const uint64_t at = (uint64_t)(loo ? r : 0) * nb;
-          for (uint32_t k = l; k < n; k += 64) dst[at + k] = envelope_smooth_at(src + at, n, k);
-        }
-      }
+      rows_smooth_pass(mine + (pass & 1) * copy, mine + ((pass + 1) & 1) * copy, nb, n, B, loo);
       __syncthreads();
     }
     const double* const rows = mine + (a.smooth & 1) * copy;
 
     // 3. the six numbers, a wave for a row
 #pragma unroll 1
-    for (int o = 0; o < kShapeOwnRows; o++) {
-      const uint32_t r = w + kShapeWaves * o;
-      if (!(r == B || (loo && r < B))) continue;
-      const double* const u = rows + (uint64_t)(loo ? r : 0) * nb;
+    for (int o = 0; o < kRowsOwn; o++) {
+      const uint32_t r = w + kRowsWaves * o;
+      if (!rows_made(r, B, loo)) continue;
+      const double* const u = rows + (uint64_t)rows_slot(r, loo) * nb;
       double e = 0.0, m1 = 0.0, top = 0.0;
       uint32_t top_at = kArrayNoBin;
       for (uint32_t k = l; k < n; k += 64) {
@@ -139,15 +95,10 @@ __global__ __launch_bounds__(kShapeBlock) void envelope_shape_kernel(const Shape
         e += v, m1 += envelope_m1_term(k, v);
         array_max_take(&top, &top_at, v, k);
       }
-      e = shape_tree(e), m1 = shape_tree(m1);
-#pragma unroll
-      for (int h = 32; h >= 1; h /= 2) {
-        const double m2 = __shfl_down(top, h, 64);
-        const uint32_t at2 = __shfl_down(top_at, h, 64);
-        if (l < (uint32_t)h) array_max_merge(&top, &top_at, m2, at2);
-      }
-      const double P = __shfl(top, 0, 64);
-      const uint32_t kp = __shfl(top_at, 0, 64);
+      e = wave_sum(e), m1 = wave_sum(m1);
+      wave_argmax_all(&top, &top_at);
+      const double P = top;
+      const uint32_t kp = top_at;
       double six[kEnvelopeNShape];
       if (envelope_dead(P, six)) {                                 // (the whole wave takes this way, or none of it)
         if (l < kEnvelopeNShape) SIX[r][l] = six[l];
@@ -169,7 +120,7 @@ __global__ __launch_bounds__(kShapeBlock) void envelope_shape_kernel(const Shape
       c = __shfl(c, 0, 64);
       double m2 = 0.0;
       for (uint32_t k = l; k < n; k += 64) m2 += envelope_m2_term(k, c, u[k]);
-      m2 = shape_tree(m2);
+      m2 = wave_sum(m2);
       if (l == 0) {
         six[kEnvelopeWidth] = envelope_width(m2, e);
         for (uint32_t q = 0; q < kEnvelopeNShape; q++) SIX[r][q] = six[q];
@@ -190,45 +141,18 @@ __global__ __launch_bounds__(kShapeBlock) void envelope_shape_kernel(const Shape
       if (a.lit) a.lit[i] = KP != kEnvelopeNoBin;
     }
     if (a.envelope || a.envelope_se)
-      for (uint32_t b = threadIdx.x; b < nb; b += kShapeBlock) {
+      for (uint32_t b = threadIdx.x; b < nb; b += kRowsBlock) {
         const bool in = b >= b0 && b < b1;
-        if (a.envelope) a.envelope[(uint64_t)i * nb + b] = in ? rows[(uint64_t)(loo ? B : 0) * nb + (b - b0)] : 0.0;
+        if (a.envelope) a.envelope[(uint64_t)i * nb + b] = in ? rows[(uint64_t)rows_slot(B, loo) * nb + (b - b0)] : 0.0;
         if (a.envelope_se) a.envelope_se[(uint64_t)i * nb + b] = in ? envelope_canon(array_jackknife_se(rows + (b - b0), nb, B)) : 0.0;
       }
     __syncthreads();                                               // (SIX, KP, KQ and the scratch are the next receiver's now)
   }
 }
 
-// The windows that are not b0 <= b1 <= n_bins, counted by ONE workgroup and written by one work-item.
-__global__ __launch_bounds__(kShapeBlock) void shape_bad_kernel(const uint32_t* __restrict__ bins, uint32_t n_array,
-                                                               uint32_t n_bins, uint64_t* __restrict__ bad) {
-  __shared__ unsigned long long part[kShapeWaves];
-  unsigned long long n = 0;
-  for (uint32_t i = threadIdx.x; i < n_array; i += kShapeBlock) n += !envelope_window_ok(bins[2 * (uint64_t)i], bins[2 * (uint64_t)i + 1], n_bins);
-#pragma unroll
-  for (int h = 32; h >= 1; h /= 2) n += __shfl_down(n, h, 64);
-  if (threadIdx.x % 64 == 0) part[threadIdx.x / 64] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long total = 0;
-    for (int k = 0; k < kShapeWaves; k++) total += part[k];
-    *bad = total;
-  }
-}
-
 // What both calls refuse on the spec alone (0: nothing; else the message is set).
 int check_envelope_spec(const char* who, const r3d_envelope_spec* a) {
-  if (!a) return refuse(who, "null envelope spec");
-  if (a->size != sizeof(r3d_envelope_spec))
-    return refuse(who, "r3d_envelope_spec.size is " + std::to_string(a->size) + ", this library's is " +
-                           std::to_string(sizeof(r3d_envelope_spec)));
-  if (a->n_bins == 0) return refuse(who, "n_bins must be at least 1");
-  if (a->last < a->first || a->last >= a->n_seismometers)
-    return refuse(who, "the array " + std::to_string(a->first) + " .. " + std::to_string(a->last) + " is not within the " +
-                           std::to_string(a->n_seismometers) + " seismometers");
-  for (int k = 0; k < R3D_N_ENERGY; k++)
-    if (!std::isfinite(a->weight[k]) || a->weight[k] < 0.0)
-      return refuse(who, "weight " + std::to_string(k) + " is negative or not finite (the rounding bounds need non-negative terms)");
+  if (check_receiver_array_spec(who, a, "envelope", "r3d_envelope_spec", "the rounding bounds need non-negative terms")) return 1;
   if (a->smooth > R3D_ENVELOPE_MAX_SMOOTH)
     return refuse(who, "at most R3D_ENVELOPE_MAX_SMOOTH (64) smoothing passes, got " + std::to_string(a->smooth));
   if (!a->d_bins) return refuse(who, "null bins");
@@ -240,23 +164,18 @@ int enqueue_envelope_shape(const char* who, uint32_t n_batches, const double* d_
                            const uint32_t* d_bins, double* d_shape, double* d_shape_se, double* d_envelope,
                            double* d_envelope_se, uint32_t* d_peak_bin, uint32_t* d_half_bin, uint32_t* d_lit,
                            uint64_t* d_bad, hipStream_t s) {
+  RowsLaunch go(n_batches, d_shape_se || d_envelope_se, spec->last - spec->first + 1);
   ShapeArgs a;
   a.x = d_batch_energy, a.bins = d_bins, a.shape = d_shape, a.shape_se = d_shape_se, a.envelope = d_envelope;
   a.envelope_se = d_envelope_se, a.peak_bin = d_peak_bin, a.half_bin = d_half_bin, a.lit = d_lit;
   a.n_batches = n_batches, a.n_seis = spec->n_seismometers, a.n_bins = spec->n_bins, a.first = spec->first;
-  a.n_array = spec->last - spec->first + 1, a.smooth = spec->smooth;
-  a.rows = n_batches >= 2 && (d_shape_se || d_envelope_se) ? n_batches + 1 : 1;
+  a.n_array = spec->last - spec->first + 1, a.smooth = spec->smooth, a.rows = go.rows;
   for (int k = 0; k < kWindowComponents; k++) a.w[k] = spec->weight[k];
-  const uint32_t groups = a.n_array < kShapeMaxGroups ? a.n_array : kShapeMaxGroups;
-  void* scratch = nullptr;
-  if (hipError_t err = hipMallocAsync(&scratch, (size_t)groups * 2 * a.rows * a.n_bins * sizeof(double), s); err != hipSuccess)
-    return refuse(who, err, "scratch for the rows");
-  a.scratch = static_cast<double*>(scratch);
-  envelope_shape_kernel<<<dim3(groups), dim3(kShapeBlock), 0, s>>>(a);
-  if (d_bad) shape_bad_kernel<<<dim3(1), dim3(kShapeBlock), 0, s>>>(d_bins, a.n_array, a.n_bins, d_bad);
-  hipError_t err = hipGetLastError();
-  if (hipError_t f = hipFreeAsync(scratch, s); f != hipSuccess && err == hipSuccess) err = f;
-  return err == hipSuccess ? 0 : refuse(who, err);
+  if (go.take(who, (size_t)go.groups * 2 * a.rows * a.n_bins, s)) return 1;
+  a.scratch = static_cast<double*>(go.scratch);
+  envelope_shape_kernel<<<dim3(go.groups), dim3(kRowsBlock), 0, s>>>(a);
+  if (d_bad) envelope_count_kernel<<<dim3(1), dim3(kRowsBlock), 0, s>>>(d_bins, nullptr, a.n_array, a.n_bins, d_bad, nullptr);
+  return go.give(who, s);
 }
 
 }  // namespace

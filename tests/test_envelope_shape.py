@@ -456,12 +456,13 @@ def test_write_envshape_round_trips_every_value_at_17_digits(tmp_path):
 
 # ---- the add-on's place -------------------------------------------------------------------------------------------------------
 def test_the_envelope_shape_lives_in_an_add_on_of_its_own():
-    """One .hip and one header, on include/r3d.h, common/r3d_entry.h and the two sibling headers, nothing from csrc/ and
-    nothing of it in the hashed kernel sources, whose hash is the parent commit's; no update of memory shared between
-    workgroups; the sibling headers are prerequisites in the Makefile."""
+    """One .hip, its header and the header of the rows it shares with the envelope misfit, on include/r3d.h,
+    common/r3d_entry.h and the two sibling headers, nothing from csrc/ and nothing of it in the hashed kernel sources, whose
+    hash is the parent commit's; no update of memory shared between workgroups; the sibling headers are prerequisites in the
+    Makefile."""
     import bench
     shapes = os.path.join(REPO, "radiative3d_amd", "shapes")
-    assert sorted(os.listdir(shapes)) == ["r3d_envelope_shape.h", "r3d_envelope_shape.hip"]
+    assert sorted(os.listdir(shapes)) == ["r3d_envelope_rows.h", "r3d_envelope_shape.h", "r3d_envelope_shape.hip"]
     csrc = os.path.join(REPO, "radiative3d_amd", "csrc")
     for f in os.listdir(csrc):
         text = open(os.path.join(csrc, f), errors="ignore").read()
@@ -470,10 +471,11 @@ def test_the_envelope_shape_lives_in_an_add_on_of_its_own():
     whole = open(os.path.join(shapes, "r3d_envelope_shape.hip")).read()
     text = re.sub(r"//[^\n]*", "", whole)
     assert "csrc/" not in text and "atomic" not in whole.replace("no atomics", "") and '#include "../common/r3d_entry.h"' in text
-    head = open(os.path.join(shapes, "r3d_envelope_shape.h")).read()
-    assert '#include "../stats/r3d_window_sums.h"' in head and '#include "../arrays/r3d_array_image.h"' in head
-    code = re.sub(r"//[^\n]*", "", head)
-    assert not re.search(r"\b(pow|log|log10|exp)\s*\(", code) and "csrc/" not in code and "atomic" not in head
+    for name in ("r3d_envelope_shape.h", "r3d_envelope_rows.h"):
+        head = open(os.path.join(shapes, name)).read()
+        assert '#include "../stats/r3d_window_sums.h"' in head and '#include "../arrays/r3d_array_image.h"' in head, name
+        code = re.sub(r"//[^\n]*", "", head)
+        assert not re.search(r"\b(pow|log|log10|exp)\s*\(", code) and "csrc/" not in code and "atomic" not in head, name
     make = open(os.path.join(REPO, "Makefile")).read()
     assert re.search(r"^ADDONS := .*\bshapes\b", make, re.M)
     assert "$(filter shapes,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h" in make
