@@ -1025,6 +1025,99 @@ int r3d_run_batched_envelope_misfit(r3d_engine* e, uint64_t n, uint64_t first_id
                                     r3d_result* out, double* energy_se, double* counts_se, const r3d_misfit_spec* spec,
                                     r3d_misfit_result* res);
 
+/* ---- the slant stack of a receiver array with jackknife errors ---------------------------
+ * The products above give every SINGLE receiver an error bar, and the travel-time image shows the whole array only as a
+ * picture whose slanted streaks -- Pn, Pg, Sn, Lg by their apparent velocity -- are read off by eye.  This combines the
+ * receivers ACROSS a linear array (vis/seisplot/array.m's geometry): the slant stack (vespagram, tau-p image), the beam
+ * power per trial slowness in delay windows, and per window the slowness and the delay of the strongest beam.  A peak over
+ * slownesses is nonlinear in all rows of all receivers: the errors are jackknives over the batch blocks where they lie.
+ * radiative3d_amd/beams/r3d_slant_stack.h has the arithmetic:
+ *     SHIFTS.  M = n_slowness trial slownesses p_m = p0 + m dp reach the device as shifts per slowness and array receiver:
+ *       s = (p_m (r_i - r_ref)) / dt, k = floor(s) (int32), f = s - k in [0, 1) (double).  r3d_slant_shifts makes them on the
+ *       host; where the rounded s - k would be 1.0 (a tiny negative s) the entry is k + 1, f = 0.  Nothing transcendental
+ *       runs on the device.
+ *     ROWS per receiver over the whole trace [0, n_bins): the total t and, for B >= 2, the t_(j), as r3d_envelope_shape makes
+ *       them (weights finite and >= 0; scans, never t - e_j); v = sqrt(row) if `amplitude`, else the row; then `smooth` passes
+ *       of the shape's three-point rule.
+ *     SAMPLE of receiver i at slowness m, delay bin b, c = b + k: it contributes iff 0 <= f < 1, 0 <= c <= n_bins - 1 and
+ *       (f == 0 or c + 1 <= n_bins - 1); a = v[c] if f == 0, else (1 - f) v[c] + f v[c + 1] (two products, one add, not
+ *       contracted).  Nothing outside a row is read.  An entry with f outside [0, 1) (a NaN too) contributes nowhere and is
+ *       counted in bad_shifts.
+ *     STACK.  acc = +0.0, then for the contributing receivers in the order i = 0 .. A - 1: acc = acc + gain_i a_i (gain
+ *       finite and >= 0, a pure multiplier); fold[m][b] = how many contribute; stack[m][b] = acc / (double)fold, +0.0 where
+ *       fold == 0.  The order is the definition: one work-item owns an element.
+ *     CURVES per window w of bins [c0, c1) (W = n_windows): power[w][m] = rowsum(stack[m]^2) over the window by the window
+ *       sum's strands and tree; peak[w][m] = rowmax with the first bin that holds it.
+ *     FOUR NUMBERS per window (R3D_SLANT_N):  0 Pmax = power[w][m*], m* the first m that holds the curve's maximum (a value
+ *       above +0.0)  1 p* = p0 + (m* + d) dp, d the vertex of the parabola through the curve at m* - 1, m*, m* + 1 as the
+ *       envelope shape's tp takes it (|d| <= 0.5; 0 at either end of the grid)  2 tau* = the absolute bin of peak[w][m*]
+ *       3 that peak value.  A window with c0 > c1 or c1 > n_bins is never read through: dead, and counted in bad.  A dead
+ *       window (no bins, or no power above zero) gives Pmax = +0.0 and NaN for the other three.
+ *     se, B >= 2: every stack[m][b], power[w][m] and each of the four numbers again from every t_(j) of all receivers;
+ *       se = sqrt((B-1)/B sum_j (v_(j) - mean)^2) as r3d_array_image takes it; NaN as soon as one value is NaN.
+ *     The same bits on every run, machine and launch geometry; the header derives the rounding bounds.
+ *
+ * r3d_slant_shifts: host only, no device needed.  shift_bin, shift_frac [n_slowness][n_array] from the receivers' distances.
+ * REFUSED (non-zero, r3d_last_error): a null pointer, dt not finite and > 0, an s that is not finite or with |s| >= 2^30.
+ *
+ * r3d_slant_stack: device level, like r3d_envelope_misfit -- B >= 1 batch-major blocks d_batch_energy [B][n_seis][n_bins][5]
+ * on `device`, only read; spec->d_shift_bin, d_shift_frac [M][A], d_gain [A], d_windows [W][2] on the device (d_windows may
+ * be NULL where W == 0).  WRITTEN, every entry by one work-item: d_stack, d_stack_se [M][n_bins]; d_fold [M][n_bins] (u32);
+ * d_power, d_power_se [W][M]; d_picks, d_picks_se [W][4]; d_bad, d_bad_shifts (one uint64 each).  Every output but d_stack
+ * may be NULL; an se needs B >= 2.  No atomics, fixed order, 64-bit offsets, capped grids; the rows and the rows' stacks
+ * pass through scratch taken from and returned to the stream's memory pool (a scratch that cannot be taken is a refusal).
+ * Asynchronous on `stream`.  REFUSED (non-zero, r3d_last_error, nothing enqueued, no buffer touched; all checked before any
+ * HIP call): a null blocks, spec, stack, shift, gain or (W > 0) windows pointer, a size mismatch, n_batches == 0, B > 64,
+ * n_bins == 0, last < first, last >= n_seismometers, a weight that is negative or not finite, smooth >
+ * R3D_ENVELOPE_MAX_SMOOTH, amplitude not 0 or 1, n_slowness == 0 or > R3D_SLANT_MAX_SLOWNESS, n_windows >
+ * R3D_SLANT_MAX_WINDOWS, p0 or dp not finite, an se array with B < 2.
+ *
+ * r3d_run_batched_slant_stack: r3d_run_batched (same arguments, refusals, out / energy_se / counts_se) that keeps its batch
+ * blocks on the device, makes the stack there and reads back only the arrays of *res, all WRITTEN.  For THIS call the
+ * spec's four arrays are HOST arrays, checked here: a gain that is negative or not finite, an f outside [0, 1) and a window
+ * with c0 > c1 or c1 > n_bins are refused, as is a spec whose n_seismometers / n_bins are not the model's, a null res or one
+ * of another size, a null stack.  A refusal touches nothing.  Out of scope: a job sharded over several devices
+ * (r3d_node_run_batched has no slant call), and combining this call in one run with the windows, the array image, the
+ * envelope shape or the envelope misfit.                                                                                  */
+#define R3D_SLANT_MAX_SLOWNESS 256
+#define R3D_SLANT_MAX_WINDOWS 8
+#define R3D_SLANT_N 4
+typedef struct r3d_slant_spec {
+  uint32_t size;                    /* sizeof(r3d_slant_spec): a mismatch is refused           */
+  uint32_t n_seismometers, n_bins;
+  uint32_t first, last;             /* the array: seismometers first .. last                   */
+  uint32_t smooth;                  /* three-point passes, 0 .. R3D_ENVELOPE_MAX_SMOOTH        */
+  uint32_t amplitude;               /* 1: stack the roots of the energies; 0: the energies     */
+  uint32_t n_slowness;              /* M, 1 .. R3D_SLANT_MAX_SLOWNESS                          */
+  uint32_t n_windows;               /* W, 0 .. R3D_SLANT_MAX_WINDOWS                           */
+  uint32_t pad_;
+  double   p0, dp;                  /* the slowness grid, for p* alone                         */
+  const int32_t*  d_shift_bin;      /* [M][A] k; device (the run: host)                        */
+  const double*   d_shift_frac;     /* [M][A] f in [0, 1); device (the run: host)              */
+  const double*   d_gain;           /* [A] finite, >= 0; device (the run: host)                */
+  const uint32_t* d_windows;        /* [W][2] c0, c1; device (the run: host)                   */
+  double   weight[R3D_N_ENERGY];
+} r3d_slant_spec;
+typedef struct r3d_slant_result {
+  uint32_t size;                    /* sizeof(r3d_slant_result)                                */
+  uint32_t pad_;
+  double*   stack;                  /* [M][n_bins]                                             */
+  double*   stack_se;               /* [M][n_bins]  may be NULL                                */
+  uint32_t* fold;                   /* [M][n_bins]  may be NULL                                */
+  double*   power;                  /* [W][M]       may be NULL                                */
+  double*   power_se;               /* [W][M]       may be NULL                                */
+  double*   picks;                  /* [W][4]       may be NULL                                */
+  double*   picks_se;               /* [W][4]       may be NULL                                */
+} r3d_slant_result;
+int r3d_slant_shifts(double dt, uint32_t n_array, const double* distances, double r_ref, double p0, double dp,
+                     uint32_t n_slowness, int32_t* shift_bin, double* shift_frac);
+int r3d_slant_stack(int device, uint32_t n_batches, const double* d_batch_energy, const r3d_slant_spec* spec, double* d_stack,
+                    double* d_stack_se, uint32_t* d_fold, double* d_power, double* d_power_se, double* d_picks,
+                    double* d_picks_se, uint64_t* d_bad, uint64_t* d_bad_shifts, void* stream);
+int r3d_run_batched_slant_stack(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                                r3d_result* out, double* energy_se, double* counts_se, const r3d_slant_spec* spec,
+                                r3d_slant_result* res);
+
 /* ---- run to a target standard error: rounds of batches, judged on the device ------------
  * How many histories a run needs is asked before every run; this call answers it by running in rounds and looking at the
  * error bars where they lie.  radiative3d_amd/precision/r3d_precision.h has the criterion's arithmetic, built by the host too.

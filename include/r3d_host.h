@@ -306,6 +306,61 @@ int r3dh_envfit_plan(const r3dh_model* m, const r3dh_envfit_opts* rq, double* di
                      double* observed, uint32_t* max_lag);
 int r3dh_write_envfit(const r3dh_model* m, const r3dh_envfit_opts* rq, const r3dh_envfit_result* res, const char* path);
 
+/* --slant-stack=PMIN,PMAX,NP[,RREF[,SMOOTH]] [--slant-array=FIRST,LAST] [--slant-axes=X,Y,Z] [--slant-energy]
+ * [--slant-range-power=Q] [--slant-windows=T0,T1[,T0,T1...]] in the model's arguments (the last five refused without the first;
+ * the first without --error-batches and with --job-error-batches, --lapse-windows, --ttimage, --target-error,
+ * --envelope-shape, --envelope-fit or --reports): the slant stack of a linear array over NP slownesses PMIN .. PMAX (s/km)
+ * about the reference distance RREF (km; default: the mean of the first and the last receiver's distance) with jackknife
+ * errors from the batches (r3d.h r3d_run_batched_slant_stack).  Amplitudes are stacked (energies with --slant-energy), after
+ * SMOOTH three-point passes (default 0), each receiver times (r_i / r_ref)^Q (default Q = 0); the windows are in seconds of
+ * the run's clock (default: one over the whole trace; at most R3D_SLANT_MAX_WINDOWS).
+ * r3dh_slant_request: returns 1 and fills *rq when the stack was asked for, 0 otherwise; -1 (r3dh_last_error) if
+ * --slant-array's LAST is not a seismometer of the model.
+ * r3dh_slant_plan: for the A = last - first + 1 receivers, distances [A] as r3dh_lapse_plan gives them (range_km); grid[3] =
+ * r_ref, p0, dp (dp = (PMAX - PMIN) / (NP - 1); 0 for NP == 1); shift_bin, shift_frac [NP][A] by r3d.h r3d_slant_shifts' rule;
+ * gain [A] = (r_i / r_ref)^Q by pow; windows [W][2] in bins, floor(t / dt) clipped to [0, n_bins], W = max(1, n_windows).
+ * Non-zero: what the shift rule refuses, a reference distance or a gain that is not finite and positive / not negative.
+ * r3dh_write_slant: slantstack.octv-style GNU/Octave text at 17 digits to `path`: Slowness [M] (s/km), TimeWindow [2] (0,
+ * n_bins dt), RefDistance, Distances [A], SlantSeismometers [A], SlantAxes [3], SlantAmplitude, SlantSmooth,
+ * SlantRangePower, Stack / StackSE [M][n_bins], Fold [M][n_bins], Windows [W][2] (seconds: bins times dt), WindowBins [W][2],
+ * Power / PowerSE [W][M], Picks / PicksSE [W][4] (Pmax, p* in s/km, tau* in seconds at the bin's begin, the peak; the se of
+ * tau* times dt), NumBatches, NumPhonons.  Returns 0 ok.                                                                */
+typedef struct r3dh_slant_opts {
+  uint32_t size;                 /* sizeof(r3dh_slant_opts)                                      */
+  uint32_t first, last;          /* the array: seismometers first .. last                        */
+  uint32_t smooth;               /* three-point passes, 0 .. 64                                  */
+  uint32_t amplitude;            /* 1: amplitudes are stacked; 0: energies                       */
+  uint32_t n_slowness;           /* NP, 1 .. R3D_SLANT_MAX_SLOWNESS                              */
+  uint32_t n_windows;            /* 0: one window over the whole trace                           */
+  uint32_t pad_;
+  double   p_min, p_max;         /* s/km                                                         */
+  double   r_ref;                /* km; NaN: the mean of the end receivers' distances            */
+  double   range_power;          /* Q                                                            */
+  double   axes[3];              /* weights of the trace's X, Y, Z                               */
+  double   windows[R3D_SLANT_MAX_WINDOWS][2]; /* seconds                                         */
+} r3dh_slant_opts;
+typedef struct r3dh_slant_result {
+  uint32_t size;                 /* sizeof(r3dh_slant_result)                                    */
+  uint32_t n_batches;
+  uint32_t n_windows;            /* W of the plan                                                */
+  uint32_t pad_;
+  uint64_t n_phonons;
+  double   grid[3];              /* r_ref, p0, dp: r3dh_slant_plan's                             */
+  const double*   distances;     /* [A]                                                          */
+  const uint32_t* windows;       /* [W][2] bins                                                  */
+  const double*   stack;         /* [M][n_bins] as r3d_run_batched_slant_stack gives it          */
+  const double*   stack_se;      /* [M][n_bins]                                                  */
+  const uint32_t* fold;          /* [M][n_bins]                                                  */
+  const double*   power;         /* [W][M]                                                       */
+  const double*   power_se;      /* [W][M]                                                       */
+  const double*   picks;         /* [W][4]                                                       */
+  const double*   picks_se;      /* [W][4]                                                       */
+} r3dh_slant_result;
+int r3dh_slant_request(const r3dh_model* m, r3dh_slant_opts* rq);
+int r3dh_slant_plan(const r3dh_model* m, const r3dh_slant_opts* rq, double* distances, double* grid, int32_t* shift_bin,
+                    double* shift_frac, double* gain, uint32_t* windows);
+int r3dh_write_slant(const r3dh_model* m, const r3dh_slant_opts* rq, const r3dh_slant_result* res, const char* path);
+
 /* --target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]] [--target-array=FIRST,LAST] [--target-components=LETTERS] in the
  * model's arguments (the last two refused without the first; the first without --error-batches, with --job-error-batches,
  * --lapse-windows, --ttimage or --reports, on more than one shard, and with a --num-phonons that is no multiple of ROUNDS

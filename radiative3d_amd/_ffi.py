@@ -169,6 +169,25 @@ class MisfitResult(C.Structure):
                 ("xcorr", C.c_void_p), ("xcorr_se", C.c_void_p), ("envelope", C.c_void_p), ("lit", C.c_void_p)]
 
 
+R3D_SLANT_MAX_SLOWNESS, R3D_SLANT_MAX_WINDOWS, R3D_SLANT_N = 256, 8, 4
+
+
+class SlantSpec(C.Structure):
+    """include/r3d.h r3d_slant_spec"""
+    _fields_ = [("size", C.c_uint32), ("n_seismometers", C.c_uint32), ("n_bins", C.c_uint32), ("first", C.c_uint32),
+                ("last", C.c_uint32), ("smooth", C.c_uint32), ("amplitude", C.c_uint32), ("n_slowness", C.c_uint32),
+                ("n_windows", C.c_uint32), ("pad_", C.c_uint32), ("p0", C.c_double), ("dp", C.c_double),
+                ("d_shift_bin", C.c_void_p), ("d_shift_frac", C.c_void_p), ("d_gain", C.c_void_p), ("d_windows", C.c_void_p),
+                ("weight", C.c_double * R3D_N_ENERGY)]
+
+
+class SlantResult(C.Structure):
+    """include/r3d.h r3d_slant_result"""
+    _fields_ = [("size", C.c_uint32), ("pad_", C.c_uint32), ("stack", C.c_void_p), ("stack_se", C.c_void_p),
+                ("fold", C.c_void_p), ("power", C.c_void_p), ("power_se", C.c_void_p), ("picks", C.c_void_p),
+                ("picks_se", C.c_void_p)]
+
+
 R3D_PRECISION_MAX_ROUNDS = 64
 R3D_PRECISION_DEFAULT_MASK = 0x18   # P | S: an axis normal to the motion holds rounding noise and would never be met
 
@@ -223,6 +242,14 @@ class EnvShapeOpts(C.Structure):
     """include/r3d_host.h r3dh_envshape_opts"""
     _fields_ = [("size", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("smooth", C.c_uint32),
                 ("phase_edge", C.c_double * 2), ("window", C.c_double * 2), ("axes", C.c_double * 3)]
+
+
+class SlantOpts(C.Structure):
+    """include/r3d_host.h r3dh_slant_opts"""
+    _fields_ = [("size", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("smooth", C.c_uint32),
+                ("amplitude", C.c_uint32), ("n_slowness", C.c_uint32), ("n_windows", C.c_uint32), ("pad_", C.c_uint32),
+                ("p_min", C.c_double), ("p_max", C.c_double), ("r_ref", C.c_double), ("range_power", C.c_double),
+                ("axes", C.c_double * 3), ("windows", (C.c_double * 2) * 8)]
 
 
 class EnvShapeResult(C.Structure):
@@ -370,6 +397,11 @@ def host_lib():
         L.r3dh_envshape_plan.argtypes = [C.c_void_p, C.POINTER(EnvShapeOpts), _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
         L.r3dh_write_envshape.restype = C.c_int
         L.r3dh_write_envshape.argtypes = [C.c_void_p, C.POINTER(EnvShapeOpts), C.POINTER(EnvShapeResult), C.c_char_p]
+        L.r3dh_slant_request.restype = C.c_int
+        L.r3dh_slant_request.argtypes = [C.c_void_p, C.POINTER(SlantOpts)]
+        L.r3dh_slant_plan.restype = C.c_int
+        L.r3dh_slant_plan.argtypes = [C.c_void_p, C.POINTER(SlantOpts), _dp, _dp, C.POINTER(C.c_int32), _dp, _dp,
+                                      C.POINTER(C.c_uint32)]
         L.r3dh_observed_to_bins.restype = C.c_int
         L.r3dh_observed_to_bins.argtypes = [_dp, C.c_uint32, C.c_uint32] + [C.c_double] * 4 + [C.c_uint32, _dp]
         L.r3dh_read_octave.restype = C.c_int
@@ -590,6 +622,14 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_run_batched_envelope_misfit.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                                       C.POINTER(Result), _dp, _dp, C.POINTER(MisfitSpec),
                                                       C.POINTER(MisfitResult)]
+        L.r3d_slant_shifts.restype = C.c_int
+        L.r3d_slant_shifts.argtypes = [C.c_double, C.c_uint32, _dp, C.c_double, C.c_double, C.c_double, C.c_uint32,
+                                       C.POINTER(C.c_int32), _dp]
+        L.r3d_slant_stack.restype = C.c_int
+        L.r3d_slant_stack.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.POINTER(SlantSpec)] + [C.c_void_p] * 10
+        L.r3d_run_batched_slant_stack.restype = C.c_int
+        L.r3d_run_batched_slant_stack.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                  C.POINTER(Result), _dp, _dp, C.POINTER(SlantSpec), C.POINTER(SlantResult)]
         L.r3d_run_batched_windows.restype = C.c_int
         L.r3d_run_batched_windows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
                                               _dp, _dp, C.POINTER(WindowSpec), _dp, C.POINTER(C.c_uint64), _dp, _dp]

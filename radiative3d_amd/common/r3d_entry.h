@@ -2,7 +2,7 @@
 // error text, the caller's device kept across the call, device scratch that frees itself, the refusals the calls on
 // the event grid share, those the specs of the receiver-array add-ons share, and those of the batched runs with the way they learn their engine's device, the format of
 // the block their results come down in (ResultBlock) and the way a run is brought to the host (BatchedRun).  Host code
-// only, all inline.  An add-on (stats/, views/, maps/, arrays/, precision/, shapes/, fits/) includes this and include/r3d.h and
+// only, all inline.  An add-on (stats/, views/, maps/, arrays/, precision/, shapes/, fits/, beams/) includes this and include/r3d.h and
 // nothing from csrc/; csrc/r3d_volume.hip, whose entry points are of the same kind, uses it too.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -77,7 +77,7 @@ inline const char* bad_frame_range(const r3d_volume_desc* v, uint32_t frame_begi
   return nullptr;
 }
 
-// What the calls on a receiver array (arrays/, shapes/, fits/) refuse on the fields their specs share -- size, n_bins, first,
+// What the calls on a receiver array (arrays/, shapes/, fits/, beams/) refuse on the fields their specs share -- size, n_bins, first,
 // last, n_seismometers, weight[] -- (0: nothing; else the message is set).  `what`: the spec in the message's words; `type`:
 // its struct; `why_weights`: why this call cannot take a negative weight.
 template <class Spec>

@@ -105,6 +105,28 @@ void run_fit(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint64
     throw Runtime(r3d_last_error());
 }
 
+// --slant-stack: the batched run with its batch blocks kept on the device and the array's slant stack, its curves and picks,
+// with their jackknives, made there (include/r3d.h r3d_run_batched_slant_stack).
+void run_slant(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total,
+               BatchProducts& p) {
+  const r3dh_slant_opts& rq = job.slant;
+  const size_t M = rq.n_slowness, W = job.slant_windows.size() / 2, px = M * d.params.n_bins;
+  r3d_slant_spec spec{};
+  spec.size = sizeof spec, spec.n_seismometers = (uint32_t)d.n_seismometers, spec.n_bins = d.params.n_bins;
+  spec.first = rq.first, spec.last = rq.last, spec.smooth = rq.smooth, spec.amplitude = rq.amplitude;
+  spec.n_slowness = rq.n_slowness, spec.n_windows = (uint32_t)W, spec.p0 = job.slant_grid[1], spec.dp = job.slant_grid[2];
+  spec.d_shift_bin = job.slant_bin.data(), spec.d_shift_frac = job.slant_frac.data();   // (for this call: on the host)
+  spec.d_gain = job.slant_gain.data(), spec.d_windows = job.slant_windows.data();
+  for (int k = 0; k < 3; k++) spec.weight[k] = rq.axes[k];
+  p.stack.assign(px, 0.0), p.stack_se.assign(px, 0.0), p.fold.assign(px, 0), p.power.assign(W * M, 0.0), p.power_se.assign(W * M, 0.0);
+  p.picks.assign(W * R3D_SLANT_N, 0.0), p.picks_se.assign(W * R3D_SLANT_N, 0.0), p.n_phonons = n;
+  r3d_slant_result res{};
+  res.size = sizeof res, res.stack = p.stack.data(), res.stack_se = p.stack_se.data(), res.fold = p.fold.data();
+  res.power = p.power.data(), res.power_se = p.power_se.data(), res.picks = p.picks.data(), res.picks_se = p.picks_se.data();
+  if (r3d_run_batched_slant_stack(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data(), &spec, &res))
+    throw Runtime(r3d_last_error());
+}
+
 // --target-error: --num-phonons is the cap, run in rounds of the job's batches each and judged on the device after
 // every round (include/r3d.h r3d_run_to_precision); one line per round, and one that says whether the target was met.
 void run_precision(const BatchJob& job, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total, BatchProducts& p) {
@@ -132,7 +154,8 @@ BatchJob make_batch_job(const MissionParams& mission, const Model& model) {
   if (!mission.bRunSim || !(mission.ErrorBatches || mission.JobErrorBatches)) return job;
   job.dir = mission.OutputDir, job.batches = mission.ErrorBatches ? mission.ErrorBatches : mission.JobErrorBatches;
   job.kind = !mission.ErrorBatches ? BatchJob::JOB_ERRORS : mission.bLapse ? BatchJob::LAPSE : mission.bTTImage ? BatchJob::IMAGE
-             : mission.bTarget ? BatchJob::PRECISION : mission.bEnvShape ? BatchJob::SHAPE : mission.bEnvFit ? BatchJob::FIT : BatchJob::ERRORS;
+             : mission.bTarget ? BatchJob::PRECISION : mission.bEnvShape ? BatchJob::SHAPE : mission.bEnvFit ? BatchJob::FIT
+             : mission.bSlant ? BatchJob::SLANT : BatchJob::ERRORS;
   if (job.kind == BatchJob::PRECISION) {
     PrecisionRequest(model, mission, &job.precision);
     job.rounds = mission.TargetRounds;
@@ -158,6 +181,13 @@ BatchJob make_batch_job(const MissionParams& mission, const Model& model) {
     job.fit_observed.assign(A * model.Desc().params.n_bins, 0.0);
     EnvFitPlan(model, job.fit, job.env_distances.data(), job.env_bins.data(), job.env_clipped.data(), job.fit_observed.data(),
                &job.fit_max_lag);
+  } else if (job.kind == BatchJob::SLANT) {
+    SlantRequest(model, mission, &job.slant);
+    const size_t A = (size_t)job.slant.last - job.slant.first + 1, M = job.slant.n_slowness;
+    job.slant_distances.assign(A, 0.0), job.slant_gain.assign(A, 0.0), job.slant_bin.assign(M * A, 0), job.slant_frac.assign(M * A, 0.0);
+    job.slant_windows.assign(2 * (size_t)(job.slant.n_windows ? job.slant.n_windows : 1), 0);
+    SlantPlan(model, job.slant, job.slant_distances.data(), job.slant_grid, job.slant_bin.data(), job.slant_frac.data(),
+              job.slant_gain.data(), job.slant_windows.data());
   }
   return job;
 }
@@ -187,6 +217,7 @@ BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& d, r3d_no
   else if (job.kind == BatchJob::PRECISION) run_precision(job, e, n, seed, total, p);
   else if (job.kind == BatchJob::SHAPE) run_shape(job, d, e, n, seed, total, p);
   else if (job.kind == BatchJob::FIT) run_fit(job, d, e, n, seed, total, p);
+  else if (job.kind == BatchJob::SLANT) run_slant(job, d, e, n, seed, total, p);
   else if (shards ? r3d_node_run_batched(node, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data())
                   : r3d_run_batched(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data()))
     throw Runtime(r3d_last_error());
@@ -210,13 +241,24 @@ void write_batch_outputs(const BatchJob& job, const Model& model, const BatchPro
     return;
   }
   OutputSeismometerErrors(model, p.energy_se.data(), p.counts_se.data(), job.batches, job.dir);
-  if (job.kind != BatchJob::LAPSE && job.kind != BatchJob::IMAGE && job.kind != BatchJob::SHAPE && job.kind != BatchJob::FIT) return;
+  if (job.kind != BatchJob::LAPSE && job.kind != BatchJob::IMAGE && job.kind != BatchJob::SHAPE && job.kind != BatchJob::FIT &&
+      job.kind != BatchJob::SLANT)
+    return;
   const std::string fn = output_path(job.dir, job.kind == BatchJob::LAPSE   ? "lapse.octv"
                                               : job.kind == BatchJob::IMAGE ? "ttimage.octv"
                                               : job.kind == BatchJob::SHAPE ? "envshape.octv"
+                                              : job.kind == BatchJob::SLANT ? "slantstack.octv"
                                                                             : "envfit.octv");
   std::ofstream f(fn.c_str());
-  if (job.kind == BatchJob::FIT) {
+  if (job.kind == BatchJob::SLANT) {
+    r3dh_slant_result res{};
+    res.size = sizeof res, res.n_batches = job.batches, res.n_windows = (uint32_t)(job.slant_windows.size() / 2), res.n_phonons = p.n_phonons;
+    for (int k = 0; k < 3; k++) res.grid[k] = job.slant_grid[k];
+    res.distances = job.slant_distances.data(), res.windows = job.slant_windows.data(), res.stack = p.stack.data();
+    res.stack_se = p.stack_se.data(), res.fold = p.fold.data(), res.power = p.power.data(), res.power_se = p.power_se.data();
+    res.picks = p.picks.data(), res.picks_se = p.picks_se.data();
+    OutputSlant(model, job.slant, res, f);
+  } else if (job.kind == BatchJob::FIT) {
     r3dh_envfit_result res{};
     res.size = sizeof res, res.n_batches = job.batches, res.max_lag = job.fit_max_lag;
     res.distances = job.env_distances.data(), res.bins = job.env_bins.data(), res.clipped = job.env_clipped.data();

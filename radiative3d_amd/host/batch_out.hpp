@@ -1,6 +1,6 @@
 // batch_out.hpp -- the batched-run stage of ./main: what --error-batches, --job-error-batches, --lapse-windows, --ttimage,
-// --target-error, --envelope-shape and --envelope-fit run in place of the plain run, and what they write after it
-// (seis_NNN_err.octv, lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv).
+// --target-error, --envelope-shape, --envelope-fit and --slant-stack run in place of the plain run, and what they write after
+// it (seis_NNN_err.octv, lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv, slantstack.octv).
 // Compiled into ./main beside main.cpp (it calls r3d_run_batched* and r3d_node_run_batched of the engine's library, so
 // it is no part of libr3d_host.so); its row arithmetic is batch_plan.hpp.
 #ifndef R3DH_BATCH_OUT_HPP_
@@ -20,8 +20,8 @@ inline std::string output_path(const std::string& dir, const std::string& name) 
 // What the options ask for, and where it goes.
 struct BatchJob {
   // ERRORS: --error-batches alone; LAPSE, IMAGE, PRECISION, SHAPE, FIT: with --lapse-windows, --ttimage, --target-error,
-  // --envelope-shape, --envelope-fit; JOB_ERRORS: --job-error-batches
-  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION, SHAPE, FIT } kind = NONE;
+  // --envelope-shape, --envelope-fit; SLANT: with --slant-stack; JOB_ERRORS: --job-error-batches
+  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION, SHAPE, FIT, SLANT } kind = NONE;
   unsigned batches = 0;   // (PRECISION: of a round)
   std::string dir;   // --output-dir
   // LAPSE: the request and the array's plan, [S] receivers (include/r3d_host.h r3dh_lapse_plan)
@@ -45,6 +45,13 @@ struct BatchJob {
   r3dh_envfit_opts fit{};              // (fit.file points into the mission the job was made from)
   std::vector<double> fit_observed;    // [A][n_bins]
   uint32_t fit_max_lag = 0;
+  // SLANT: the request and the array's plan (include/r3d_host.h r3dh_slant_plan): distances and gains [A], shifts [M][A],
+  // windows [W][2] in bins, the grid r_ref, p0, dp
+  r3dh_slant_opts slant{};
+  std::vector<double> slant_distances, slant_frac, slant_gain;
+  std::vector<int32_t> slant_bin;
+  std::vector<uint32_t> slant_windows;
+  double slant_grid[3] = {0, 0, 0};
 };
 
 // What a batched run hands back beside its totals: every bin's standard error, then the kind's own arrays (the shapes
@@ -70,11 +77,15 @@ struct BatchProducts {
   std::vector<uint32_t> env_peak_bin, env_half_bin, env_lit;
   // FIT (its envelope and lit: SHAPE's)
   std::vector<double> misfit, misfit_se, xcorr, xcorr_se;
+  // SLANT
+  std::vector<double> stack, stack_se, power, power_se, picks, picks_se;
+  std::vector<uint32_t> fold;
+  uint64_t n_phonons = 0;
 };
 
 // The job of a simulation run (`kind` stays NONE without one of the options).  The model is needed for the arrays:
 // throws what LapseRequest / LapsePlan / TTImageRequest / TTImagePlan / EnvShapeRequest / EnvShapePlan / EnvFitRequest /
-// EnvFitPlan (dataout.hpp) throw.
+// EnvFitPlan / SlantRequest / SlantPlan (dataout.hpp) throw.
 BatchJob make_batch_job(const MissionParams& mission, const Model& model);
 
 // What --error-batches cannot be combined with, told BEFORE the node is built.  Throws Runtime.
@@ -86,7 +97,8 @@ void check_batch_job(const BatchJob& job, size_t n_shards, uint32_t report_mask)
 BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& model, r3d_node* node, uint64_t n, uint64_t seed,
                             r3d_result& total);
 
-// seis_NNN_err.octv, then lapse.octv, ttimage.octv, precision.octv, envshape.octv or envfit.octv, under the job's directory.
+// seis_NNN_err.octv, then lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv or slantstack.octv, under the
+// job's directory.
 // Throws Runtime.
 void write_batch_outputs(const BatchJob& job, const Model& model, const BatchProducts& products);
 

@@ -278,6 +278,48 @@ int r3dh_write_envshape(const r3dh_model* m, const r3dh_envshape_opts* rq, const
   return 1;
 }
 
+int r3dh_slant_request(const r3dh_model* m, r3dh_slant_opts* rq) {
+  if (!m || !m->mission.bSlant) return 0;
+  if (!rq) return 1;
+  try {
+    SlantRequest(*m->model, m->mission, rq);
+    return 1;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return -1;
+}
+
+int r3dh_slant_plan(const r3dh_model* m, const r3dh_slant_opts* rq, double* distances, double* grid, int32_t* shift_bin,
+                    double* shift_frac, double* gain, uint32_t* windows) {
+  if (!m || !rq || !distances || !grid || !shift_bin || !shift_frac || !gain || !windows)
+    return g_error = "r3dh_slant_plan: null argument", 1;
+  try {
+    // (through the global coordinate system, as r3dh_lapse_plan)
+    SlantPlan(*m->model, *rq, distances, grid, shift_bin, shift_frac, gain, windows);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
+int r3dh_write_slant(const r3dh_model* m, const r3dh_slant_opts* rq, const r3dh_slant_result* res, const char* path) {
+  if (!m || !rq || !res || !path) return g_error = "r3dh_write_slant: null argument", 1;
+  if (!res->distances || !res->windows || !res->stack || !res->stack_se || !res->fold || !res->power || !res->power_se || !res->picks ||
+      !res->picks_se)
+    return g_error = "r3dh_write_slant: null array in the result", 1;
+  try {
+    std::ofstream f(path);
+    OutputSlant(*m->model, *rq, *res, f);
+    if (!f) throw Runtime(std::string("cannot write ") + path);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
 int r3dh_observed_to_bins(const double* samples, uint32_t n_samples, uint32_t stride, double t0, double t1, double t_begin,
                           double t_end, uint32_t n_bins, double* out) {
   if (ObservedToBins(samples, n_samples, stride, t0, t1, t_begin, t_end, n_bins, out)) return 0;

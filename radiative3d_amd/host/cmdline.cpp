@@ -24,7 +24,8 @@ enum OptID {
   OPTX_TTIMAGE, OPTX_TTIMAGE_ARRAY, OPTX_TTIMAGE_AXES, OPTX_TTIMAGE_FIT, OPTX_TTIMAGE_NORMCURVE,
   OPTX_TARGET, OPTX_TARGET_ARRAY, OPTX_TARGET_COMPONENTS,
   OPTX_ENVSHAPE, OPTX_ENVSHAPE_ARRAY, OPTX_ENVSHAPE_AXES,
-  OPTX_ENVFIT, OPTX_ENVFIT_ARRAY, OPTX_ENVFIT_AXES, OPTX_ENVFIT_ENERGY
+  OPTX_ENVFIT, OPTX_ENVFIT_ARRAY, OPTX_ENVFIT_AXES, OPTX_ENVFIT_ENERGY,
+  OPTX_SLANT, OPTX_SLANT_ARRAY, OPTX_SLANT_AXES, OPTX_SLANT_ENERGY, OPTX_SLANT_RANGEPOWER, OPTX_SLANT_WINDOWS
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -66,7 +67,9 @@ const std::map<std::string, OptID>& option_table() {
       {"--target-error", OPTX_TARGET}, {"--target-array", OPTX_TARGET_ARRAY}, {"--target-components", OPTX_TARGET_COMPONENTS},
       {"--envelope-shape", OPTX_ENVSHAPE}, {"--envelope-array", OPTX_ENVSHAPE_ARRAY}, {"--envelope-axes", OPTX_ENVSHAPE_AXES},
       {"--envelope-fit", OPTX_ENVFIT}, {"--envelope-fit-array", OPTX_ENVFIT_ARRAY}, {"--envelope-fit-axes", OPTX_ENVFIT_AXES},
-      {"--envelope-fit-energy", OPTX_ENVFIT_ENERGY}};
+      {"--envelope-fit-energy", OPTX_ENVFIT_ENERGY},
+      {"--slant-stack", OPTX_SLANT}, {"--slant-array", OPTX_SLANT_ARRAY}, {"--slant-axes", OPTX_SLANT_AXES},
+      {"--slant-energy", OPTX_SLANT_ENERGY}, {"--slant-range-power", OPTX_SLANT_RANGEPOWER}, {"--slant-windows", OPTX_SLANT_WINDOWS}};
   return t;
 }
 
@@ -533,6 +536,60 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
         mission.bEnvFitEnergy = true;
         mission.FitCompanion = "--envelope-fit-energy";
         break;
+      case OPTX_SLANT: {
+        static const char* const form = "--slant-stack=PMIN,PMAX,NP[,RREF[,SMOOTH]]: ";
+        for (int k = 0; k < 2; k++) mission.SlantP[k] = o.real();
+        const long np = o.integer();
+        long smooth = 0;
+        if (o.has()) mission.SlantRef = o.real();
+        if (o.has()) smooth = o.integer();
+        if (!std::isfinite(mission.SlantP[0]) || !std::isfinite(mission.SlantP[1]) || !(mission.SlantP[1] >= mission.SlantP[0]))
+          throw Runtime(std::string(form) + "the slownesses (s/km) must be finite, PMAX not below PMIN.");
+        if (np < 1 || np > 256 || (np == 1 && mission.SlantP[1] != mission.SlantP[0]))
+          throw Runtime(std::string(form) + "NP, the number of slownesses, must be 1 .. 256, and 1 only with PMAX = PMIN (got " +
+                        std::to_string(np) + ").");
+        if (!std::isnan(mission.SlantRef) && (!std::isfinite(mission.SlantRef) || !(mission.SlantRef > 0)))
+          throw Runtime(std::string(form) + "RREF, the reference distance (km), must be finite and positive.");
+        if (smooth < 0 || smooth > 64)
+          throw Runtime(std::string(form) + "SMOOTH, the three-point smoothing passes, must be 0 .. 64 (got " + std::to_string(smooth) + ").");
+        mission.SlantNP = (unsigned)np, mission.SlantSmooth = (unsigned)smooth;
+        mission.bSlant = true;
+        break;
+      }
+      case OPTX_SLANT_ARRAY:
+        mission.SlantArray[0] = o.integer();
+        mission.SlantArray[1] = o.integer();
+        if (mission.SlantArray[0] < 0 || mission.SlantArray[1] < mission.SlantArray[0])
+          throw Runtime("--slant-array=FIRST,LAST: seismometer indices with 0 <= FIRST <= LAST.");
+        mission.SlantCompanion = "--slant-array";
+        break;
+      case OPTX_SLANT_AXES:
+        for (int k = 0; k < 3; k++) mission.SlantAxes[k] = o.real();
+        for (int k = 0; k < 3; k++)
+          if (!std::isfinite(mission.SlantAxes[k]) || mission.SlantAxes[k] < 0)
+            throw Runtime("--slant-axes=X,Y,Z: the weights must be finite and not negative (roots are taken of the weighted energy).");
+        mission.SlantCompanion = "--slant-axes";
+        break;
+      case OPTX_SLANT_ENERGY:
+        mission.bSlantEnergy = true;
+        mission.SlantCompanion = "--slant-energy";
+        break;
+      case OPTX_SLANT_RANGEPOWER:
+        mission.SlantRangePower = o.real();
+        if (!std::isfinite(mission.SlantRangePower)) throw Runtime("--slant-range-power=Q: the exponent of r / r_ref must be finite.");
+        mission.SlantCompanion = "--slant-range-power";
+        break;
+      case OPTX_SLANT_WINDOWS:
+        mission.SlantWindows.clear();
+        while (o.has()) mission.SlantWindows.push_back(o.real());
+        if (mission.SlantWindows.empty() || mission.SlantWindows.size() % 2 || mission.SlantWindows.size() > 16)
+          throw Runtime("--slant-windows=T0,T1[,T0,T1...]: one to eight pairs of times in seconds.");
+        for (size_t k = 0; k < mission.SlantWindows.size(); k += 2)
+          if (!std::isfinite(mission.SlantWindows[k]) || !std::isfinite(mission.SlantWindows[k + 1]) ||
+              !(mission.SlantWindows[k + 1] >= mission.SlantWindows[k]))
+            throw Runtime("--slant-windows=T0,T1[,T0,T1...]: every time must be finite and no window's end before its start.");
+        mission.SlantCompanion = "--slant-windows";
+        break;
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }
@@ -645,6 +702,28 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
                     "rounds keep only their moments): out of scope.");
     if (ReportMaskFromKeywords(mission.Reports))
       throw Runtime("--envelope-fit cannot be combined with --reports (the event log's launches run one at a time).");
+  }
+  // the slant stack's errors come from one device's batches, and it keeps the run's batch blocks for itself
+  if (mission.SlantCompanion && !mission.bSlant)
+    throw Runtime(std::string(mission.SlantCompanion) + " needs --slant-stack: it only says how that stack is made.");
+  if (mission.bSlant) {
+    if (mission.JobErrorBatches)
+      throw Runtime("--slant-stack cannot be combined with --job-error-batches: the stack is made where ONE device's batch "
+                    "blocks lie (r3d_run_batched_slant_stack); a job sharded over devices has no slant call.  Use "
+                    "--error-batches=B.");
+    if (!mission.ErrorBatches)
+      throw Runtime("--slant-stack needs --error-batches=B: the standard errors of the stack, the power and the picks are "
+                    "jackknives over the B batches.");
+    if (mission.bLapse || mission.bTTImage || mission.bEnvShape || mission.bEnvFit)
+      throw Runtime(std::string("--slant-stack cannot be combined with ") +
+                    (mission.bLapse ? "--lapse-windows" : mission.bTTImage ? "--ttimage" : mission.bEnvShape ? "--envelope-shape"
+                                                                                                            : "--envelope-fit") +
+                    " in one run (each keeps the run's batch blocks for itself): out of scope.");
+    if (mission.bTarget)
+      throw Runtime("--slant-stack cannot be combined with --target-error (the stack needs one run's batch blocks, the "
+                    "rounds keep only their moments): out of scope.");
+    if (ReportMaskFromKeywords(mission.Reports))
+      throw Runtime("--slant-stack cannot be combined with --reports (the event log's launches run one at a time).");
   }
   // the views and the maps are made from the grid: none of their options means anything without it
   if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile || mission.bScatterMaps))

@@ -114,6 +114,19 @@ struct MissionParams {
   double FitEdge[2] = {3.6, 0.0}, FitWindow[2] = {0.0, std::nan("")}, FitAxes[3] = {1.0, 1.0, 1.0}, FitMaxLagSeconds = 0.0;
   unsigned FitSmooth = 8, FitObsSmooth = 0;
   long FitArray[2] = {0, -1};             // LAST < 0: through the last receiver
+  // --slant-stack=PMIN,PMAX,NP[,RREF[,SMOOTH]]: the slant stack (vespagram) of a linear receiver array over NP slownesses
+  // PMIN .. PMAX (s/km) about the distance RREF (km; default: the mean of the end receivers') -- the stack, the beam power per
+  // slowness in delay windows, and per window the picked slowness and delay -- with jackknife errors from the batches of
+  // --error-batches (include/r3d.h r3d_run_batched_slant_stack), as slantstack.octv.  --slant-array=FIRST,LAST the receivers
+  // (default all), --slant-axes=X,Y,Z the weights of the three trace axes, --slant-energy: energies are stacked, not
+  // amplitudes, --slant-range-power=Q: receiver i times (r_i / r_ref)^Q, --slant-windows=T0,T1[,T0,T1...] the delay windows in
+  // seconds (default: one over the whole trace).
+  bool bSlant = false, bSlantEnergy = false;
+  const char* SlantCompanion = nullptr;   // one of the five that was given (they are refused without --slant-stack)
+  double SlantP[2] = {0.0, 0.0}, SlantRef = std::nan(""), SlantAxes[3] = {1.0, 1.0, 1.0}, SlantRangePower = 0.0;
+  unsigned SlantNP = 0, SlantSmooth = 0;
+  long SlantArray[2] = {0, -1};           // LAST < 0: through the last receiver
+  std::vector<double> SlantWindows;       // T0, T1 pairs
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

@@ -86,6 +86,15 @@ void EnvFitPlan(const Model& model, const r3dh_envfit_opts& rq, double* distance
                 uint32_t* max_lag);
 void OutputEnvFit(const Model& model, const r3dh_envfit_opts& rq, const r3dh_envfit_result& res, std::ostream& out);
 
+// The slant stack of --slant-stack (include/r3d_host.h has the request, the plan, the file's items): SlantRequest fills *rq
+// from the mission (throws if --slant-array names a receiver the model does not have), SlantPlan the array's distances, the
+// grid (r_ref, p0, dp), the shifts by ../beams/r3d_slant_stack.h's rule, the gains and the windows in bins, OutputSlant
+// writes the file's text.
+void SlantRequest(const Model& model, const MissionParams& mission, r3dh_slant_opts* rq);
+void SlantPlan(const Model& model, const r3dh_slant_opts& rq, double* distances, double* grid, int32_t* shift_bin, double* shift_frac,
+               double* gain, uint32_t* windows);
+void OutputSlant(const Model& model, const r3dh_slant_opts& rq, const r3dh_slant_result& res, std::ostream& out);
+
 // precision.octv of --target-error (include/r3d_host.h r3dh_write_precision has the file's items): the target, the
 // selection, what was run and the judge's tables (their rows are batch_plan.hpp's).  Needs no model.  PrecisionRequest
 // fills *spec from the mission (throws if --target-array names a receiver the model does not have).

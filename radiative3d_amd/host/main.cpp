@@ -5,14 +5,15 @@
 // files.  The N-phonon loop itself (Model::RunSimulation, model.cpp:602-633)
 // is one call into the engine's C-ABI.  What a run with --scatter-grid writes afterwards (the grid, its views, its maps)
 // is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches, --lapse-windows, --ttimage,
-// --target-error, --envelope-shape and --envelope-fit run and write (the batched runs, seis_NNN_err.octv, lapse.octv,
-// ttimage.octv, precision.octv, envshape.octv, envfit.octv) is the stage of batch_out.cpp.  This file
+// --target-error, --envelope-shape, --envelope-fit and --slant-stack run and write (the batched runs, seis_NNN_err.octv,
+// lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv, slantstack.octv) is the stage of batch_out.cpp.  This file
 // makes both jobs, has them checked before the node is built, and calls each once to run and once to write.
 //
 // Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B`,
 // `--job-error-batches=N` (error bars of a job on any number of shards), `--lapse-windows` (lapse.octv), `--ttimage`
 // (ttimage.octv), `--target-error` (a run that stops when its error bars are good enough; precision.octv) and
-// `--envelope-shape` (envshape.octv) and `--envelope-fit` (the misfit against observed envelopes; envfit.octv) are accepted
+// `--envelope-shape` (envshape.octv), `--envelope-fit` (the misfit against observed envelopes; envfit.octv) and `--slant-stack`
+// (the vespagram of a receiver array; slantstack.octv) are accepted
 // (the reference seeds from the clock, is single-process, has no event histogram and no error bars, and takes its phonon
 // count from a hand-tuned table); the `--reports` stream is written
 // after the run, grouped by history, where the reference writes its lines as they happen (the engine appends binary
@@ -270,7 +271,15 @@ int main(int argc, char* argv[]) {
               << "--envelope-fit-array=FIRST,LAST (default all)  --envelope-fit-axes=X,Y,Z (default 1,1,1)  --envelope-fit-energy: FILE\n"
               << "holds energies, not amplitudes.  (The names share no prefix rule with --envelope-array / --envelope-axes: options\n"
               << "are matched whole.)  Not in one run with --lapse-windows, --ttimage, --target-error, --envelope-shape,\n"
-              << "--job-error-batches or --reports (out of scope)\n\n";
+              << "--job-error-batches or --reports (out of scope)\n"
+              << "--slant-stack=PMIN,PMAX,NP[,RREF[,SMOOTH]] (with --error-batches; RREF default: the mean of the end receivers'\n"
+              << "distances, SMOOTH 0): the slant stack (vespagram) of a linear receiver array over NP slownesses PMIN .. PMAX in s/km\n"
+              << "-- every receiver's envelope delayed by p (r - RREF) and the array averaged --, the beam power per slowness in delay\n"
+              << "windows and per window the picked slowness and delay, made on the GPU with jackknife standard errors, as\n"
+              << "slantstack.octv;  --slant-array=FIRST,LAST (default all)  --slant-axes=X,Y,Z (default 1,1,1)  --slant-energy: stack\n"
+              << "energies, not amplitudes  --slant-range-power=Q: receiver i times (r_i / RREF)^Q (default 0)\n"
+              << "--slant-windows=T0,T1[,T0,T1...] in seconds, at most eight (default: one over the whole trace).  Not in one run with\n"
+              << "--lapse-windows, --ttimage, --target-error, --envelope-shape, --envelope-fit, --job-error-batches or --reports\n\n";
     return 0;
   }
   // A simulation run makes its tables where it uses them (seconds of host work and GBs of upload

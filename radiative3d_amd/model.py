@@ -403,6 +403,27 @@ class Model:
         return dict(first=int(rq.first), last=int(rq.last), smooth=int(rq.smooth), phase_edge=tuple(rq.phase_edge),
                     window=tuple(rq.window), axes=tuple(rq.axes))
 
+    def slant_plan(self):
+        """What --slant-stack and its companions asked for, planned for the model's array (include/r3d_host.h
+        r3dh_slant_request, r3dh_slant_plan): None without the option, else a dict of first, last, smooth, amplitude, axes,
+        distances [A] (km), r_ref, p0, dp (s/km), shift_bin, shift_frac [M, A], gain [A] and windows [W, 2] (bins)."""
+        rq = _ffi.SlantOpts()
+        rc = self._lib.r3dh_slant_request(self._h, C.byref(rq))
+        if rc < 0:
+            raise RuntimeError("slant_request failed: " + self._lib.r3dh_last_error().decode())
+        if rc == 0:
+            return None
+        A, M, W = int(rq.last) - int(rq.first) + 1, int(rq.n_slowness), max(1, int(rq.n_windows))
+        dist, grid, gain = np.zeros(A), np.zeros(3), np.zeros(A)
+        k, f, win = np.zeros((M, A), dtype=np.int32), np.zeros((M, A)), np.zeros((W, 2), dtype=np.uint32)
+        if self._lib.r3dh_slant_plan(self._h, C.byref(rq), dist.ctypes.data_as(_ffi._dp), grid.ctypes.data_as(_ffi._dp),
+                                     k.ctypes.data_as(C.POINTER(C.c_int32)), f.ctypes.data_as(_ffi._dp),
+                                     gain.ctypes.data_as(_ffi._dp), win.ctypes.data_as(C.POINTER(C.c_uint32))):
+            raise RuntimeError("slant_plan failed: " + self._lib.r3dh_last_error().decode())
+        return dict(first=int(rq.first), last=int(rq.last), smooth=int(rq.smooth), amplitude=int(rq.amplitude), axes=tuple(rq.axes),
+                    distances=dist, r_ref=float(grid[0]), p0=float(grid[1]), dp=float(grid[2]), shift_bin=k, shift_frac=f, gain=gain,
+                    windows=win)
+
     @staticmethod
     def _envshape_opts(request):
         edge, window = request.get("phase_edge", (3.6, 0.0)), request.get("window", (0.0, math.nan))
@@ -865,6 +886,87 @@ def envelope_misfit(batch_energy, bins, observed, first, last, weights, smooth_s
                                  stream)
     if rc:
         raise RuntimeError("r3d_envelope_misfit failed: " + lib.r3d_last_error().decode())
+    return out
+
+
+def slant_shifts(dt, distances, r_ref, p0, dp, n_slowness):
+    """r3d_slant_shifts (host only): the shifts of the slowness grid p0 + m dp (s/km) over receivers at `distances` (km) about
+    r_ref, in bins of dt seconds.  Returns (shift_bin [M, A] int32, shift_frac [M, A] float64 in [0, 1))."""
+    lib = _ffi.hip_lib()
+    r = np.ascontiguousarray(distances, dtype=np.float64).reshape(-1)
+    k = np.zeros((int(n_slowness), r.size), dtype=np.int32)
+    f = np.zeros((int(n_slowness), r.size), dtype=np.float64)
+    if lib.r3d_slant_shifts(float(dt), r.size, r.ctypes.data_as(_ffi._dp), float(r_ref), float(p0), float(dp), int(n_slowness),
+                            k.ctypes.data_as(C.POINTER(C.c_int32)), f.ctypes.data_as(_ffi._dp)):
+        raise ValueError(lib.r3d_last_error().decode())
+    return k, f
+
+
+def slant_spec(n_seismometers, n_bins, first, last, weights, shift_bin_ptr, shift_frac_ptr, gain_ptr, windows_ptr, n_slowness,
+               n_windows, p0=0.0, dp=0.0, smooth=0, amplitude=1):
+    """An r3d_slant_spec (include/r3d.h): the addresses of the int32 [M][A] and float64 [M][A] shifts, the float64 [A] gains
+    and the uint32 [W][2] windows -- on the device for slant_stack, on the host for Engine.run_batched_slant_stack."""
+    w = [float(v) for v in weights]
+    if len(w) != _ffi.R3D_N_ENERGY:
+        raise ValueError("five component weights (X, Y, Z, P, S) are needed")
+    return _ffi.SlantSpec(size=C.sizeof(_ffi.SlantSpec), n_seismometers=int(n_seismometers), n_bins=int(n_bins), first=int(first),
+                          last=int(last), smooth=int(smooth), amplitude=int(amplitude), n_slowness=int(n_slowness),
+                          n_windows=int(n_windows), p0=float(p0), dp=float(dp), d_shift_bin=shift_bin_ptr,
+                          d_shift_frac=shift_frac_ptr, d_gain=gain_ptr, d_windows=windows_ptr,
+                          weight=(C.c_double * _ffi.R3D_N_ENERGY)(*w))
+
+
+def slant_stack(batch_energy, shift_bin, shift_frac, gain, windows, first, last, weights, p0=0.0, dp=0.0, smooth=0, amplitude=1,
+                with_se=None, stream=None):
+    """r3d_slant_stack on torch tensors of one device: batch_energy [B, S, n_bins, 5] float64 are B batch blocks, the array the
+    receivers first .. last (A of them), shift_bin [M, A] int32 and shift_frac [M, A] float64 the shifts of the M slownesses
+    (slant_shifts makes them), gain [A] float64 the receivers' multipliers, windows [W, 2] int32 the delay windows c0, c1 (W may
+    be 0), p0 and dp the slowness grid the picked slowness is expressed in.  Returns a dict of tensors, all WRITTEN: stack [M,
+    n_bins], fold [M, n_bins] (int32), power [W, M], picks [W, 4] (Pmax, p*, tau* in bins, the peak), their _se (with_se;
+    default: B >= 2), bad and bad_shifts [1] (int64).  include/r3d.h has the arithmetic.  Asynchronous on `stream` (a raw
+    hipStream_t; None: torch's current one)."""
+    import torch
+    lib = _ffi.hip_lib()
+    if batch_energy.dim() != 4 or batch_energy.shape[3] != _ffi.R3D_N_ENERGY or batch_energy.dtype != torch.float64:
+        raise ValueError("batch_energy must be float64 [B, S, n_bins, 5]")
+    if not batch_energy.is_cuda or not batch_energy.is_contiguous():
+        raise ValueError("the blocks must be a contiguous tensor on a GPU")
+    B, S, n_bins = (int(v) for v in batch_energy.shape[:3])
+    dev = batch_energy.device
+    A = int(last) - int(first) + 1
+    if A < 1 or last >= S:
+        raise ValueError("the array first .. last must lie within the blocks' seismometers")
+    M = int(shift_bin.shape[0]) if shift_bin.dim() == 2 else 0
+    W = int(windows.shape[0]) if windows is not None else 0
+
+    def on_device(t, shape, what, floating):
+        if tuple(t.shape) != shape or t.device != dev or not t.is_contiguous() or \
+                (t.dtype != torch.float64 if floating else (t.element_size() != 4 or t.dtype.is_floating_point)):
+            raise ValueError(f"{what} must be a contiguous {'float64' if floating else '32-bit integer'} tensor "
+                             f"{list(shape)} on the blocks' GPU")
+    on_device(shift_bin, (M, A), "shift_bin", False)
+    on_device(shift_frac, (M, A), "shift_frac", True)
+    on_device(gain, (A,), "gain", True)
+    if W:
+        on_device(windows, (W, 2), "windows", False)
+    with_se = B >= 2 if with_se is None else with_se
+
+    def f64(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=dev)
+
+    def i64():
+        return torch.zeros(1, dtype=torch.int64, device=dev)
+    out = dict(stack=f64(M, n_bins), stack_se=f64(M, n_bins) if with_se else None,
+               fold=torch.empty((M, n_bins), dtype=torch.int32, device=dev), power=f64(W, M), power_se=f64(W, M) if with_se else None,
+               picks=f64(W, _ffi.R3D_SLANT_N), picks_se=f64(W, _ffi.R3D_SLANT_N) if with_se else None, bad=i64(), bad_shifts=i64())
+    spec = slant_spec(S, n_bins, first, last, weights, shift_bin.data_ptr(), shift_frac.data_ptr(), gain.data_ptr(),
+                      windows.data_ptr() if W else None, M, W, p0, dp, smooth, amplitude)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    ptr = [(v.data_ptr() if v is not None else None) for v in out.values()]
+    rc = lib.r3d_slant_stack(dev.index or 0, B, batch_energy.data_ptr(), C.byref(spec), *ptr, stream)
+    if rc:
+        raise RuntimeError("r3d_slant_stack failed: " + lib.r3d_last_error().decode())
     return out
 
 
@@ -1451,6 +1553,33 @@ class Engine:
         res, ese, cse = _run_batched_to_host(self._lib, "r3d_run_batched_envelope_misfit", self._e, m, n, first_id, seed,
                                              n_batches, None, C.byref(spec), C.byref(out))
         return res, ese, cse, fit
+
+    def run_batched_slant_stack(self, n, n_batches, shift_bin, shift_frac, gain, windows, first, last, weights, p0=0.0, dp=0.0,
+                                smooth=0, amplitude=1, first_id=0, seed=0x5EED):
+        """run_batched that also makes the slant stack of the receivers first .. last where the batch blocks lie (include/r3d.h
+        r3d_run_batched_slant_stack): shift_bin, shift_frac [M, A] (slant_shifts makes them), gain [A] and windows [W, 2] on
+        the host.  Returns (Result, energy_se, counts_se, slant): a dict of stack, stack_se [M, n_bins], fold [M, n_bins]
+        (uint32), power, power_se [W, M], picks, picks_se [W, 4]."""
+        m = self.model
+        A = int(last) - int(first) + 1
+        if A < 1:
+            raise ValueError("the array needs first <= last")
+        k = np.ascontiguousarray(shift_bin, dtype=np.int32)
+        f = np.ascontiguousarray(shift_frac, dtype=np.float64)
+        g = np.ascontiguousarray(gain, dtype=np.float64)
+        w = np.ascontiguousarray(windows, dtype=np.uint32).reshape(-1, 2)
+        M, W = k.shape[0], w.shape[0]
+        if k.shape != (M, A) or f.shape != (M, A) or g.shape != (A,):
+            raise ValueError("shift_bin and shift_frac must be [M, A] and gain [A]")
+        spec = slant_spec(m.n_seismometers, m.n_bins, first, last, weights, k.ctypes.data, f.ctypes.data, g.ctypes.data,
+                          w.ctypes.data if W else None, M, W, p0, dp, smooth, amplitude)
+        got = dict(stack=np.zeros((M, m.n_bins)), stack_se=np.zeros((M, m.n_bins)), fold=np.zeros((M, m.n_bins), dtype=np.uint32),
+                   power=np.zeros((W, M)), power_se=np.zeros((W, M)), picks=np.zeros((W, _ffi.R3D_SLANT_N)),
+                   picks_se=np.zeros((W, _ffi.R3D_SLANT_N)))
+        out = _ffi.SlantResult(size=C.sizeof(_ffi.SlantResult), **{name: v.ctypes.data for name, v in got.items()})
+        res, ese, cse = _run_batched_to_host(self._lib, "r3d_run_batched_slant_stack", self._e, m, n, first_id, seed, n_batches,
+                                             None, C.byref(spec), C.byref(out))
+        return res, ese, cse, got
 
     def run_device(self, n, first_id, seed, d_energy, d_counts, d_scalars, stream=None, carry=None):
         """Asynchronous, device-resident accumulate (pointers are raw device
