@@ -44,7 +44,8 @@ HOST_SRC := $(HOSTDIR)/ecs.cpp $(HOSTDIR)/grid.cpp $(HOSTDIR)/model.cpp \
             $(HOSTDIR)/models_builtin.cpp $(HOSTDIR)/cmdline.cpp $(HOSTDIR)/dataout.cpp \
             $(HOSTDIR)/capi.cpp
 HOST_HDR := $(wildcard $(HOSTDIR)/*.hpp) include/r3d.h include/r3d_host.h radiative3d_amd/stats/r3d_window_sums.h \
-            radiative3d_amd/arrays/r3d_array_image.h $(wildcard radiative3d_amd/shapes/*.h) radiative3d_amd/beams/r3d_slant_stack.h
+            radiative3d_amd/arrays/r3d_array_image.h $(wildcard radiative3d_amd/shapes/*.h) radiative3d_amd/beams/r3d_slant_stack.h \
+            radiative3d_amd/contrasts/r3d_array_contrast.h
 ENGINE_HDR := $(wildcard $(CSRC)/*.h) include/r3d.h
 # The add-ons: what stands beside the engine on its C-ABI, each a directory radiative3d_amd/<name>/ of ONE .hip and
 # its headers, which includes $(COMMON)/r3d_entry.h and include/r3d.h and nothing from csrc/.  A new one is a word here.
@@ -60,15 +61,18 @@ ENGINE_HDR := $(wildcard $(CSRC)/*.h) include/r3d.h
 #          (r3d_envelope_misfit, r3d_run_batched_envelope_misfit)
 #   beams  the slant stack of a receiver array -- the vespagram, the beam power per slowness, the picked slowness and delay per
 #          window -- with jackknife errors (r3d_slant_shifts, r3d_slant_stack, r3d_run_batched_slant_stack)
-ADDONS := stats views maps arrays precision shapes fits beams
+#   contrasts  the contrast of two runs along a receiver array -- per pixel, per window, per region of the array -- with the
+#          two-sample jackknife over both runs' batches (r3d_array_contrast, r3d_run_batched_contrast, r3d_contrast_decibel)
+ADDONS := stats views maps arrays precision shapes fits beams contrasts
 addon_src = $(wildcard radiative3d_amd/$(1)/*.hip)
 # (arrays/ takes the bin energy and the strand constants from stats/r3d_window_sums.h; shapes/ those and the scans, the
 # running maximum and the jackknife from arrays/r3d_array_image.h; fits/ all of that and every header of shapes/: the rows
-# of a receiver with their smoothing rule, r3d_envelope_rows.h, and the shape's arithmetic; beams/ the same headers as fits/)
+# of a receiver with their smoothing rule, r3d_envelope_rows.h, and the shape's arithmetic; beams/ and contrasts/ the same
+# headers as fits/)
 addon_hdr = $(wildcard radiative3d_amd/$(1)/*.h) $(COMMON)/r3d_entry.h include/r3d.h $(if $(filter arrays,$(1)),radiative3d_amd/stats/r3d_window_sums.h) \
             $(if $(filter shapes,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h) \
             $(if $(filter fits,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h $(wildcard radiative3d_amd/shapes/*.h)) \
-            $(if $(filter beams,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h $(wildcard radiative3d_amd/shapes/*.h))
+            $(if $(filter beams contrasts,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h $(wildcard radiative3d_amd/shapes/*.h))
 OBJDIR   := build/obj
 
 # (the default goal is the first target of the file: it has to come before the generated object rules)

@@ -1118,6 +1118,98 @@ int r3d_run_batched_slant_stack(r3d_engine* e, uint64_t n, uint64_t first_id, ui
                                 r3d_result* out, double* energy_se, double* counts_se, const r3d_slant_spec* spec,
                                 r3d_slant_result* res);
 
+/* ---- the contrast of two runs along a receiver array with jackknife errors ----------------
+ * Every product above is made of ONE run.  The studies the run scripts drive end in a comparison of two: a changed model
+ * against its baseline (vis/seisplot/normcurve_compare.m, "Series reduction (dB)") -- how much of the energy behind a phase
+ * edge a change of structure removes, and where along the array.  This makes that comparison where both runs' batch
+ * blocks lie, with the two-sample jackknife over BOTH runs' batches.  radiative3d_amd/contrasts/r3d_array_contrast.h has the
+ * arithmetic:
+ *     ROWS per side and receiver over the whole trace, as r3d_envelope_shape makes its energy rows (weights finite and
+ *       >= 0; scans, never t - e_j); every finished row value times its side's scale (scale[0] the base's, scale[1] the
+ *       test's: one product, one rounding; N_a / N_b where the history counts differ); then `smooth` three-point passes, u.
+ *     PIXEL.  c(ua, ub) = (ub - ua) / (ub + ua), +0.0 where ub + ua is not > 0.  contrast[i][b] = c(ua[b], ub[b]); lit[i] =
+ *       1 where a pixel of the row has a positive denominator.  A receiver the test run does not reach: -1; equal runs: +0.0.
+ *     PIXEL se (both B >= 2): sa the jackknife se (r3d_array_image's) of c(ua_(j), ub), j < Ba, sb that of c(ua, ub_(j)),
+ *       j < Bb; se = sqrt(sa sa + sb sb) -- the runs are independent, the variances add.
+ *     WINDOWS per receiver, bins [b0, b1) of d_bins[A][W][2], summed from the scaled UNSMOOTHED rows by the window sum's
+ *       strands and tree: window[i][w] = (Ea, Eb, rho = Eb / Ea; NaN where Ea is not > 0), window_se = (se Ea, se Eb, the
+ *       two-sample se of Eb / Ea_(j) and Eb_(j) / Ea; NaN as soon as one value is).  A window with b0 > b1 or b1 > n_bins
+ *       is never read through: dead, and counted in bad.
+ *     REGIONS, receiver ranges regions[r] = (i0, i1), inclusive indices INTO THE ARRAY: Na = sum_i gain_i Ea_w[i] in the
+ *       order i from +0.0, Nb likewise, and the same of every leave-one-out sum; region[r][w] = (Na, Nb, rho_R = Nb / Na),
+ *       region_se likewise, region_loo[r][w][Ba + Bb] = Nb / Na_(j), j < Ba, then Nb_(j) / Na, j < Bb.
+ *     The same bits on every run, machine and launch geometry; the header derives the rounding bounds (the pixel's is
+ *       absolute) and states three exact properties (side swap, power-of-two scale, equal batches).
+ *
+ * r3d_contrast_decibel: host only.  dB = 10 log10(rho) and the two-sample jackknife se of 10 log10 of the Ba + Bb
+ * leave-one-out quotients `loo` (region_loo's; NULL: no se); both NaN where rho or a quotient is not positive.
+ * r3d_contrast_gains: host only.  gain[i] = (distances[i] / r_ref)^power; refused: a null pointer, r_ref not finite and
+ * > 0, a power or a gain that is not finite (and > 0).
+ *
+ * r3d_array_contrast: device level, like r3d_slant_stack -- base blocks d_base_energy [Ba][n_seis][n_bins][5] and test blocks
+ * d_test_energy [Bb][n_seis][n_bins][5] on `device`, only read; spec->d_bins [A][W][2] and d_gain [A] on the device.
+ * WRITTEN, every entry by one work-item: d_contrast, d_contrast_se [A][n_bins]; d_lit [A] (u32); d_window, d_window_se
+ * [A][W][3]; d_region, d_region_se [R][W][3]; d_region_loo [R][W][Ba + Bb]; d_bad (one uint64).  Every output but
+ * d_contrast may be NULL, and one that is not asked for is not touched.  One workgroup per receiver; no atomics, fixed
+ * order, 64-bit offsets, capped grids; every block bin is read once per side; the rows pass through scratch taken from and
+ * returned to the stream's memory pool.  Asynchronous on `stream`.  REFUSED (non-zero, r3d_last_error, nothing enqueued, no
+ * buffer touched; all checked before any HIP call): a null blocks, spec or contrast pointer, a size mismatch, either B == 0
+ * or > 64, n_bins == 0, last < first, last >= n_seismometers, a weight that is negative or not finite, a scale that is not
+ * finite and > 0, smooth > R3D_ENVELOPE_MAX_SMOOTH, n_windows > R3D_CONTRAST_MAX_WINDOWS, n_regions >
+ * R3D_CONTRAST_MAX_REGIONS, windows without bins, regions without gains or without a window, a region reversed or outside
+ * the array, an se array or d_region_loo with either B < 2.
+ *
+ * r3d_run_batched_contrast: r3d_run_batched of `base` (n_base histories from first_id under seed_base in base_batches
+ * batches) and then of `test`, one after the other, each with r3d_run_batched's refusals, totals ADDED into out_base /
+ * out_test and the four se arrays WRITTEN (each may be NULL); base == test is allowed.  Both keep their batch blocks on the
+ * device, the contrast is made there and only the arrays of *res come back, all WRITTEN.  For THIS call the spec's d_bins
+ * and d_gain are HOST arrays, checked before anything runs: a window with b0 > b1 or b1 > n_bins and a gain that is not
+ * finite and > 0 are refused, as are engines on different devices, two models whose n_seismometers x n_bins differ from
+ * each other or from the spec's (the bin width is not the engine's to tell: Engine.run_batched_contrast and ./main compare
+ * it), a null res or one of another size, a null contrast.  A refusal touches nothing.  Out of scope: a job sharded over
+ * several devices, combining the contrast with another batched product in one run, more than two runs, and writing the
+ * test run's traces.                                                                                                      */
+#define R3D_CONTRAST_MAX_WINDOWS 8
+#define R3D_CONTRAST_MAX_REGIONS 8
+#define R3D_CONTRAST_N 3
+typedef struct r3d_contrast_spec {
+  uint32_t size;                    /* sizeof(r3d_contrast_spec): a mismatch is refused        */
+  uint32_t n_seismometers, n_bins;
+  uint32_t first, last;             /* the array: seismometers first .. last                   */
+  uint32_t smooth;                  /* three-point passes, 0 .. R3D_ENVELOPE_MAX_SMOOTH        */
+  uint32_t n_windows;               /* W per receiver, 0 .. R3D_CONTRAST_MAX_WINDOWS           */
+  uint32_t n_regions;               /* R, 0 .. R3D_CONTRAST_MAX_REGIONS                        */
+  uint32_t regions[R3D_CONTRAST_MAX_REGIONS][2];   /* i0, i1: array indices, inclusive         */
+  const uint32_t* d_bins;           /* [A][W][2] b0, b1; device (the run: host)                */
+  const double*   d_gain;           /* [A] finite, > 0; device (the run: host)                 */
+  double   weight[R3D_N_ENERGY];
+  double   scale[2];                /* base, test: finite, > 0                                 */
+} r3d_contrast_spec;
+typedef struct r3d_contrast_result {
+  uint32_t size;                    /* sizeof(r3d_contrast_result)                             */
+  uint32_t pad_;
+  double*   contrast;               /* [A][n_bins]                                             */
+  double*   contrast_se;            /* [A][n_bins]      may be NULL                            */
+  uint32_t* lit;                    /* [A]              may be NULL                            */
+  double*   window;                 /* [A][W][3]        may be NULL                            */
+  double*   window_se;              /* [A][W][3]        may be NULL                            */
+  double*   region;                 /* [R][W][3]        may be NULL                            */
+  double*   region_se;              /* [R][W][3]        may be NULL                            */
+  double*   region_loo;             /* [R][W][Ba + Bb]  may be NULL                            */
+} r3d_contrast_result;
+int r3d_contrast_decibel(uint32_t n_base, uint32_t n_test, double rho, const double* loo, double* decibel,
+                         double* decibel_se);
+int r3d_contrast_gains(uint32_t n_array, const double* distances, double r_ref, double power, double* gain);
+int r3d_array_contrast(int device, uint32_t n_base, const double* d_base_energy, uint32_t n_test,
+                       const double* d_test_energy, const r3d_contrast_spec* spec, double* d_contrast,
+                       double* d_contrast_se, uint32_t* d_lit, double* d_window, double* d_window_se, double* d_region,
+                       double* d_region_se, double* d_region_loo, uint64_t* d_bad, void* stream);
+int r3d_run_batched_contrast(r3d_engine* base, r3d_engine* test, uint64_t n_base, uint64_t n_test, uint64_t first_id,
+                             uint64_t seed_base, uint64_t seed_test, uint32_t base_batches, uint32_t test_batches,
+                             r3d_result* out_base, r3d_result* out_test, double* base_energy_se, double* base_counts_se,
+                             double* test_energy_se, double* test_counts_se, const r3d_contrast_spec* spec,
+                             r3d_contrast_result* res);
+
 /* ---- run to a target standard error: rounds of batches, judged on the device ------------
  * How many histories a run needs is asked before every run; this call answers it by running in rounds and looking at the
  * error bars where they lie.  radiative3d_amd/precision/r3d_precision.h has the criterion's arithmetic, built by the host too.

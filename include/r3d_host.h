@@ -361,6 +361,43 @@ int r3dh_slant_plan(const r3dh_model* m, const r3dh_slant_opts* rq, double* dist
                     double* shift_frac, double* gain, uint32_t* windows);
 int r3dh_write_slant(const r3dh_model* m, const r3dh_slant_opts* rq, const r3dh_slant_result* res, const char* path);
 
+/* --array-contrast[=SMOOTH] --contrast-model-args=a,b,... [--contrast-array=FIRST,LAST] [--contrast-axes=X,Y,Z]
+ * [--contrast-windows=V1,V2[,V1,V2...]] [--contrast-regions=R0,R1[,...]] [--contrast-range-power=Q] [--contrast-seed=S]
+ * [--contrast-num-phonons=N] in the model's arguments (the first two refused without each other, the others without the
+ * first; the first without --error-batches, on more than one shard, and with --job-error-batches, --lapse-windows, --ttimage,
+ * --target-error, --envelope-shape, --envelope-fit, --slant-stack or --reports; regions without windows): the contrast of
+ * two runs along a receiver array (r3d.h r3d_run_batched_contrast) -- the arguments' own model is the base, the test model
+ * the same with --model-args replaced by --contrast-model-args.  SMOOTH three-point passes (default 8); windows as
+ * group-velocity pairs V1 > V2 (km/s); regions as distance ranges (km); each receiver times (r_i / r_ref)^Q in a region's
+ * sums, r_ref the mean of the end receivers' distances; the test run's seed defaults to --seed + 1, its histories to the
+ * base's.
+ * r3dh_contrast_request: returns 1 and fills *rq when the contrast was asked for, 0 otherwise; -1 (r3dh_last_error) if
+ * --contrast-array's LAST is not a seismometer of the model.  rq->test_args points into the handle.
+ * r3dh_contrast_plan: for the A = last - first + 1 receivers, distances [A] as r3dh_lapse_plan gives them (range_km); bins
+ * [A][W][2] and clipped [A][W]: receiver i's window [r_i / V1, r_i / V2] by r3d.h r3d_window_bins' rule (v = V1, t0 = 0, o = 0,
+ * e = r_i / V2 - r_i / V1); region_receivers [R][2]: the smallest and the largest array index whose distance lies in [R0, R1];
+ * gain [A] = (r_i / r_ref)^Q (r3d.h r3d_contrast_gains), *r_ref.  Non-zero: a region that holds no receiver, a reference
+ * distance or a gain that is not finite and positive, what the bin rule refuses.                                         */
+typedef struct r3dh_contrast_opts {
+  uint32_t size;                 /* sizeof(r3dh_contrast_opts)                                   */
+  uint32_t first, last;          /* the array: seismometers first .. last                        */
+  uint32_t smooth;               /* three-point passes, 0 .. 64                                  */
+  uint32_t n_windows;            /* W, 0 .. R3D_CONTRAST_MAX_WINDOWS                             */
+  uint32_t n_regions;            /* R, 0 .. R3D_CONTRAST_MAX_REGIONS                             */
+  uint32_t n_test_args;
+  uint32_t pad_;
+  uint64_t seed;                 /* the test run's                                               */
+  uint64_t num_phonons;          /* the test run's                                               */
+  double   range_power;          /* Q                                                            */
+  double   axes[3];              /* weights of the trace's X, Y, Z                               */
+  double   velocities[R3D_CONTRAST_MAX_WINDOWS][2];   /* V1 > V2, km/s                           */
+  double   regions[R3D_CONTRAST_MAX_REGIONS][2];      /* R0 <= R1, km                            */
+  const double* test_args;       /* [n_test_args] --contrast-model-args                          */
+} r3dh_contrast_opts;
+int r3dh_contrast_request(const r3dh_model* m, r3dh_contrast_opts* rq);
+int r3dh_contrast_plan(const r3dh_model* m, const r3dh_contrast_opts* rq, double* distances, uint32_t* bins, int32_t* clipped,
+                       uint32_t* region_receivers, double* gain, double* r_ref);
+
 /* --target-error=REL[,COVERAGE[,MINCOUNT[,ROUNDS]]] [--target-array=FIRST,LAST] [--target-components=LETTERS] in the
  * model's arguments (the last two refused without the first; the first without --error-batches, with --job-error-batches,
  * --lapse-windows, --ttimage or --reports, on more than one shard, and with a --num-phonons that is no multiple of ROUNDS

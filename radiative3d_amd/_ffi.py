@@ -188,6 +188,24 @@ class SlantResult(C.Structure):
                 ("picks_se", C.c_void_p)]
 
 
+R3D_CONTRAST_MAX_WINDOWS, R3D_CONTRAST_MAX_REGIONS, R3D_CONTRAST_N = 8, 8, 3
+
+
+class ContrastSpec(C.Structure):
+    """include/r3d.h r3d_contrast_spec"""
+    _fields_ = [("size", C.c_uint32), ("n_seismometers", C.c_uint32), ("n_bins", C.c_uint32), ("first", C.c_uint32),
+                ("last", C.c_uint32), ("smooth", C.c_uint32), ("n_windows", C.c_uint32), ("n_regions", C.c_uint32),
+                ("regions", (C.c_uint32 * 2) * R3D_CONTRAST_MAX_REGIONS), ("d_bins", C.c_void_p), ("d_gain", C.c_void_p),
+                ("weight", C.c_double * R3D_N_ENERGY), ("scale", C.c_double * 2)]
+
+
+class ContrastResult(C.Structure):
+    """include/r3d.h r3d_contrast_result"""
+    _fields_ = [("size", C.c_uint32), ("pad_", C.c_uint32), ("contrast", C.c_void_p), ("contrast_se", C.c_void_p),
+                ("lit", C.c_void_p), ("window", C.c_void_p), ("window_se", C.c_void_p), ("region", C.c_void_p),
+                ("region_se", C.c_void_p), ("region_loo", C.c_void_p)]
+
+
 R3D_PRECISION_MAX_ROUNDS = 64
 R3D_PRECISION_DEFAULT_MASK = 0x18   # P | S: an axis normal to the motion holds rounding noise and would never be met
 
@@ -250,6 +268,14 @@ class SlantOpts(C.Structure):
                 ("amplitude", C.c_uint32), ("n_slowness", C.c_uint32), ("n_windows", C.c_uint32), ("pad_", C.c_uint32),
                 ("p_min", C.c_double), ("p_max", C.c_double), ("r_ref", C.c_double), ("range_power", C.c_double),
                 ("axes", C.c_double * 3), ("windows", (C.c_double * 2) * 8)]
+
+
+class ContrastOpts(C.Structure):
+    """include/r3d_host.h r3dh_contrast_opts"""
+    _fields_ = [("size", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("smooth", C.c_uint32),
+                ("n_windows", C.c_uint32), ("n_regions", C.c_uint32), ("n_test_args", C.c_uint32), ("pad_", C.c_uint32),
+                ("seed", C.c_uint64), ("num_phonons", C.c_uint64), ("range_power", C.c_double), ("axes", C.c_double * 3),
+                ("velocities", (C.c_double * 2) * 8), ("regions", (C.c_double * 2) * 8), ("test_args", C.POINTER(C.c_double))]
 
 
 class EnvShapeResult(C.Structure):
@@ -402,6 +428,11 @@ def host_lib():
         L.r3dh_slant_plan.restype = C.c_int
         L.r3dh_slant_plan.argtypes = [C.c_void_p, C.POINTER(SlantOpts), _dp, _dp, C.POINTER(C.c_int32), _dp, _dp,
                                       C.POINTER(C.c_uint32)]
+        L.r3dh_contrast_request.restype = C.c_int
+        L.r3dh_contrast_request.argtypes = [C.c_void_p, C.POINTER(ContrastOpts)]
+        L.r3dh_contrast_plan.restype = C.c_int
+        L.r3dh_contrast_plan.argtypes = [C.c_void_p, C.POINTER(ContrastOpts), _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_uint32), _dp, _dp]
         L.r3dh_observed_to_bins.restype = C.c_int
         L.r3dh_observed_to_bins.argtypes = [_dp, C.c_uint32, C.c_uint32] + [C.c_double] * 4 + [C.c_uint32, _dp]
         L.r3dh_read_octave.restype = C.c_int
@@ -630,6 +661,16 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_run_batched_slant_stack.restype = C.c_int
         L.r3d_run_batched_slant_stack.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                                   C.POINTER(Result), _dp, _dp, C.POINTER(SlantSpec), C.POINTER(SlantResult)]
+        L.r3d_contrast_decibel.restype = C.c_int
+        L.r3d_contrast_decibel.argtypes = [C.c_uint32, C.c_uint32, C.c_double, _dp, _dp, _dp]
+        L.r3d_contrast_gains.restype = C.c_int
+        L.r3d_contrast_gains.argtypes = [C.c_uint32, _dp, C.c_double, C.c_double, _dp]
+        L.r3d_array_contrast.restype = C.c_int
+        L.r3d_array_contrast.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(ContrastSpec)] + \
+            [C.c_void_p] * 10
+        L.r3d_run_batched_contrast.restype = C.c_int
+        L.r3d_run_batched_contrast.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint64] * 5 + [C.c_uint32] * 2 + \
+            [C.POINTER(Result)] * 2 + [_dp] * 4 + [C.POINTER(ContrastSpec), C.POINTER(ContrastResult)]
         L.r3d_run_batched_windows.restype = C.c_int
         L.r3d_run_batched_windows.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(Result),
                                               _dp, _dp, C.POINTER(WindowSpec), _dp, C.POINTER(C.c_uint64), _dp, _dp]

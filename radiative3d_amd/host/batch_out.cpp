@@ -3,6 +3,7 @@
 
 #include <fstream>
 #include <iostream>
+#include <sstream>
 
 #include "batch_plan.hpp"
 #include "dataout.hpp"
@@ -127,6 +128,46 @@ void run_slant(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint
     throw Runtime(r3d_last_error());
 }
 
+// --array-contrast: the base run on the node's engine and the test run on a second node of one shard on the same device, both
+// batched with their batch blocks kept there, and the contrast made where they lie (include/r3d.h r3d_run_batched_contrast).
+// The test run's totals are not written: out of scope.
+void run_contrast(const BatchJob& job, const r3d_model_desc& d, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total,
+                  BatchProducts& p) {
+  const ContrastJob& c = job.contrast;
+  const r3dh_contrast_opts& rq = c.opts;
+  const size_t A = (size_t)rq.last - rq.first + 1, W = rq.n_windows, R = rq.n_regions, px = A * d.params.n_bins;
+  struct Held {
+    r3d_node* node = nullptr;
+    ~Held() {
+      if (node) r3d_node_destroy(node);
+    }
+  } test;
+  int device = c.device;
+  if (!(test.node = r3d_node_create(&c.test_model->Desc(), &device, 1))) throw Runtime(r3d_last_error());
+  r3d_contrast_spec spec{};
+  spec.size = sizeof spec, spec.n_seismometers = (uint32_t)d.n_seismometers, spec.n_bins = d.params.n_bins;
+  spec.first = rq.first, spec.last = rq.last, spec.smooth = rq.smooth, spec.n_windows = rq.n_windows, spec.n_regions = rq.n_regions;
+  for (size_t r = 0; r < R; r++) spec.regions[r][0] = c.regions[2 * r], spec.regions[r][1] = c.regions[2 * r + 1];
+  spec.d_bins = c.bins.data(), spec.d_gain = c.gain.data();   // (for this call: on the host)
+  for (int k = 0; k < 3; k++) spec.weight[k] = rq.axes[k];
+  spec.scale[0] = 1.0, spec.scale[1] = (double)n / (double)rq.num_phonons;
+  p.contrast.assign(px, 0.0), p.contrast_se.assign(px, 0.0), p.lit.assign(A, 0), p.n_phonons = n;
+  p.contrast_window.assign(A * W * R3D_CONTRAST_N, 0.0), p.contrast_window_se.assign(A * W * R3D_CONTRAST_N, 0.0);
+  p.contrast_region.assign(R * W * R3D_CONTRAST_N, 0.0), p.contrast_region_se.assign(R * W * R3D_CONTRAST_N, 0.0);
+  p.contrast_region_loo.assign(R * W * 2 * (size_t)job.batches, 0.0);
+  r3d_contrast_result res{};
+  res.size = sizeof res, res.contrast = p.contrast.data(), res.contrast_se = p.contrast_se.data(), res.lit = p.lit.data();
+  res.window = p.contrast_window.data(), res.window_se = p.contrast_window_se.data(), res.region = p.contrast_region.data();
+  res.region_se = p.contrast_region_se.data(), res.region_loo = p.contrast_region_loo.data();
+  std::vector<double> test_energy(p.energy_se.size(), 0.0);
+  std::vector<uint64_t> test_counts(p.counts_se.size(), 0);
+  r3d_result test_total{};
+  test_total.energy = test_energy.data(), test_total.counts = test_counts.data();
+  if (r3d_run_batched_contrast(e, r3d_node_engine(test.node, 0), n, rq.num_phonons, 0, seed, rq.seed, job.batches, job.batches, &total,
+                               &test_total, p.energy_se.data(), p.counts_se.data(), nullptr, nullptr, &spec, &res))
+    throw Runtime(r3d_last_error());
+}
+
 // --target-error: --num-phonons is the cap, run in rounds of the job's batches each and judged on the device after
 // every round (include/r3d.h r3d_run_to_precision); one line per round, and one that says whether the target was met.
 void run_precision(const BatchJob& job, r3d_engine* e, uint64_t n, uint64_t seed, r3d_result& total, BatchProducts& p) {
@@ -149,13 +190,13 @@ void run_precision(const BatchJob& job, r3d_engine* e, uint64_t n, uint64_t seed
 
 }  // namespace
 
-BatchJob make_batch_job(const MissionParams& mission, const Model& model) {
+BatchJob make_batch_job(const MissionParams& mission, const Model& model, const ModelParams& par) {
   BatchJob job;
   if (!mission.bRunSim || !(mission.ErrorBatches || mission.JobErrorBatches)) return job;
   job.dir = mission.OutputDir, job.batches = mission.ErrorBatches ? mission.ErrorBatches : mission.JobErrorBatches;
   job.kind = !mission.ErrorBatches ? BatchJob::JOB_ERRORS : mission.bLapse ? BatchJob::LAPSE : mission.bTTImage ? BatchJob::IMAGE
              : mission.bTarget ? BatchJob::PRECISION : mission.bEnvShape ? BatchJob::SHAPE : mission.bEnvFit ? BatchJob::FIT
-             : mission.bSlant ? BatchJob::SLANT : BatchJob::ERRORS;
+             : mission.bSlant ? BatchJob::SLANT : mission.bContrast ? BatchJob::CONTRAST : BatchJob::ERRORS;
   if (job.kind == BatchJob::PRECISION) {
     PrecisionRequest(model, mission, &job.precision);
     job.rounds = mission.TargetRounds;
@@ -188,6 +229,24 @@ BatchJob make_batch_job(const MissionParams& mission, const Model& model) {
     job.slant_windows.assign(2 * (size_t)(job.slant.n_windows ? job.slant.n_windows : 1), 0);
     SlantPlan(model, job.slant, job.slant_distances.data(), job.slant_grid, job.slant_bin.data(), job.slant_frac.data(),
               job.slant_gain.data(), job.slant_windows.data());
+  } else if (job.kind == BatchJob::CONTRAST) {
+    ContrastJob& c = job.contrast;
+    ContrastRequest(model, mission, &c.opts);
+    const size_t A = (size_t)c.opts.last - c.opts.first + 1, W = c.opts.n_windows;
+    c.distances.assign(A, 0.0), c.gain.assign(A, 0.0), c.bins.assign(2 * A * W, 0), c.clipped.assign(A * W, 0);
+    c.regions.assign(2 * (size_t)c.opts.n_regions, 0);
+    ContrastPlan(model, c.opts, c.distances.data(), c.bins.data(), c.clipped.data(), c.regions.data(), c.gain.data(), &c.r_ref);
+    c.base_args = par.CompiledArgs, c.device = mission.Devices.empty() ? 0 : mission.Devices[0], c.seed = mission.Seed;
+    // the test model: the same parameters with the compiled model's arguments replaced, built on the host like the base
+    ModelParams test = par;
+    test.CompiledArgs = mission.ContrastArgs;
+    std::ostringstream log;
+    c.test_model = std::make_shared<Model>(test, &log);
+    const r3d_model_desc &a = model.Desc(), &b = c.test_model->Desc();
+    if (a.n_seismometers != b.n_seismometers || a.params.n_bins != b.params.n_bins || a.params.time_per_bin != b.params.time_per_bin)
+      throw Runtime("--contrast-model-args: the test model's seismometers or bins differ from the base's (" +
+                    std::to_string(b.n_seismometers) + " receivers of " + std::to_string(b.params.n_bins) + " bins against " +
+                    std::to_string(a.n_seismometers) + " of " + std::to_string(a.params.n_bins) + ")");
   }
   return job;
 }
@@ -218,6 +277,7 @@ BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& d, r3d_no
   else if (job.kind == BatchJob::SHAPE) run_shape(job, d, e, n, seed, total, p);
   else if (job.kind == BatchJob::FIT) run_fit(job, d, e, n, seed, total, p);
   else if (job.kind == BatchJob::SLANT) run_slant(job, d, e, n, seed, total, p);
+  else if (job.kind == BatchJob::CONTRAST) run_contrast(job, d, e, n, seed, total, p);
   else if (shards ? r3d_node_run_batched(node, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data())
                   : r3d_run_batched(e, n, 0, seed, job.batches, &total, p.energy_se.data(), p.counts_se.data()))
     throw Runtime(r3d_last_error());
@@ -242,15 +302,26 @@ void write_batch_outputs(const BatchJob& job, const Model& model, const BatchPro
   }
   OutputSeismometerErrors(model, p.energy_se.data(), p.counts_se.data(), job.batches, job.dir);
   if (job.kind != BatchJob::LAPSE && job.kind != BatchJob::IMAGE && job.kind != BatchJob::SHAPE && job.kind != BatchJob::FIT &&
-      job.kind != BatchJob::SLANT)
+      job.kind != BatchJob::SLANT && job.kind != BatchJob::CONTRAST)
     return;
   const std::string fn = output_path(job.dir, job.kind == BatchJob::LAPSE   ? "lapse.octv"
                                               : job.kind == BatchJob::IMAGE ? "ttimage.octv"
                                               : job.kind == BatchJob::SHAPE ? "envshape.octv"
                                               : job.kind == BatchJob::SLANT ? "slantstack.octv"
+                                              : job.kind == BatchJob::CONTRAST ? "contrast.octv"
                                                                             : "envfit.octv");
   std::ofstream f(fn.c_str());
-  if (job.kind == BatchJob::SLANT) {
+  if (job.kind == BatchJob::CONTRAST) {
+    const ContrastJob& c = job.contrast;
+    ContrastFile res;
+    res.batches[0] = res.batches[1] = job.batches, res.phonons[0] = p.n_phonons, res.phonons[1] = c.opts.num_phonons;
+    res.seeds[0] = c.seed, res.seeds[1] = c.opts.seed, res.base_args = &c.base_args, res.r_ref = c.r_ref;
+    res.distances = c.distances.data(), res.bins = c.bins.data(), res.region_receivers = c.regions.data();
+    res.contrast = p.contrast.data(), res.contrast_se = p.contrast_se.data(), res.lit = p.lit.data();
+    res.window = p.contrast_window.data(), res.window_se = p.contrast_window_se.data(), res.region = p.contrast_region.data();
+    res.region_se = p.contrast_region_se.data(), res.region_loo = p.contrast_region_loo.data();
+    OutputContrast(model, c.opts, res, f);
+  } else if (job.kind == BatchJob::SLANT) {
     r3dh_slant_result res{};
     res.size = sizeof res, res.n_batches = job.batches, res.n_windows = (uint32_t)(job.slant_windows.size() / 2), res.n_phonons = p.n_phonons;
     for (int k = 0; k < 3; k++) res.grid[k] = job.slant_grid[k];

@@ -1,11 +1,13 @@
 // batch_out.hpp -- the batched-run stage of ./main: what --error-batches, --job-error-batches, --lapse-windows, --ttimage,
-// --target-error, --envelope-shape, --envelope-fit and --slant-stack run in place of the plain run, and what they write after
-// it (seis_NNN_err.octv, lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv, slantstack.octv).
+// --target-error, --envelope-shape, --envelope-fit, --slant-stack and --array-contrast run in place of the plain run, and what
+// they write after it (seis_NNN_err.octv, lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv, slantstack.octv,
+// contrast.octv).
 // Compiled into ./main beside main.cpp (it calls r3d_run_batched* and r3d_node_run_batched of the engine's library, so
 // it is no part of libr3d_host.so); its row arithmetic is batch_plan.hpp.
 #ifndef R3DH_BATCH_OUT_HPP_
 #define R3DH_BATCH_OUT_HPP_
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -17,11 +19,23 @@
 // A file of the run: `name` under --output-dir ("" = the current directory).
 inline std::string output_path(const std::string& dir, const std::string& name) { return dir.empty() ? name : dir + "/" + name; }
 
+struct ContrastJob {
+  r3dh_contrast_opts opts{};       // (opts.test_args points into the mission the job was made from)
+  std::vector<double> distances, gain;
+  std::vector<uint32_t> bins, regions;
+  std::vector<int32_t> clipped;
+  double r_ref = 0;
+  std::shared_ptr<Model> test_model;
+  std::vector<Real> base_args;
+  int device = 0;
+  unsigned long seed = 0;          // the base run's
+};
+
 // What the options ask for, and where it goes.
 struct BatchJob {
   // ERRORS: --error-batches alone; LAPSE, IMAGE, PRECISION, SHAPE, FIT: with --lapse-windows, --ttimage, --target-error,
-  // --envelope-shape, --envelope-fit; SLANT: with --slant-stack; JOB_ERRORS: --job-error-batches
-  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION, SHAPE, FIT, SLANT } kind = NONE;
+  // --envelope-shape, --envelope-fit; SLANT: with --slant-stack; CONTRAST: with --array-contrast; JOB_ERRORS: --job-error-batches
+  enum Kind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION, SHAPE, FIT, SLANT, CONTRAST } kind = NONE;
   unsigned batches = 0;   // (PRECISION: of a round)
   std::string dir;   // --output-dir
   // LAPSE: the request and the array's plan, [S] receivers (include/r3d_host.h r3dh_lapse_plan)
@@ -52,6 +66,10 @@ struct BatchJob {
   std::vector<int32_t> slant_bin;
   std::vector<uint32_t> slant_windows;
   double slant_grid[3] = {0, 0, 0};
+  // CONTRAST: the request and the array's plan (include/r3d_host.h r3dh_contrast_plan): distances and gains [A], windows
+  // [A][W][2] in bins with their clipped flags, regions [R][2] as array indices, r_ref; the TEST model (the base's parameters
+  // with the compiled model's arguments replaced), the base's own arguments for the file, the device both runs use, the seed
+  ContrastJob contrast;
 };
 
 // What a batched run hands back beside its totals: every bin's standard error, then the kind's own arrays (the shapes
@@ -81,12 +99,15 @@ struct BatchProducts {
   std::vector<double> stack, stack_se, power, power_se, picks, picks_se;
   std::vector<uint32_t> fold;
   uint64_t n_phonons = 0;
+  // CONTRAST (its lit: IMAGE's; n_phonons: the base run's)
+  std::vector<double> contrast, contrast_se, contrast_window, contrast_window_se, contrast_region, contrast_region_se, contrast_region_loo;
 };
 
 // The job of a simulation run (`kind` stays NONE without one of the options).  The model is needed for the arrays:
 // throws what LapseRequest / LapsePlan / TTImageRequest / TTImagePlan / EnvShapeRequest / EnvShapePlan / EnvFitRequest /
-// EnvFitPlan / SlantRequest / SlantPlan (dataout.hpp) throw.
-BatchJob make_batch_job(const MissionParams& mission, const Model& model);
+// EnvFitPlan / SlantRequest / SlantPlan / ContrastRequest / ContrastPlan (dataout.hpp) throw.  `par`: what the model was built from
+// -- --array-contrast builds its test model from it here, on the host, and refuses one whose seismometers or bins differ.
+BatchJob make_batch_job(const MissionParams& mission, const Model& model, const ModelParams& par);
 
 // What --error-batches cannot be combined with, told BEFORE the node is built.  Throws Runtime.
 void check_batch_job(const BatchJob& job, size_t n_shards, uint32_t report_mask);
@@ -97,8 +118,8 @@ void check_batch_job(const BatchJob& job, size_t n_shards, uint32_t report_mask)
 BatchProducts run_batch_job(const BatchJob& job, const r3d_model_desc& model, r3d_node* node, uint64_t n, uint64_t seed,
                             r3d_result& total);
 
-// seis_NNN_err.octv, then lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv or slantstack.octv, under the
-// job's directory.
+// seis_NNN_err.octv, then lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv, slantstack.octv or
+// contrast.octv, under the job's directory.
 // Throws Runtime.
 void write_batch_outputs(const BatchJob& job, const Model& model, const BatchProducts& products);
 

@@ -320,6 +320,32 @@ int r3dh_write_slant(const r3dh_model* m, const r3dh_slant_opts* rq, const r3dh_
   return 1;
 }
 
+int r3dh_contrast_request(const r3dh_model* m, r3dh_contrast_opts* rq) {
+  if (!m || !m->mission.bContrast) return 0;
+  if (!rq) return 1;
+  try {
+    ContrastRequest(*m->model, m->mission, rq);
+    return 1;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return -1;
+}
+
+int r3dh_contrast_plan(const r3dh_model* m, const r3dh_contrast_opts* rq, double* distances, uint32_t* bins, int32_t* clipped,
+                       uint32_t* region_receivers, double* gain, double* r_ref) {
+  if (!m || !rq || !distances || !gain || !r_ref || (rq->n_windows && (!bins || !clipped)) || (rq->n_regions && !region_receivers))
+    return g_error = "r3dh_contrast_plan: null argument", 1;
+  try {
+    // (through the global coordinate system, as r3dh_lapse_plan)
+    ContrastPlan(*m->model, *rq, distances, bins, clipped, region_receivers, gain, r_ref);
+    return 0;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return 1;
+}
+
 int r3dh_observed_to_bins(const double* samples, uint32_t n_samples, uint32_t stride, double t0, double t1, double t_begin,
                           double t_end, uint32_t n_bins, double* out) {
   if (ObservedToBins(samples, n_samples, stride, t0, t1, t_begin, t_end, n_bins, out)) return 0;

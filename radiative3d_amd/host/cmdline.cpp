@@ -25,7 +25,9 @@ enum OptID {
   OPTX_TARGET, OPTX_TARGET_ARRAY, OPTX_TARGET_COMPONENTS,
   OPTX_ENVSHAPE, OPTX_ENVSHAPE_ARRAY, OPTX_ENVSHAPE_AXES,
   OPTX_ENVFIT, OPTX_ENVFIT_ARRAY, OPTX_ENVFIT_AXES, OPTX_ENVFIT_ENERGY,
-  OPTX_SLANT, OPTX_SLANT_ARRAY, OPTX_SLANT_AXES, OPTX_SLANT_ENERGY, OPTX_SLANT_RANGEPOWER, OPTX_SLANT_WINDOWS
+  OPTX_SLANT, OPTX_SLANT_ARRAY, OPTX_SLANT_AXES, OPTX_SLANT_ENERGY, OPTX_SLANT_RANGEPOWER, OPTX_SLANT_WINDOWS,
+  OPTX_CONTRAST, OPTX_CONTRAST_ARGS, OPTX_CONTRAST_ARRAY, OPTX_CONTRAST_AXES, OPTX_CONTRAST_WINDOWS, OPTX_CONTRAST_REGIONS,
+  OPTX_CONTRAST_RANGEPOWER, OPTX_CONTRAST_SEED, OPTX_CONTRAST_NUMBER
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -69,7 +71,11 @@ const std::map<std::string, OptID>& option_table() {
       {"--envelope-fit", OPTX_ENVFIT}, {"--envelope-fit-array", OPTX_ENVFIT_ARRAY}, {"--envelope-fit-axes", OPTX_ENVFIT_AXES},
       {"--envelope-fit-energy", OPTX_ENVFIT_ENERGY},
       {"--slant-stack", OPTX_SLANT}, {"--slant-array", OPTX_SLANT_ARRAY}, {"--slant-axes", OPTX_SLANT_AXES},
-      {"--slant-energy", OPTX_SLANT_ENERGY}, {"--slant-range-power", OPTX_SLANT_RANGEPOWER}, {"--slant-windows", OPTX_SLANT_WINDOWS}};
+      {"--slant-energy", OPTX_SLANT_ENERGY}, {"--slant-range-power", OPTX_SLANT_RANGEPOWER}, {"--slant-windows", OPTX_SLANT_WINDOWS},
+      {"--array-contrast", OPTX_CONTRAST}, {"--contrast-model-args", OPTX_CONTRAST_ARGS}, {"--contrast-array", OPTX_CONTRAST_ARRAY},
+      {"--contrast-axes", OPTX_CONTRAST_AXES}, {"--contrast-windows", OPTX_CONTRAST_WINDOWS},
+      {"--contrast-regions", OPTX_CONTRAST_REGIONS}, {"--contrast-range-power", OPTX_CONTRAST_RANGEPOWER},
+      {"--contrast-seed", OPTX_CONTRAST_SEED}, {"--contrast-num-phonons", OPTX_CONTRAST_NUMBER}};
   return t;
 }
 
@@ -590,6 +596,71 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
             throw Runtime("--slant-windows=T0,T1[,T0,T1...]: every time must be finite and no window's end before its start.");
         mission.SlantCompanion = "--slant-windows";
         break;
+      case OPTX_CONTRAST: {
+        long smooth = 8;
+        if (o.has()) smooth = o.integer();
+        if (smooth < 0 || smooth > 64)
+          throw Runtime("--array-contrast[=SMOOTH]: SMOOTH, the three-point smoothing passes, must be 0 .. 64 (got " + std::to_string(smooth) + ").");
+        mission.ContrastSmooth = (unsigned)smooth;
+        mission.bContrast = true;
+        break;
+      }
+      case OPTX_CONTRAST_ARGS:
+        mission.ContrastArgs.clear();
+        while (o.has()) mission.ContrastArgs.push_back(o.real());
+        mission.bContrastArgs = true;
+        break;
+      case OPTX_CONTRAST_ARRAY:
+        mission.ContrastArray[0] = o.integer();
+        mission.ContrastArray[1] = o.integer();
+        if (mission.ContrastArray[0] < 0 || mission.ContrastArray[1] < mission.ContrastArray[0])
+          throw Runtime("--contrast-array=FIRST,LAST: seismometer indices with 0 <= FIRST <= LAST.");
+        mission.ContrastCompanion = "--contrast-array";
+        break;
+      case OPTX_CONTRAST_AXES:
+        for (int k = 0; k < 3; k++) mission.ContrastAxes[k] = o.real();
+        for (int k = 0; k < 3; k++)
+          if (!std::isfinite(mission.ContrastAxes[k]) || mission.ContrastAxes[k] < 0)
+            throw Runtime("--contrast-axes=X,Y,Z: the weights must be finite and not negative (the rounding bounds need non-negative terms).");
+        mission.ContrastCompanion = "--contrast-axes";
+        break;
+      case OPTX_CONTRAST_WINDOWS:
+        mission.ContrastWindows.clear();
+        while (o.has()) mission.ContrastWindows.push_back(o.real());
+        if (mission.ContrastWindows.empty() || mission.ContrastWindows.size() % 2 || mission.ContrastWindows.size() > 16)
+          throw Runtime("--contrast-windows=V1,V2[,V1,V2...]: one to eight pairs of group velocities in km/s.");
+        for (size_t k = 0; k < mission.ContrastWindows.size(); k += 2)
+          if (!std::isfinite(mission.ContrastWindows[k]) || !(mission.ContrastWindows[k + 1] > 0) ||
+              !(mission.ContrastWindows[k] > mission.ContrastWindows[k + 1]))
+            throw Runtime("--contrast-windows=V1,V2[,V1,V2...]: every pair must be finite with V1 > V2 > 0 (the window is [r / V1, r / V2]).");
+        mission.ContrastCompanion = "--contrast-windows";
+        break;
+      case OPTX_CONTRAST_REGIONS:
+        mission.ContrastRegions.clear();
+        while (o.has()) mission.ContrastRegions.push_back(o.real());
+        if (mission.ContrastRegions.empty() || mission.ContrastRegions.size() % 2 || mission.ContrastRegions.size() > 16)
+          throw Runtime("--contrast-regions=R0,R1[,R0,R1...]: one to eight pairs of distances in km.");
+        for (size_t k = 0; k < mission.ContrastRegions.size(); k += 2)
+          if (!std::isfinite(mission.ContrastRegions[k]) || !std::isfinite(mission.ContrastRegions[k + 1]) ||
+              !(mission.ContrastRegions[k + 1] >= mission.ContrastRegions[k]))
+            throw Runtime("--contrast-regions=R0,R1[,R0,R1...]: every distance must be finite and no region's end before its start.");
+        mission.ContrastCompanion = "--contrast-regions";
+        break;
+      case OPTX_CONTRAST_RANGEPOWER:
+        mission.ContrastRangePower = o.real();
+        if (!std::isfinite(mission.ContrastRangePower)) throw Runtime("--contrast-range-power=Q: the exponent of r / r_ref must be finite.");
+        mission.ContrastCompanion = "--contrast-range-power";
+        break;
+      case OPTX_CONTRAST_SEED:
+        mission.ContrastSeed = (unsigned long)std::strtoull(o.text().c_str(), nullptr, 0);
+        mission.bContrastSeed = true;
+        mission.ContrastCompanion = "--contrast-seed";
+        break;
+      case OPTX_CONTRAST_NUMBER:
+        mission.ContrastNumPhonons = o.integer();
+        if (mission.ContrastNumPhonons < 0) throw Runtime("--contrast-num-phonons=N: the test run's histories cannot be negative.");
+        mission.ContrastCompanion = "--contrast-num-phonons";
+        break;
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;
     }
@@ -724,6 +795,43 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
                     "rounds keep only their moments): out of scope.");
     if (ReportMaskFromKeywords(mission.Reports))
       throw Runtime("--slant-stack cannot be combined with --reports (the event log's launches run one at a time).");
+  }
+  // the contrast of two runs is made where ONE device holds both runs' batch blocks, and keeps them for itself
+  if (mission.ContrastCompanion && !mission.bContrast)
+    throw Runtime(std::string(mission.ContrastCompanion) + " needs --array-contrast: it only says how that contrast is made.");
+  if (mission.bContrastArgs && !mission.bContrast)
+    throw Runtime("--contrast-model-args needs --array-contrast: it names the model the command line's own is compared with.");
+  if (mission.bContrast) {
+    const unsigned long shards = mission.Devices.empty() ? (unsigned long)std::max(1, mission.Gpus) : mission.Devices.size();
+    if (!mission.bContrastArgs)
+      throw Runtime("--array-contrast needs --contrast-model-args=a,b,...: the arguments of the test model, which the command "
+                    "line's own model (the base) is compared with.");
+    if (mission.JobErrorBatches)
+      throw Runtime("--array-contrast cannot be combined with --job-error-batches: the contrast is made where ONE device's batch "
+                    "blocks of both runs lie (r3d_run_batched_contrast); a job sharded over devices has no contrast call.  Use "
+                    "--error-batches=B.");
+    if (!mission.ErrorBatches)
+      throw Runtime("--array-contrast needs --error-batches=B: the standard errors of the contrast are two-sample jackknives over "
+                    "the B batches of either run.");
+    if (mission.bLapse || mission.bTTImage || mission.bEnvShape || mission.bEnvFit || mission.bSlant)
+      throw Runtime(std::string("--array-contrast cannot be combined with ") +
+                    (mission.bLapse ? "--lapse-windows" : mission.bTTImage ? "--ttimage" : mission.bEnvShape ? "--envelope-shape"
+                     : mission.bEnvFit ? "--envelope-fit" : "--slant-stack") +
+                    " in one run (each keeps the run's batch blocks for itself): out of scope.");
+    if (mission.bTarget)
+      throw Runtime("--array-contrast cannot be combined with --target-error (the contrast needs both runs' batch blocks, the "
+                    "rounds keep only their moments): out of scope.");
+    if (ReportMaskFromKeywords(mission.Reports))
+      throw Runtime("--array-contrast cannot be combined with --reports (the event log's launches run one at a time).");
+    if (shards > 1)
+      throw Runtime("--array-contrast runs on one device: --gpus / --devices name " + std::to_string(shards) +
+                    " shards (both runs' batch blocks must lie on the same device).");
+    if (!mission.ContrastRegions.empty() && mission.ContrastWindows.empty())
+      throw Runtime("--contrast-regions needs --contrast-windows: a region's sums are sums of window energies.");
+    const long n_test = mission.ContrastNumPhonons < 0 ? par.NumPhonons : mission.ContrastNumPhonons;
+    if (n_test < (long)mission.ErrorBatches)
+      throw Runtime("--array-contrast: the test run's " + std::to_string(n_test) + " histories are fewer than the " +
+                    std::to_string(mission.ErrorBatches) + " batches of --error-batches.");
   }
   // the views and the maps are made from the grid: none of their options means anything without it
   if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile || mission.bScatterMaps))

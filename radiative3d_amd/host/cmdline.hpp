@@ -10,7 +10,9 @@
 // energies and coda ratios with batch errors), --ttimage and its four (the array's travel-time image with jackknife errors),
 // --target-error and its two (a run to a target standard error, in rounds judged on the GPU), --envelope-shape and its two
 // (peak delay, decay, centroid and width of every array receiver's envelope with jackknife errors), --envelope-fit and its three
-// (the misfit of every array receiver's envelope against an observed one, with jackknife errors).
+// (the misfit of every array receiver's envelope against an observed one, with jackknife errors), --slant-stack and its five
+// (the vespagram of a receiver array), --array-contrast with --contrast-model-args and its seven (a second model's run compared
+// with this one's along a receiver array, with two-sample jackknife errors).
 #ifndef R3DH_CMDLINE_HPP_
 #define R3DH_CMDLINE_HPP_
 
@@ -127,6 +129,25 @@ struct MissionParams {
   unsigned SlantNP = 0, SlantSmooth = 0;
   long SlantArray[2] = {0, -1};           // LAST < 0: through the last receiver
   std::vector<double> SlantWindows;       // T0, T1 pairs
+  // --array-contrast[=SMOOTH] --contrast-model-args=a,b,...: the contrast of TWO runs along a receiver array -- the command
+  // line's own model is the base, the test model the same parameters with the compiled model's arguments replaced -- per
+  // pixel, per receiver and group-velocity window, per region of the array, with the two-sample jackknife over both runs'
+  // batches of --error-batches (include/r3d.h r3d_run_batched_contrast), as contrast.octv.  SMOOTH three-point passes
+  // (default 8).  --contrast-array=FIRST,LAST the receivers (default all), --contrast-axes=X,Y,Z the weights of the three
+  // trace axes, --contrast-windows=V1,V2[,V1,V2...] group-velocity pairs (km/s, V1 > V2): receiver at distance r gets the
+  // window [r / V1, r / V2], --contrast-regions=R0,R1[,...] distance ranges (km) whose receivers' window energies are summed,
+  // --contrast-range-power=Q: receiver i times (r_i / r_ref)^Q in those sums, --contrast-seed=S and
+  // --contrast-num-phonons=N the test run's (defaults: --seed + 1 and the base's count).
+  bool bContrast = false, bContrastArgs = false, bContrastSeed = false;
+  const char* ContrastCompanion = nullptr;   // one of the seven that was given (they are refused without --array-contrast)
+  unsigned ContrastSmooth = 8;
+  std::vector<Real> ContrastArgs;
+  long ContrastArray[2] = {0, -1};        // LAST < 0: through the last receiver
+  double ContrastAxes[3] = {1.0, 1.0, 1.0}, ContrastRangePower = 0.0;
+  std::vector<double> ContrastWindows;    // V1, V2 pairs
+  std::vector<double> ContrastRegions;    // R0, R1 pairs
+  unsigned long ContrastSeed = 0;
+  long ContrastNumPhonons = -1;           // < 0: the base run's
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

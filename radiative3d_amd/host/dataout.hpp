@@ -95,6 +95,32 @@ void SlantPlan(const Model& model, const r3dh_slant_opts& rq, double* distances,
                double* gain, uint32_t* windows);
 void OutputSlant(const Model& model, const r3dh_slant_opts& rq, const r3dh_slant_result& res, std::ostream& out);
 
+// The contrast of two runs of --array-contrast (include/r3d_host.h has the request and the plan): ContrastRequest fills *rq
+// from the mission (throws if --contrast-array names a receiver the model does not have; rq->test_args points into the
+// mission), ContrastPlan the array's distances, every receiver's group-velocity windows in bins with their clipped flags, the
+// regions as receiver indices, the gains and r_ref; OutputContrast writes contrast.octv's text at 17 digits: NumBatches,
+// NumPhonons, Seeds [1 x 2] (base, test), BaseModelArgs, TestModelArgs, Distances [A], TimeWindow, ContrastSeismometers [A],
+// ContrastAxes, ContrastSmooth, Contrast / ContrastSE [A][n_bins], Lit [A], and with windows WindowVelocities [W][2],
+// WindowBins [A][2 W], WindowEnergyBase / WindowEnergyTest / WindowRatio [A][W] with their SE, and with regions Regions [R][2]
+// (km), RegionReceivers [R][2] (seismometer indices), RangePower, RefDistance, RegionRatio / RegionRatioSE / RegionDecibel /
+// RegionDecibelSE [R][W] (the decibels by ../contrasts/r3d_array_contrast.h contrast_decibel).
+struct ContrastFile {
+  unsigned batches[2] = {0, 0};
+  uint64_t phonons[2] = {0, 0}, seeds[2] = {0, 0};
+  const std::vector<Real>* base_args = nullptr;
+  double r_ref = 0;
+  const double* distances = nullptr;           // [A]
+  const uint32_t* bins = nullptr;              // [A][W][2]
+  const uint32_t* region_receivers = nullptr;  // [R][2] array indices
+  const double *contrast = nullptr, *contrast_se = nullptr;
+  const uint32_t* lit = nullptr;
+  const double *window = nullptr, *window_se = nullptr, *region = nullptr, *region_se = nullptr, *region_loo = nullptr;
+};
+void ContrastRequest(const Model& model, const MissionParams& mission, r3dh_contrast_opts* rq);
+void ContrastPlan(const Model& model, const r3dh_contrast_opts& rq, double* distances, uint32_t* bins, int32_t* clipped,
+                  uint32_t* region_receivers, double* gain, double* r_ref);
+void OutputContrast(const Model& model, const r3dh_contrast_opts& rq, const ContrastFile& res, std::ostream& out);
+
 // precision.octv of --target-error (include/r3d_host.h r3dh_write_precision has the file's items): the target, the
 // selection, what was run and the judge's tables (their rows are batch_plan.hpp's).  Needs no model.  PrecisionRequest
 // fills *spec from the mission (throws if --target-array names a receiver the model does not have).

@@ -5,15 +5,17 @@
 // files.  The N-phonon loop itself (Model::RunSimulation, model.cpp:602-633)
 // is one call into the engine's C-ABI.  What a run with --scatter-grid writes afterwards (the grid, its views, its maps)
 // is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches, --lapse-windows, --ttimage,
-// --target-error, --envelope-shape, --envelope-fit and --slant-stack run and write (the batched runs, seis_NNN_err.octv,
-// lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv, slantstack.octv) is the stage of batch_out.cpp.  This file
+// --target-error, --envelope-shape, --envelope-fit, --slant-stack and --array-contrast run and write (the batched runs,
+// seis_NNN_err.octv, lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv, slantstack.octv, contrast.octv) is the
+// stage of batch_out.cpp.  This file
 // makes both jobs, has them checked before the node is built, and calls each once to run and once to write.
 //
 // Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B`,
 // `--job-error-batches=N` (error bars of a job on any number of shards), `--lapse-windows` (lapse.octv), `--ttimage`
 // (ttimage.octv), `--target-error` (a run that stops when its error bars are good enough; precision.octv) and
 // `--envelope-shape` (envshape.octv), `--envelope-fit` (the misfit against observed envelopes; envfit.octv) and `--slant-stack`
-// (the vespagram of a receiver array; slantstack.octv) are accepted
+// (the vespagram of a receiver array; slantstack.octv) and `--array-contrast` (a second model's run compared with this one's
+// along a receiver array; contrast.octv) are accepted
 // (the reference seeds from the clock, is single-process, has no event histogram and no error bars, and takes its phonon
 // count from a hand-tuned table); the `--reports` stream is written
 // after the run, grouped by history, where the reference writes its lines as they happen (the engine appends binary
@@ -279,7 +281,19 @@ int main(int argc, char* argv[]) {
               << "slantstack.octv;  --slant-array=FIRST,LAST (default all)  --slant-axes=X,Y,Z (default 1,1,1)  --slant-energy: stack\n"
               << "energies, not amplitudes  --slant-range-power=Q: receiver i times (r_i / RREF)^Q (default 0)\n"
               << "--slant-windows=T0,T1[,T0,T1...] in seconds, at most eight (default: one over the whole trace).  Not in one run with\n"
-              << "--lapse-windows, --ttimage, --target-error, --envelope-shape, --envelope-fit, --job-error-batches or --reports\n\n";
+              << "--lapse-windows, --ttimage, --target-error, --envelope-shape, --envelope-fit, --job-error-batches or --reports\n"
+              << "--array-contrast[=SMOOTH] --contrast-model-args=a,b,... (with --error-batches; one device; SMOOTH 8): the contrast of\n"
+              << "TWO runs along a receiver array -- the command line's own model is the base, the test model the same with\n"
+              << "--model-args replaced, run on the same device behind it -- per receiver and bin (test - base) / (test + base) of the\n"
+              << "smoothed energies, per receiver and window the ratio of the window energies, per region of the array the ratio of the\n"
+              << "summed window energies and its decibels (normcurve_compare.m's reduction), made on the GPU with two-sample jackknife\n"
+              << "standard errors over both runs' batches, as contrast.octv;  --contrast-array=FIRST,LAST (default all)\n"
+              << "--contrast-axes=X,Y,Z (default 1,1,1)  --contrast-windows=V1,V2[,V1,V2...]: group velocities in km/s, V1 > V2, at most\n"
+              << "eight pairs -- the receiver at distance r gets the window r / V1 .. r / V2  --contrast-regions=R0,R1[,R0,R1...]:\n"
+              << "distance ranges in km, at most eight (with --contrast-windows)  --contrast-range-power=Q: receiver i times\n"
+              << "(r_i / r_ref)^Q in a region's sums (default 0)  --contrast-seed=S (default --seed + 1)  --contrast-num-phonons=N\n"
+              << "(default: the base's; the test side is scaled by N_base / N).  seis_NNN.octv and seis_NNN_err.octv are the base run's;\n"
+              << "the test run's traces are not written.  Not in one run with another batched product or --reports\n\n";
     return 0;
   }
   // A simulation run makes its tables where it uses them (seconds of host work and GBs of upload
@@ -314,7 +328,7 @@ int main(int argc, char* argv[]) {
         for (int g = 0; g < std::max(1, mission.Gpus); g++) mission.Devices.push_back(g);
       const std::vector<int>& devices = mission.Devices;
       // what the run is asked for beyond its seismograms is made into jobs and checked here: a refusal needs no device
-      const BatchJob batch = make_batch_job(mission, model);
+      const BatchJob batch = make_batch_job(mission, model, par);
       check_batch_job(batch, devices.size(), report_mask);
       const GridJob grid = make_grid_job(mission, par);
       check_grid_job(grid, devices.size());

@@ -424,6 +424,30 @@ class Model:
                     distances=dist, r_ref=float(grid[0]), p0=float(grid[1]), dp=float(grid[2]), shift_bin=k, shift_frac=f, gain=gain,
                     windows=win)
 
+    def contrast_plan(self):
+        """What --array-contrast and its companions asked for, planned for the model's array (include/r3d_host.h
+        r3dh_contrast_request, r3dh_contrast_plan): None without the option, else a dict of first, last, smooth, axes, test_args
+        (--contrast-model-args), seed and num_phonons (the test run's), velocities [W, 2] (km/s), regions_km [R, 2], range_power,
+        distances [A] (km), bins [A, W, 2], clipped [A, W], regions [R, 2] (indices into the array), gain [A] and r_ref."""
+        rq = _ffi.ContrastOpts()
+        rc = self._lib.r3dh_contrast_request(self._h, C.byref(rq))
+        if rc < 0:
+            raise RuntimeError("contrast_request failed: " + self._lib.r3dh_last_error().decode())
+        if rc == 0:
+            return None
+        A, W, R = int(rq.last) - int(rq.first) + 1, int(rq.n_windows), int(rq.n_regions)
+        dist, gain, ref = np.zeros(A), np.zeros(A), C.c_double()
+        bins, cut, reg = np.zeros((A, W, 2), dtype=np.uint32), np.zeros((A, W), dtype=np.int32), np.zeros((R, 2), dtype=np.uint32)
+        if self._lib.r3dh_contrast_plan(self._h, C.byref(rq), dist.ctypes.data_as(_ffi._dp), bins.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        cut.ctypes.data_as(C.POINTER(C.c_int32)), reg.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        gain.ctypes.data_as(_ffi._dp), C.byref(ref)):
+            raise RuntimeError("contrast_plan failed: " + self._lib.r3dh_last_error().decode())
+        return dict(first=int(rq.first), last=int(rq.last), smooth=int(rq.smooth), axes=tuple(rq.axes),
+                    test_args=[rq.test_args[k] for k in range(rq.n_test_args)], seed=int(rq.seed), num_phonons=int(rq.num_phonons),
+                    velocities=np.array([tuple(rq.velocities[w]) for w in range(W)]).reshape(W, 2),
+                    regions_km=np.array([tuple(rq.regions[r]) for r in range(R)]).reshape(R, 2), range_power=rq.range_power,
+                    distances=dist, bins=bins, clipped=cut, regions=reg, gain=gain, r_ref=ref.value)
+
     @staticmethod
     def _envshape_opts(request):
         edge, window = request.get("phase_edge", (3.6, 0.0)), request.get("window", (0.0, math.nan))
@@ -967,6 +991,99 @@ def slant_stack(batch_energy, shift_bin, shift_frac, gain, windows, first, last,
     rc = lib.r3d_slant_stack(dev.index or 0, B, batch_energy.data_ptr(), C.byref(spec), *ptr, stream)
     if rc:
         raise RuntimeError("r3d_slant_stack failed: " + lib.r3d_last_error().decode())
+    return out
+
+
+def contrast_gains(distances, r_ref, power):
+    """r3d_contrast_gains (host only): gain [A] = (distances / r_ref)^power, the multipliers of a region's sums."""
+    lib = _ffi.hip_lib()
+    r = np.ascontiguousarray(distances, dtype=np.float64).reshape(-1)
+    g = np.zeros(r.size)
+    if lib.r3d_contrast_gains(r.size, r.ctypes.data_as(_ffi._dp), float(r_ref), float(power), g.ctypes.data_as(_ffi._dp)):
+        raise ValueError(lib.r3d_last_error().decode())
+    return g
+
+
+def contrast_decibel(n_base, n_test, rho, loo=None):
+    """r3d_contrast_decibel (host only): (dB, se) = 10 log10(rho) and the two-sample jackknife se of 10 log10 of the n_base +
+    n_test leave-one-out quotients `loo` (array_contrast's region_loo[r][w]; None: no se); NaN where rho or a quotient is not
+    positive."""
+    lib = _ffi.hip_lib()
+    q = None
+    if loo is not None:
+        q = np.ascontiguousarray(loo, dtype=np.float64).reshape(-1)
+        if q.size != int(n_base) + int(n_test):
+            raise ValueError("loo must hold n_base + n_test quotients")
+    db, se = C.c_double(), C.c_double()
+    if lib.r3d_contrast_decibel(int(n_base), int(n_test), float(rho), q.ctypes.data_as(_ffi._dp) if q is not None else None,
+                                C.byref(db), C.byref(se)):
+        raise ValueError(lib.r3d_last_error().decode())
+    return db.value, se.value
+
+
+def contrast_spec(n_seismometers, n_bins, first, last, weights, bins_ptr, gain_ptr, n_windows, regions=(), scale=(1.0, 1.0), smooth=0):
+    """An r3d_contrast_spec (include/r3d.h): the addresses of the uint32 [A][W][2] bins and the float64 [A] gains -- on the
+    device for array_contrast, on the host for Engine.run_batched_contrast; regions: (i0, i1) pairs, indices into the array."""
+    w = [float(v) for v in weights]
+    if len(w) != _ffi.R3D_N_ENERGY:
+        raise ValueError("five component weights (X, Y, Z, P, S) are needed")
+    reg = [(int(a), int(b)) for a, b in regions]
+    spec = _ffi.ContrastSpec(size=C.sizeof(_ffi.ContrastSpec), n_seismometers=int(n_seismometers), n_bins=int(n_bins), first=int(first),
+                             last=int(last), smooth=int(smooth), n_windows=int(n_windows), n_regions=len(reg), d_bins=bins_ptr,
+                             d_gain=gain_ptr, weight=(C.c_double * _ffi.R3D_N_ENERGY)(*w), scale=(C.c_double * 2)(*[float(v) for v in scale]))
+    for k, (a, b) in enumerate(reg[:_ffi.R3D_CONTRAST_MAX_REGIONS]):
+        spec.regions[k][0], spec.regions[k][1] = a, b
+    return spec
+
+
+def array_contrast(base_energy, test_energy, first, last, weights, bins=None, regions=(), gain=None, scale=(1.0, 1.0), smooth=0,
+                   with_se=None, stream=None):
+    """r3d_array_contrast on torch tensors of one device: base_energy [Ba, S, n_bins, 5] and test_energy [Bb, S, n_bins, 5]
+    float64 are the batch blocks of the two runs, the array the receivers first .. last (A of them), bins [A, W, 2] int32 each
+    receiver's windows b0, b1 (None: no window), regions (i0, i1) pairs of array indices, gain [A] float64 the receivers'
+    multipliers in a region's sums, scale the two sides' multipliers.  Returns a dict of tensors, all WRITTEN: contrast [A,
+    n_bins], lit [A] (int32), window [A, W, 3] (Ea, Eb, rho), region [R, W, 3] (Na, Nb, rho_R), their _se and region_loo [R, W,
+    Ba + Bb] (with_se; default: both B >= 2; else None), bad [1] (int64).  include/r3d.h has the arithmetic.  Asynchronous on
+    `stream` (a raw hipStream_t; None: torch's current one)."""
+    import torch
+    lib = _ffi.hip_lib()
+    for t in (base_energy, test_energy):
+        if t.dim() != 4 or t.shape[3] != _ffi.R3D_N_ENERGY or t.dtype != torch.float64:
+            raise ValueError("the blocks must be float64 [B, S, n_bins, 5]")
+        if not t.is_cuda or not t.is_contiguous():
+            raise ValueError("the blocks must be contiguous tensors on a GPU")
+    if base_energy.device != test_energy.device or tuple(base_energy.shape[1:]) != tuple(test_energy.shape[1:]):
+        raise ValueError("the two runs' blocks must lie on one GPU and have the same shape behind the batches")
+    Ba, S, n_bins = (int(v) for v in base_energy.shape[:3])
+    Bb = int(test_energy.shape[0])
+    dev = base_energy.device
+    A = int(last) - int(first) + 1
+    if A < 1 or last >= S:
+        raise ValueError("the array first .. last must lie within the blocks' seismometers")
+    W = int(bins.shape[1]) if bins is not None else 0
+    R = len(regions)
+    if W and (tuple(bins.shape) != (A, W, 2) or bins.device != dev or not bins.is_contiguous() or bins.element_size() != 4 or
+              bins.dtype.is_floating_point):
+        raise ValueError("bins must be a contiguous 32-bit integer tensor [A, W, 2] on the blocks' GPU")
+    if gain is not None and (tuple(gain.shape) != (A,) or gain.device != dev or not gain.is_contiguous() or gain.dtype != torch.float64):
+        raise ValueError("gain must be a contiguous float64 tensor [A] on the blocks' GPU")
+    with_se = (Ba >= 2 and Bb >= 2) if with_se is None else with_se
+
+    def f64(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=dev)
+    out = dict(contrast=f64(A, n_bins), contrast_se=f64(A, n_bins) if with_se else None,
+               lit=torch.empty(A, dtype=torch.int32, device=dev), window=f64(A, W, _ffi.R3D_CONTRAST_N),
+               window_se=f64(A, W, _ffi.R3D_CONTRAST_N) if with_se else None, region=f64(R, W, _ffi.R3D_CONTRAST_N),
+               region_se=f64(R, W, _ffi.R3D_CONTRAST_N) if with_se else None, region_loo=f64(R, W, Ba + Bb) if with_se else None,
+               bad=torch.zeros(1, dtype=torch.int64, device=dev))
+    spec = contrast_spec(S, n_bins, first, last, weights, bins.data_ptr() if W else None, gain.data_ptr() if gain is not None else None,
+                         W, regions, scale, smooth)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    ptr = [(v.data_ptr() if v is not None else None) for v in out.values()]
+    rc = lib.r3d_array_contrast(dev.index or 0, Ba, base_energy.data_ptr(), Bb, test_energy.data_ptr(), C.byref(spec), *ptr, stream)
+    if rc:
+        raise RuntimeError("r3d_array_contrast failed: " + lib.r3d_last_error().decode())
     return out
 
 
@@ -1580,6 +1697,53 @@ class Engine:
         res, ese, cse = _run_batched_to_host(self._lib, "r3d_run_batched_slant_stack", self._e, m, n, first_id, seed, n_batches,
                                              None, C.byref(spec), C.byref(out))
         return res, ese, cse, got
+
+    def run_batched_contrast(self, other, n, n_other, n_batches, other_batches, first, last, weights, bins=None, regions=(), gain=None,
+                             scale=None, smooth=0, first_id=0, seed=0x5EED, other_seed=0x5EED + 1):
+        """run_batched of this engine (the BASE: n histories in n_batches batches under `seed`) and then of `other` (the TEST:
+        n_other, other_batches, other_seed), with the contrast of the receivers first .. last made where both runs' batch
+        blocks lie (include/r3d.h r3d_run_batched_contrast): bins [A, W, 2] and gain [A] on the host, regions (i0, i1) pairs of
+        array indices, scale the two sides' multipliers (None: (1, n / n_other)).  Returns ((Result, energy_se, counts_se) of
+        the base, the same of the test, contrast): a dict of contrast, contrast_se [A, n_bins], lit [A] (uint32), window,
+        window_se [A, W, 3], region, region_se [R, W, 3], region_loo [R, W, n_batches + other_batches]."""
+        m, mo = self.model, other.model
+        for what in ("n_seismometers", "n_bins"):
+            if getattr(m, what) != getattr(mo, what):
+                raise ValueError(f"the two models' {what} differ")
+        if m.desc.params.time_per_bin != mo.desc.params.time_per_bin:
+            raise ValueError("the two models' time_per_bin differ")
+        A = int(last) - int(first) + 1
+        if A < 1:
+            raise ValueError("the array needs first <= last")
+        b = np.ascontiguousarray(bins, dtype=np.uint32) if bins is not None else np.zeros((A, 0, 2), dtype=np.uint32)
+        if b.ndim != 3 or b.shape[0] != A or b.shape[2] != 2:
+            raise ValueError("bins must be [A, W, 2]")
+        W, R = b.shape[1], len(regions)
+        g = np.ascontiguousarray(gain, dtype=np.float64) if gain is not None else None
+        if g is not None and g.shape != (A,):
+            raise ValueError("gain must be [A]")
+        Ba, Bb = max(int(n_batches), 0), max(int(other_batches), 0)
+        spec = contrast_spec(m.n_seismometers, m.n_bins, first, last, weights, b.ctypes.data if W else None,
+                             g.ctypes.data if g is not None else None, W, regions,
+                             scale if scale is not None else (1.0, float(n) / float(n_other) if n_other else 1.0), smooth)
+        N3 = _ffi.R3D_CONTRAST_N
+        got = dict(contrast=np.zeros((A, m.n_bins)), contrast_se=np.zeros((A, m.n_bins)), lit=np.zeros(A, dtype=np.uint32),
+                   window=np.zeros((A, W, N3)), window_se=np.zeros((A, W, N3)), region=np.zeros((R, W, N3)),
+                   region_se=np.zeros((R, W, N3)), region_loo=np.zeros((R, W, Ba + Bb)))
+        out = _ffi.ContrastResult(size=C.sizeof(_ffi.ContrastResult), **{name: v.ctypes.data for name, v in got.items()})
+        shape = (m.n_seismometers, m.n_bins)
+        sides = []
+        for model in (m, mo):
+            res = model.new_result()
+            sides.append([res, res._as_c(), np.zeros(shape + (_ffi.R3D_N_ENERGY,)), np.zeros(shape + (_ffi.R3D_N_COUNT,))])
+        (ra, ca, esa, csa), (rb, cb, esb, csb) = sides
+        if self._lib.r3d_run_batched_contrast(self._e, other._e, n, n_other, first_id, seed, other_seed, n_batches, other_batches,
+                                              C.byref(ca), C.byref(cb), esa.ctypes.data_as(_ffi._dp), csa.ctypes.data_as(_ffi._dp),
+                                              esb.ctypes.data_as(_ffi._dp), csb.ctypes.data_as(_ffi._dp), C.byref(spec), C.byref(out)):
+            raise RuntimeError("r3d_run_batched_contrast failed: " + self._lib.r3d_last_error().decode())
+        ra._from_c(ca)
+        rb._from_c(cb)
+        return (ra, esa, csa), (rb, esb, csb), got
 
     def run_device(self, n, first_id, seed, d_energy, d_counts, d_scalars, stream=None, carry=None):
         """Asynchronous, device-resident accumulate (pointers are raw device
