@@ -136,7 +136,7 @@ cli: main
 
 # The command-line program the reference's do-*.sh scripts call as ./main
 MAIN_SRC := $(HOSTDIR)/main.cpp $(HOSTDIR)/scatter_out.cpp $(HOSTDIR)/batch_out.cpp
-main: $(MAIN_SRC) $(HOSTDIR)/scatter_out.hpp $(HOSTDIR)/scatter_plan.hpp $(HOSTDIR)/batch_out.hpp $(HOSTDIR)/batch_plan.hpp \
+main: $(MAIN_SRC) $(HOSTDIR)/scatter_out.hpp $(HOSTDIR)/scatter_plan.hpp $(HOSTDIR)/batch_out.hpp $(HOSTDIR)/batch_plan.hpp $(HOSTDIR)/batch_products.hpp \
       $(LIBDIR)/libr3d_host.so $(LIBDIR)/libr3d_hip.so $(ENGINE_HDR)
 	$(CXX) $(CXXFLAGS) -pthread -o $@ $(MAIN_SRC) -L$(LIBDIR) -lr3d_host -lr3d_hip \
 	    -Wl,-rpath,'$$ORIGIN/$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib

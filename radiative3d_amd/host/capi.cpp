@@ -12,7 +12,29 @@
 
 namespace {
 thread_local std::string g_error;
+
+// Runs `body`: `ok`, or -- the exception's text kept for r3dh_last_error -- `failed`.
+template <class Body>
+int guarded(int ok, int failed, Body body) {
+  try {
+    body();
+    return ok;
+  } catch (const std::exception& e) {
+    g_error = e.what();
+  }
+  return failed;
 }
+
+// Opens `path` and has `write` fill it: 0, or 1 where it threw or the file could not be written.
+template <class Write>
+int write_file(const char* path, Write write) {
+  return guarded(0, 1, [&] {
+    std::ofstream f(path);
+    write(f);
+    if (!f) throw Runtime(std::string("cannot write ") + path);
+  });
+}
+}  // namespace
 
 struct r3dh_model {
   ModelParams params;
@@ -115,13 +137,7 @@ int r3dh_write_errors(r3dh_model* m, const double* energy_se, const double* coun
                       const char* outdir) {
   if (!m || !energy_se || !counts_se) return g_error = "r3dh_write_errors: null argument", 1;
   if (n_batches < 2) return g_error = "r3dh_write_errors: a standard error needs at least 2 batches", 1;
-  try {
-    OutputSeismometerErrors(*m->model, energy_se, counts_se, n_batches, outdir ? outdir : "");
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
+  return guarded(0, 1, [&] { OutputSeismometerErrors(*m->model, energy_se, counts_se, n_batches, outdir ? outdir : ""); });
 }
 
 uint32_t r3dh_error_batches(const r3dh_model* m) { return m ? m->mission.ErrorBatches : 0; }
@@ -157,29 +173,19 @@ int r3dh_write_maps_header(const r3dh_maps_header* h, const char* path) {
   return 0;
 }
 
+// The trios of the batched products: _request (0: not asked for, 1: made, -1: refused), _plan and _write_ (0, or 1).  The
+// plans go through the global coordinate system, which still holds this model's mapping only if no other model was built
+// since -- as for r3dh_grid_dump.
+
 int r3dh_lapse_request(const r3dh_model* m, r3dh_lapse_opts* rq) {
   if (!m || !m->mission.bLapse) return 0;
   if (!rq) return 1;
-  try {
-    LapseRequest(*m->model, m->mission, rq);
-    return 1;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return -1;
+  return guarded(1, -1, [&] { LapseRequest(*m->model, m->mission, rq); });
 }
 
 int r3dh_lapse_plan(const r3dh_model* m, const r3dh_lapse_opts* rq, double* distances, uint32_t* bins, int32_t* clipped) {
   if (!m || !rq || !distances || !bins || !clipped) return g_error = "r3dh_lapse_plan: null argument", 1;
-  try {
-    // (through the global coordinate system, which still holds this model's mapping only if no other model was built
-    //  since -- as for r3dh_grid_dump)
-    LapsePlan(*m->model, *rq, distances, bins, clipped);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
+  return guarded(0, 1, [&] { LapsePlan(*m->model, *rq, distances, bins, clipped); });
 }
 
 int r3dh_write_lapse(const r3dh_model* m, const r3dh_lapse_opts* rq, const r3dh_lapse_result* res, const char* path) {
@@ -187,39 +193,18 @@ int r3dh_write_lapse(const r3dh_model* m, const r3dh_lapse_opts* rq, const r3dh_
   if (!res->distances || !res->bins || !res->clipped || !res->window_energy || !res->window_se || !res->window_counts ||
       !res->batch_window_energy)
     return g_error = "r3dh_write_lapse: null array in the result", 1;
-  try {
-    std::ofstream f(path);
-    OutputLapse(*m->model, *rq, *res, f);
-    if (!f) throw Runtime(std::string("cannot write ") + path);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
+  return write_file(path, [&](std::ostream& f) { OutputLapse(*m->model, *rq, *res, f); });
 }
 
 int r3dh_ttimage_request(const r3dh_model* m, r3dh_ttimage_opts* rq) {
   if (!m || !m->mission.bTTImage) return 0;
   if (!rq) return 1;
-  try {
-    TTImageRequest(*m->model, m->mission, rq);
-    return 1;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return -1;
+  return guarded(1, -1, [&] { TTImageRequest(*m->model, m->mission, rq); });
 }
 
 int r3dh_ttimage_plan(const r3dh_model* m, const r3dh_ttimage_opts* rq, double* distances, double* azimuths) {
   if (!m || !rq || !distances || !azimuths) return g_error = "r3dh_ttimage_plan: null argument", 1;
-  try {
-    // (through the global coordinate system, as r3dh_lapse_plan)
-    TTImagePlan(*m->model, *rq, distances, azimuths);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
+  return guarded(0, 1, [&] { TTImagePlan(*m->model, *rq, distances, azimuths); });
 }
 
 int r3dh_write_ttimage(const r3dh_model* m, const r3dh_ttimage_opts* rq, const r3dh_ttimage_result* res, const char* path) {
@@ -227,39 +212,18 @@ int r3dh_write_ttimage(const r3dh_model* m, const r3dh_ttimage_opts* rq, const r
   if (!res->distances || !res->azimuths || !res->image || !res->image_se || !res->lit || !res->summed || !res->summed_se ||
       !res->peak || !res->peak_bin || (res->has_fit && (!res->curve || !res->image_curve || !res->image_curve_se)))
     return g_error = "r3dh_write_ttimage: null array in the result", 1;
-  try {
-    std::ofstream f(path);
-    OutputTTImage(*m->model, *rq, *res, f);
-    if (!f) throw Runtime(std::string("cannot write ") + path);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
+  return write_file(path, [&](std::ostream& f) { OutputTTImage(*m->model, *rq, *res, f); });
 }
 
 int r3dh_envshape_request(const r3dh_model* m, r3dh_envshape_opts* rq) {
   if (!m || !m->mission.bEnvShape) return 0;
   if (!rq) return 1;
-  try {
-    EnvShapeRequest(*m->model, m->mission, rq);
-    return 1;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return -1;
+  return guarded(1, -1, [&] { EnvShapeRequest(*m->model, m->mission, rq); });
 }
 
 int r3dh_envshape_plan(const r3dh_model* m, const r3dh_envshape_opts* rq, double* distances, uint32_t* bins, int32_t* clipped) {
   if (!m || !rq || !distances || !bins || !clipped) return g_error = "r3dh_envshape_plan: null argument", 1;
-  try {
-    // (through the global coordinate system, as r3dh_lapse_plan)
-    EnvShapePlan(*m->model, *rq, distances, bins, clipped);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
+  return guarded(0, 1, [&] { EnvShapePlan(*m->model, *rq, distances, bins, clipped); });
 }
 
 int r3dh_write_envshape(const r3dh_model* m, const r3dh_envshape_opts* rq, const r3dh_envshape_result* res, const char* path) {
@@ -267,41 +231,20 @@ int r3dh_write_envshape(const r3dh_model* m, const r3dh_envshape_opts* rq, const
   if (!res->distances || !res->bins || !res->clipped || !res->shape || !res->shape_se || !res->envelope || !res->envelope_se ||
       !res->peak_bin || !res->half_bin || !res->lit)
     return g_error = "r3dh_write_envshape: null array in the result", 1;
-  try {
-    std::ofstream f(path);
-    OutputEnvShape(*m->model, *rq, *res, f);
-    if (!f) throw Runtime(std::string("cannot write ") + path);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
+  return write_file(path, [&](std::ostream& f) { OutputEnvShape(*m->model, *rq, *res, f); });
 }
 
 int r3dh_slant_request(const r3dh_model* m, r3dh_slant_opts* rq) {
   if (!m || !m->mission.bSlant) return 0;
   if (!rq) return 1;
-  try {
-    SlantRequest(*m->model, m->mission, rq);
-    return 1;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return -1;
+  return guarded(1, -1, [&] { SlantRequest(*m->model, m->mission, rq); });
 }
 
 int r3dh_slant_plan(const r3dh_model* m, const r3dh_slant_opts* rq, double* distances, double* grid, int32_t* shift_bin,
                     double* shift_frac, double* gain, uint32_t* windows) {
   if (!m || !rq || !distances || !grid || !shift_bin || !shift_frac || !gain || !windows)
     return g_error = "r3dh_slant_plan: null argument", 1;
-  try {
-    // (through the global coordinate system, as r3dh_lapse_plan)
-    SlantPlan(*m->model, *rq, distances, grid, shift_bin, shift_frac, gain, windows);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
+  return guarded(0, 1, [&] { SlantPlan(*m->model, *rq, distances, grid, shift_bin, shift_frac, gain, windows); });
 }
 
 int r3dh_write_slant(const r3dh_model* m, const r3dh_slant_opts* rq, const r3dh_slant_result* res, const char* path) {
@@ -309,41 +252,56 @@ int r3dh_write_slant(const r3dh_model* m, const r3dh_slant_opts* rq, const r3dh_
   if (!res->distances || !res->windows || !res->stack || !res->stack_se || !res->fold || !res->power || !res->power_se || !res->picks ||
       !res->picks_se)
     return g_error = "r3dh_write_slant: null array in the result", 1;
-  try {
-    std::ofstream f(path);
-    OutputSlant(*m->model, *rq, *res, f);
-    if (!f) throw Runtime(std::string("cannot write ") + path);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
+  return write_file(path, [&](std::ostream& f) { OutputSlant(*m->model, *rq, *res, f); });
 }
 
 int r3dh_contrast_request(const r3dh_model* m, r3dh_contrast_opts* rq) {
   if (!m || !m->mission.bContrast) return 0;
   if (!rq) return 1;
-  try {
-    ContrastRequest(*m->model, m->mission, rq);
-    return 1;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return -1;
+  return guarded(1, -1, [&] { ContrastRequest(*m->model, m->mission, rq); });
 }
 
 int r3dh_contrast_plan(const r3dh_model* m, const r3dh_contrast_opts* rq, double* distances, uint32_t* bins, int32_t* clipped,
                        uint32_t* region_receivers, double* gain, double* r_ref) {
   if (!m || !rq || !distances || !gain || !r_ref || (rq->n_windows && (!bins || !clipped)) || (rq->n_regions && !region_receivers))
     return g_error = "r3dh_contrast_plan: null argument", 1;
-  try {
-    // (through the global coordinate system, as r3dh_lapse_plan)
-    ContrastPlan(*m->model, *rq, distances, bins, clipped, region_receivers, gain, r_ref);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
+  return guarded(0, 1, [&] { ContrastPlan(*m->model, *rq, distances, bins, clipped, region_receivers, gain, r_ref); });
+}
+
+int r3dh_envfit_request(const r3dh_model* m, r3dh_envfit_opts* rq) {
+  if (!m || !m->mission.bEnvFit) return 0;
+  if (!rq) return 1;
+  return guarded(1, -1, [&] { EnvFitRequest(*m->model, m->mission, rq); });
+}
+
+int r3dh_envfit_plan(const r3dh_model* m, const r3dh_envfit_opts* rq, double* distances, uint32_t* bins, int32_t* clipped,
+                     double* observed, uint32_t* max_lag) {
+  if (!m || !rq || !distances || !bins || !clipped || !observed || !max_lag) return g_error = "r3dh_envfit_plan: null argument", 1;
+  return guarded(0, 1, [&] { EnvFitPlan(*m->model, *rq, distances, bins, clipped, observed, max_lag); });
+}
+
+int r3dh_write_envfit(const r3dh_model* m, const r3dh_envfit_opts* rq, const r3dh_envfit_result* res, const char* path) {
+  if (!m || !rq || !res || !path) return g_error = "r3dh_write_envfit: null argument", 1;
+  if (!res->distances || !res->bins || !res->clipped || !res->observed || !res->misfit || !res->misfit_se || !res->xcorr ||
+      !res->xcorr_se || !res->envelope || !res->lit)
+    return g_error = "r3dh_write_envfit: null array in the result", 1;
+  return write_file(path, [&](std::ostream& f) { OutputEnvFit(*m->model, *rq, *res, f); });
+}
+
+int r3dh_precision_request(const r3dh_model* m, r3d_precision_spec* spec, uint32_t* max_rounds) {
+  if (!m || !m->mission.bTarget) return 0;
+  return guarded(1, -1, [&] {
+    r3d_precision_spec made;
+    PrecisionRequest(*m->model, m->mission, &made);
+    if (spec) *spec = made;
+    if (max_rounds) *max_rounds = m->mission.TargetRounds;
+  });
+}
+
+int r3dh_write_precision(const r3d_precision_spec* spec, uint32_t n_batches, uint32_t max_rounds, uint64_t n_max,
+                         const r3d_precision_report* report, const char* path) {
+  if (!spec || !report || !path) return g_error = "r3dh_write_precision: null argument", 1;
+  return write_file(path, [&](std::ostream& f) { OutputPrecision(*spec, n_batches, max_rounds, n_max, *report, f); });
 }
 
 int r3dh_observed_to_bins(const double* samples, uint32_t n_samples, uint32_t stride, double t0, double t1, double t_begin,
@@ -369,74 +327,6 @@ int r3dh_read_octave(const char* path, const char* name, uint32_t* rows, uint32_
       return 0;
     }
     throw Runtime(std::string("Octave text: ") + path + " holds no variable '" + name + "'");
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
-}
-
-int r3dh_envfit_request(const r3dh_model* m, r3dh_envfit_opts* rq) {
-  if (!m || !m->mission.bEnvFit) return 0;
-  if (!rq) return 1;
-  try {
-    EnvFitRequest(*m->model, m->mission, rq);
-    return 1;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return -1;
-}
-
-int r3dh_envfit_plan(const r3dh_model* m, const r3dh_envfit_opts* rq, double* distances, uint32_t* bins, int32_t* clipped,
-                     double* observed, uint32_t* max_lag) {
-  if (!m || !rq || !distances || !bins || !clipped || !observed || !max_lag) return g_error = "r3dh_envfit_plan: null argument", 1;
-  try {
-    EnvFitPlan(*m->model, *rq, distances, bins, clipped, observed, max_lag);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
-}
-
-int r3dh_write_envfit(const r3dh_model* m, const r3dh_envfit_opts* rq, const r3dh_envfit_result* res, const char* path) {
-  if (!m || !rq || !res || !path) return g_error = "r3dh_write_envfit: null argument", 1;
-  if (!res->distances || !res->bins || !res->clipped || !res->observed || !res->misfit || !res->misfit_se || !res->xcorr ||
-      !res->xcorr_se || !res->envelope || !res->lit)
-    return g_error = "r3dh_write_envfit: null array in the result", 1;
-  try {
-    std::ofstream f(path);
-    OutputEnvFit(*m->model, *rq, *res, f);
-    if (!f) throw Runtime(std::string("cannot write ") + path);
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return 1;
-}
-
-int r3dh_precision_request(const r3dh_model* m, r3d_precision_spec* spec, uint32_t* max_rounds) {
-  if (!m || !m->mission.bTarget) return 0;
-  try {
-    r3d_precision_spec made;
-    PrecisionRequest(*m->model, m->mission, &made);
-    if (spec) *spec = made;
-    if (max_rounds) *max_rounds = m->mission.TargetRounds;
-    return 1;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-  }
-  return -1;
-}
-
-int r3dh_write_precision(const r3d_precision_spec* spec, uint32_t n_batches, uint32_t max_rounds, uint64_t n_max,
-                         const r3d_precision_report* report, const char* path) {
-  if (!spec || !report || !path) return g_error = "r3dh_write_precision: null argument", 1;
-  try {
-    std::ofstream f(path);
-    OutputPrecision(*spec, n_batches, max_rounds, n_max, *report, f);
-    if (!f) throw Runtime(std::string("cannot write ") + path);
-    return 0;
   } catch (const std::exception& e) {
     g_error = e.what();
   }

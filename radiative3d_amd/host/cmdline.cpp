@@ -8,6 +8,7 @@
 #include <iostream>
 #include <map>
 
+#include "batch_products.hpp"
 #include "dataout.hpp"
 
 namespace {
@@ -195,6 +196,11 @@ void set_source(Opt& o, ModelParams& par) {
   } else {
     throw Runtime(kind + " is not a valid source mechanism keyword.");
   }
+}
+
+// The shards that --gpus / --devices name.
+unsigned long shard_count(const MissionParams& mission) {
+  return mission.Devices.empty() ? (unsigned long)std::max(1, mission.Gpus) : mission.Devices.size();
 }
 
 }  // namespace
@@ -667,7 +673,7 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
   }
   // --job-error-batches=N deals the job's N batches evenly to the shards that --gpus / --devices name
   if (mission.JobErrorBatches) {
-    const unsigned long shards = mission.Devices.empty() ? (unsigned long)std::max(1, mission.Gpus) : mission.Devices.size();
+    const unsigned long shards = shard_count(mission);
     const unsigned long N = mission.JobErrorBatches;
     const std::string over = std::to_string(N) + " batches over " + std::to_string(shards) + (shards == 1 ? " shard" : " shards");
     if (mission.ErrorBatches)
@@ -680,158 +686,57 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
     if (N / shards < 2 || N / shards > 64)
       throw Runtime("--job-error-batches=N: every shard runs N / shards batches, which must be 2 .. 64 (got " + over + ").");
   }
-  // the lapse windows' errors come from one device's batches
-  if (mission.LapseCompanion && !mission.bLapse)
-    throw Runtime(std::string(mission.LapseCompanion) + " needs --lapse-windows: it only says how those windows are summed.");
-  if (mission.bLapse && mission.JobErrorBatches)
-    throw Runtime("--lapse-windows cannot be combined with --job-error-batches: the window sums are taken where ONE device's "
-                  "batch blocks lie (r3d_run_batched_windows); a job sharded over devices has no windows call.  Use "
-                  "--error-batches=B.");
-  if (mission.bLapse && !mission.ErrorBatches)
-    throw Runtime("--lapse-windows needs --error-batches=B: the windows' standard errors and the ratios' jackknife come from "
-                  "the B batches.");
-  // the travel-time image's errors come from one device's batches, too
-  if (mission.TTCompanion && !mission.bTTImage)
-    throw Runtime(std::string(mission.TTCompanion) + " needs --ttimage: it only says how that image is made.");
-  if (mission.bTTImage && mission.JobErrorBatches)
-    throw Runtime("--ttimage cannot be combined with --job-error-batches: the image is made where ONE device's batch blocks "
-                  "lie (r3d_run_batched_array_image); a job sharded over devices has no image call.  Use --error-batches=B.");
-  if (mission.bTTImage && !mission.ErrorBatches)
-    throw Runtime("--ttimage needs --error-batches=B: the pixels' and the fit's standard errors are jackknives over the B batches.");
-  if (mission.bTTImage && mission.bLapse)
-    throw Runtime("--ttimage cannot be combined with --lapse-windows in one run (each keeps the run's batch blocks for itself): "
-                  "out of scope.");
-  if (mission.bTTNormCurve && mission.TTFit[0] == 0)
-    throw Runtime("--ttimage-normcurve needs --ttimage-fit=IBEGIN,IEND: the curve's range window comes from the fit's array.");
-  // a run to a target standard error is one device's batched run, in rounds
-  if (mission.TargetCompanion && !mission.bTarget)
-    throw Runtime(std::string(mission.TargetCompanion) + " needs --target-error: it only says which entries are judged.");
-  if (mission.bTarget) {
-    const unsigned long shards = mission.Devices.empty() ? (unsigned long)std::max(1, mission.Gpus) : mission.Devices.size();
-    if (mission.JobErrorBatches)
-      throw Runtime("--target-error cannot be combined with --job-error-batches: the rounds are judged where ONE device's "
-                    "batch blocks lie (r3d_run_to_precision).  Use --error-batches=B.");
-    if (!mission.ErrorBatches)
-      throw Runtime("--target-error needs --error-batches=B: every round runs as B batches, and the standard errors that are "
-                    "judged come from the batches of all rounds so far.");
-    if (mission.bLapse)
-      throw Runtime("--target-error cannot be combined with --lapse-windows (the window sums need one run's batch blocks, the "
-                    "rounds keep only their moments): out of scope.");
-    if (mission.bTTImage)
-      throw Runtime("--target-error cannot be combined with --ttimage (the image needs one run's batch blocks, the rounds keep "
-                    "only their moments): out of scope.");
-    if (ReportMaskFromKeywords(mission.Reports))
-      throw Runtime("--target-error cannot be combined with --reports (the event log's launches run one at a time).");
-    if (shards > 1)
-      throw Runtime("--target-error runs on one device: --gpus / --devices name " + std::to_string(shards) +
-                    " shards (a run in rounds over several devices is not built).");
-    const long n = par.NumPhonons, R = (long)mission.TargetRounds;
-    if (n < 0 || n % R)
-      throw Runtime("--target-error: --num-phonons (" + std::to_string(n) + "), the cap, must be a multiple of ROUNDS (" +
-                    std::to_string(R) + "): every round runs the same number of histories.");
-    if (n / R < (long)mission.ErrorBatches)
-      throw Runtime("--target-error: a round of --num-phonons / ROUNDS = " + std::to_string(n / R) + " histories is fewer than the " +
-                    std::to_string(mission.ErrorBatches) + " batches of --error-batches.");
-  }
-  // the envelope shape's errors come from one device's batches, and it keeps the run's batch blocks for itself
-  if (mission.EnvCompanion && !mission.bEnvShape)
-    throw Runtime(std::string(mission.EnvCompanion) + " needs --envelope-shape: it only says how that shape is made.");
-  if (mission.bEnvShape) {
-    if (mission.JobErrorBatches)
-      throw Runtime("--envelope-shape cannot be combined with --job-error-batches: the shape is made where ONE device's batch "
-                    "blocks lie (r3d_run_batched_envelope_shape); a job sharded over devices has no shape call.  Use "
-                    "--error-batches=B.");
-    if (!mission.ErrorBatches)
-      throw Runtime("--envelope-shape needs --error-batches=B: the standard errors of the shape's numbers are jackknives over "
-                    "the B batches.");
-    if (mission.bLapse || mission.bTTImage)
-      throw Runtime(std::string("--envelope-shape cannot be combined with ") + (mission.bLapse ? "--lapse-windows" : "--ttimage") +
-                    " in one run (each keeps the run's batch blocks for itself): out of scope.");
-    if (mission.bTarget)
-      throw Runtime("--envelope-shape cannot be combined with --target-error (the shape needs one run's batch blocks, the "
-                    "rounds keep only their moments): out of scope.");
-    if (ReportMaskFromKeywords(mission.Reports))
-      throw Runtime("--envelope-shape cannot be combined with --reports (the event log's launches run one at a time).");
-  }
-  // the envelope misfit's errors come from one device's batches, and it keeps the run's batch blocks for itself
-  if (mission.FitCompanion && !mission.bEnvFit)
-    throw Runtime(std::string(mission.FitCompanion) + " needs --envelope-fit: it only says how that misfit is made.");
-  if (mission.bEnvFit) {
-    if (mission.JobErrorBatches)
-      throw Runtime("--envelope-fit cannot be combined with --job-error-batches: the misfit is made where ONE device's batch "
-                    "blocks lie (r3d_run_batched_envelope_misfit); a job sharded over devices has no misfit call.  Use "
-                    "--error-batches=B.");
-    if (!mission.ErrorBatches)
-      throw Runtime("--envelope-fit needs --error-batches=B: the standard errors of the misfit's numbers are jackknives over "
-                    "the B batches.");
-    if (mission.bLapse || mission.bTTImage || mission.bEnvShape)
-      throw Runtime(std::string("--envelope-fit cannot be combined with ") +
-                    (mission.bLapse ? "--lapse-windows" : mission.bTTImage ? "--ttimage" : "--envelope-shape") +
-                    " in one run (each keeps the run's batch blocks for itself): out of scope.");
-    if (mission.bTarget)
-      throw Runtime("--envelope-fit cannot be combined with --target-error (the misfit needs one run's batch blocks, the "
-                    "rounds keep only their moments): out of scope.");
-    if (ReportMaskFromKeywords(mission.Reports))
-      throw Runtime("--envelope-fit cannot be combined with --reports (the event log's launches run one at a time).");
-  }
-  // the slant stack's errors come from one device's batches, and it keeps the run's batch blocks for itself
-  if (mission.SlantCompanion && !mission.bSlant)
-    throw Runtime(std::string(mission.SlantCompanion) + " needs --slant-stack: it only says how that stack is made.");
-  if (mission.bSlant) {
-    if (mission.JobErrorBatches)
-      throw Runtime("--slant-stack cannot be combined with --job-error-batches: the stack is made where ONE device's batch "
-                    "blocks lie (r3d_run_batched_slant_stack); a job sharded over devices has no slant call.  Use "
-                    "--error-batches=B.");
-    if (!mission.ErrorBatches)
-      throw Runtime("--slant-stack needs --error-batches=B: the standard errors of the stack, the power and the picks are "
-                    "jackknives over the B batches.");
-    if (mission.bLapse || mission.bTTImage || mission.bEnvShape || mission.bEnvFit)
-      throw Runtime(std::string("--slant-stack cannot be combined with ") +
-                    (mission.bLapse ? "--lapse-windows" : mission.bTTImage ? "--ttimage" : mission.bEnvShape ? "--envelope-shape"
-                                                                                                            : "--envelope-fit") +
-                    " in one run (each keeps the run's batch blocks for itself): out of scope.");
-    if (mission.bTarget)
-      throw Runtime("--slant-stack cannot be combined with --target-error (the stack needs one run's batch blocks, the "
-                    "rounds keep only their moments): out of scope.");
-    if (ReportMaskFromKeywords(mission.Reports))
-      throw Runtime("--slant-stack cannot be combined with --reports (the event log's launches run one at a time).");
-  }
-  // the contrast of two runs is made where ONE device holds both runs' batch blocks, and keeps them for itself
-  if (mission.ContrastCompanion && !mission.bContrast)
-    throw Runtime(std::string(mission.ContrastCompanion) + " needs --array-contrast: it only says how that contrast is made.");
-  if (mission.bContrastArgs && !mission.bContrast)
-    throw Runtime("--contrast-model-args needs --array-contrast: it names the model the command line's own is compared with.");
-  if (mission.bContrast) {
-    const unsigned long shards = mission.Devices.empty() ? (unsigned long)std::max(1, mission.Gpus) : mission.Devices.size();
-    if (!mission.bContrastArgs)
+  // the batched products (batch_products.hpp), in the order of the table: each is made where ONE device's batch blocks lie
+  // and keeps them for itself.  The first rule that is broken speaks
+  const std::string each_keeps = " in one run (each keeps the run's batch blocks for itself): out of scope.";
+  for (const BatchProduct& p : kBatchProducts) {
+    const std::string option = p.option;
+    if (mission.*p.companion && !(mission.*p.given))
+      throw Runtime(std::string(mission.*p.companion) + " needs " + option + ": it only says " + p.only_says + ".");
+    if (p.kind == BatchKind::CONTRAST && mission.bContrastArgs && !mission.bContrast)
+      throw Runtime("--contrast-model-args needs --array-contrast: it names the model the command line's own is compared with.");
+    if (!(mission.*p.given)) continue;
+    if (p.kind == BatchKind::CONTRAST && !mission.bContrastArgs)
       throw Runtime("--array-contrast needs --contrast-model-args=a,b,...: the arguments of the test model, which the command "
                     "line's own model (the base) is compared with.");
     if (mission.JobErrorBatches)
-      throw Runtime("--array-contrast cannot be combined with --job-error-batches: the contrast is made where ONE device's batch "
-                    "blocks of both runs lie (r3d_run_batched_contrast); a job sharded over devices has no contrast call.  Use "
-                    "--error-batches=B.");
-    if (!mission.ErrorBatches)
-      throw Runtime("--array-contrast needs --error-batches=B: the standard errors of the contrast are two-sample jackknives over "
-                    "the B batches of either run.");
-    if (mission.bLapse || mission.bTTImage || mission.bEnvShape || mission.bEnvFit || mission.bSlant)
-      throw Runtime(std::string("--array-contrast cannot be combined with ") +
-                    (mission.bLapse ? "--lapse-windows" : mission.bTTImage ? "--ttimage" : mission.bEnvShape ? "--envelope-shape"
-                     : mission.bEnvFit ? "--envelope-fit" : "--slant-stack") +
-                    " in one run (each keeps the run's batch blocks for itself): out of scope.");
-    if (mission.bTarget)
-      throw Runtime("--array-contrast cannot be combined with --target-error (the contrast needs both runs' batch blocks, the "
-                    "rounds keep only their moments): out of scope.");
-    if (ReportMaskFromKeywords(mission.Reports))
-      throw Runtime("--array-contrast cannot be combined with --reports (the event log's launches run one at a time).");
-    if (shards > 1)
-      throw Runtime("--array-contrast runs on one device: --gpus / --devices name " + std::to_string(shards) +
-                    " shards (both runs' batch blocks must lie on the same device).");
-    if (!mission.ContrastRegions.empty() && mission.ContrastWindows.empty())
-      throw Runtime("--contrast-regions needs --contrast-windows: a region's sums are sums of window energies.");
-    const long n_test = mission.ContrastNumPhonons < 0 ? par.NumPhonons : mission.ContrastNumPhonons;
-    if (n_test < (long)mission.ErrorBatches)
-      throw Runtime("--array-contrast: the test run's " + std::to_string(n_test) + " histories are fewer than the " +
-                    std::to_string(mission.ErrorBatches) + " batches of --error-batches.");
+      throw Runtime(option + " cannot be combined with --job-error-batches: " + p.made_where + " (" + p.call + ")" +
+                    (p.call_noun ? std::string("; a job sharded over devices has no ") + p.call_noun + " call" : std::string()) +
+                    ".  Use --error-batches=B.");
+    if (!mission.ErrorBatches) throw Runtime(option + " needs --error-batches=B: " + p.needs_batches);
+    // (every earlier product in the table's order: where --target-error and a product behind it stand before this one, that
+    //  product's own turn has refused the two already, so the rounds' sentence never hides another)
+    for (const BatchProduct* q = kBatchProducts; q != &p; q++) {
+      if (!(mission.*q->given)) continue;
+      const char* blocks = p.needs_blocks && q->needs_blocks ? nullptr : p.needs_blocks ? p.needs_blocks : q->needs_blocks;
+      throw Runtime(option + " cannot be combined with " + q->option +
+                    (blocks ? " (" + std::string(blocks) + ", the rounds keep only their moments): out of scope." : each_keeps));
+    }
+    if (p.refuses_reports && ReportMaskFromKeywords(mission.Reports))
+      throw Runtime(option + " cannot be combined with --reports (the event log's launches run one at a time).");
+    if (p.one_device && shard_count(mission) > 1)
+      throw Runtime(option + " runs on one device: --gpus / --devices name " + std::to_string(shard_count(mission)) + " shards (" +
+                    p.one_device + ").");
+    // what is one product's own
+    if (p.kind == BatchKind::IMAGE && mission.bTTNormCurve && mission.TTFit[0] == 0)
+      throw Runtime("--ttimage-normcurve needs --ttimage-fit=IBEGIN,IEND: the curve's range window comes from the fit's array.");
+    if (p.kind == BatchKind::PRECISION) {
+      const long n = par.NumPhonons, R = (long)mission.TargetRounds;
+      if (n < 0 || n % R)
+        throw Runtime("--target-error: --num-phonons (" + std::to_string(n) + "), the cap, must be a multiple of ROUNDS (" +
+                      std::to_string(R) + "): every round runs the same number of histories.");
+      if (n / R < (long)mission.ErrorBatches)
+        throw Runtime("--target-error: a round of --num-phonons / ROUNDS = " + std::to_string(n / R) + " histories is fewer than the " +
+                      std::to_string(mission.ErrorBatches) + " batches of --error-batches.");
+    }
+    if (p.kind == BatchKind::CONTRAST) {
+      if (!mission.ContrastRegions.empty() && mission.ContrastWindows.empty())
+        throw Runtime("--contrast-regions needs --contrast-windows: a region's sums are sums of window energies.");
+      const long n_test = mission.ContrastNumPhonons < 0 ? par.NumPhonons : mission.ContrastNumPhonons;
+      if (n_test < (long)mission.ErrorBatches)
+        throw Runtime("--array-contrast: the test run's " + std::to_string(n_test) + " histories are fewer than the " +
+                      std::to_string(mission.ErrorBatches) + " batches of --error-batches.");
+    }
   }
   // the views and the maps are made from the grid: none of their options means anything without it
   if (!mission.bScatterGrid && (mission.bScatterViews || mission.bViewAzimuth || mission.bNoScatterGridFile || mission.bScatterMaps))

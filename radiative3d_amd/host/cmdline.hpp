@@ -12,7 +12,8 @@
 // (peak delay, decay, centroid and width of every array receiver's envelope with jackknife errors), --envelope-fit and its three
 // (the misfit of every array receiver's envelope against an observed one, with jackknife errors), --slant-stack and its five
 // (the vespagram of a receiver array), --array-contrast with --contrast-model-args and its seven (a second model's run compared
-// with this one's along a receiver array, with two-sample jackknife errors).
+// with this one's along a receiver array, with two-sample jackknife errors).  The last seven -- the batched products -- have
+// one record each in batch_products.hpp, and what they cannot be combined with is one loop over that table (cmdline.cpp).
 #ifndef R3DH_CMDLINE_HPP_
 #define R3DH_CMDLINE_HPP_
 

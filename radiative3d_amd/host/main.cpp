@@ -4,10 +4,9 @@
 // ("@@ __PHASE__", "#  R3D_GRID:", "#  BEGIN SCATTERER DUMP:"), same output
 // files.  The N-phonon loop itself (Model::RunSimulation, model.cpp:602-633)
 // is one call into the engine's C-ABI.  What a run with --scatter-grid writes afterwards (the grid, its views, its maps)
-// is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches, --lapse-windows, --ttimage,
-// --target-error, --envelope-shape, --envelope-fit, --slant-stack and --array-contrast run and write (the batched runs,
-// seis_NNN_err.octv, lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv, slantstack.octv, contrast.octv) is the
-// stage of batch_out.cpp.  This file
+// is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches and the batched products of
+// batch_products.hpp (--lapse-windows ... --array-contrast) run and write (the batched runs, seis_NNN_err.octv and each
+// product's file) is the stage of batch_out.cpp.  This file
 // makes both jobs, has them checked before the node is built, and calls each once to run and once to write.
 //
 // Differences a user can see: `--seed=S`, `--gpus=N` / `--devices=a,b,...`, `--scatter-grid=...`, `--error-batches=B`,
@@ -129,7 +128,7 @@ struct StdoutToStderr {
 };
 
 // What a simulation run hands back: the summed result with the arrays it points into, the report stream where one
-// was asked for, and what a batched run made beside them (batch_out.hpp).  `total` points into `energy` and `counts`:
+// was asked for (what a batched run made beside them stays with its job, batch_out.hpp).  `total` points into `energy` and `counts`:
 // the struct moves (the vectors keep their arrays) and cannot be copied.
 struct SimulationOutput {
   r3d_result total{};
@@ -137,7 +136,6 @@ struct SimulationOutput {
   std::vector<uint64_t> counts;
   std::vector<r3d_event> events;
   uint64_t events_dropped = 0;
-  BatchProducts batch;
   SimulationOutput() = default;
   SimulationOutput(const SimulationOutput&) = delete;
   SimulationOutput& operator=(const SimulationOutput&) = delete;
@@ -163,7 +161,7 @@ void read_reports(const std::vector<r3d_engine*>& engines, const std::vector<uin
 // grids are then added by frame (r3d_volume_reduce_by_frame: every engine ends with the job's counts for its share of
 // the frames) and handed to the output stage (scatter_out.hpp).  A batch job (batch_out.hpp) runs in the plain run's place.
 SimulationOutput run_simulation(const Model& model, const MissionParams& mission, r3d_node* node, uint32_t report_mask,
-                                const GridJob& grid, const BatchJob& batch) {
+                                const GridJob& grid, BatchJob& batch) {
   const r3d_model_desc& d = model.Desc();
   const uint64_t n = (uint64_t)std::max(0L, model.NumPhonons()), seed = mission.Seed;
   const int gpus = r3d_node_size(node);
@@ -183,8 +181,8 @@ SimulationOutput run_simulation(const Model& model, const MissionParams& mission
     if (report_mask && r3d_engine_set_event_log(e, report_mask, caps[g])) throw Runtime(r3d_last_error());
     if (grid.on && r3d_engine_set_volume(e, &grid.desc)) throw Runtime(r3d_last_error());
   }
-  if (batch.kind != BatchJob::NONE) {
-    out.batch = run_batch_job(batch, d, node, n, seed, out.total);
+  if (batch.kind != BatchKind::NONE) {
+    run_batch_job(batch, d, node, n, seed, out.total);
   } else if (r3d_node_run(node, n, 0, seed, &out.total)) {
     throw Runtime(r3d_last_error());
   }
@@ -328,8 +326,8 @@ int main(int argc, char* argv[]) {
         for (int g = 0; g < std::max(1, mission.Gpus); g++) mission.Devices.push_back(g);
       const std::vector<int>& devices = mission.Devices;
       // what the run is asked for beyond its seismograms is made into jobs and checked here: a refusal needs no device
-      const BatchJob batch = make_batch_job(mission, model, par);
-      check_batch_job(batch, devices.size(), report_mask);
+      const std::unique_ptr<BatchJob> batch = make_batch_job(mission, model, par);
+      check_batch_job(*batch, devices.size(), report_mask);
       const GridJob grid = make_grid_job(mission, par);
       check_grid_job(grid, devices.size());
       NodeHolder held;
@@ -355,7 +353,7 @@ int main(int argc, char* argv[]) {
       phase = "during simulation execution:";
       if (mission.bRunSim) {
         std::cout << "@@ __BEGINNING_SIMULATION__" << std::endl;
-        const SimulationOutput run = run_simulation(model, mission, held.node, report_mask, grid, batch);
+        const SimulationOutput run = run_simulation(model, mission, held.node, report_mask, grid, *batch);
         if (report_mask) {   // the reference writes them as they happen: stdout, or --report-file
           if (mission.ReportFile.empty()) {
             OutputReports(run.events.data(), run.events.size(), std::cout);
@@ -370,7 +368,7 @@ int main(int argc, char* argv[]) {
         // seis_traces_asc.dat is opened in the CWD whatever --output-dir says (dataout.hpp:332)
         std::ofstream trace("seis_traces_asc.dat");
         OutputPostSimSummary(model, run.total, mission.OutputDir, std::cout, trace);
-        write_batch_outputs(batch, model, run.batch);
+        write_batch_outputs(*batch, model);
       }
     }
   } catch (std::exception& e) {
