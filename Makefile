@@ -63,16 +63,18 @@ ENGINE_HDR := $(wildcard $(CSRC)/*.h) include/r3d.h
 #          window -- with jackknife errors (r3d_slant_shifts, r3d_slant_stack, r3d_run_batched_slant_stack)
 #   contrasts  the contrast of two runs along a receiver array -- per pixel, per window, per region of the array -- with the
 #          two-sample jackknife over both runs' batches (r3d_array_contrast, r3d_run_batched_contrast, r3d_contrast_decibel)
-ADDONS := stats views maps arrays precision shapes fits beams contrasts
+#   bands  bootstrap percentile bands of the envelope and its six shape numbers: the batches resampled R times, order
+#          statistics per bin and number (r3d_bootstrap_counts, r3d_envelope_bands, r3d_run_batched_envelope_bands)
+ADDONS := stats views maps arrays precision shapes fits beams contrasts bands
 addon_src = $(wildcard radiative3d_amd/$(1)/*.hip)
 # (arrays/ takes the bin energy and the strand constants from stats/r3d_window_sums.h; shapes/ those and the scans, the
 # running maximum and the jackknife from arrays/r3d_array_image.h; fits/ all of that and every header of shapes/: the rows
 # of a receiver with their smoothing rule, r3d_envelope_rows.h, and the shape's arithmetic; beams/ and contrasts/ the same
-# headers as fits/)
+# headers as fits/, and so does bands/)
 addon_hdr = $(wildcard radiative3d_amd/$(1)/*.h) $(COMMON)/r3d_entry.h include/r3d.h $(if $(filter arrays,$(1)),radiative3d_amd/stats/r3d_window_sums.h) \
             $(if $(filter shapes,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h) \
             $(if $(filter fits,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h $(wildcard radiative3d_amd/shapes/*.h)) \
-            $(if $(filter beams contrasts,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h $(wildcard radiative3d_amd/shapes/*.h))
+            $(if $(filter beams contrasts bands,$(1)),radiative3d_amd/stats/r3d_window_sums.h radiative3d_amd/arrays/r3d_array_image.h $(wildcard radiative3d_amd/shapes/*.h))
 OBJDIR   := build/obj
 
 # (the default goal is the first target of the file: it has to come before the generated object rules)

@@ -954,6 +954,79 @@ int r3d_run_batched_envelope_shape(r3d_engine* e, uint64_t n, uint64_t first_id,
                                    r3d_result* out, double* energy_se, double* counts_se, const r3d_envelope_spec* spec,
                                    r3d_envelope_result* res);
 
+/* ---- bootstrap percentile bands of the envelope and its six numbers ----------------------
+ * An INTERVAL where the calls above give value +- se: a lower and an upper curve round a receiver's smoothed envelope that
+ * stay non-negative and follow the skew of heavy-tailed bins, and an interval for each of the six numbers that is valid
+ * where the statistic jumps (tp, tq), which their jackknife is not.  The bootstrap over the batches: the B batch blocks are
+ * resampled with replacement R times, the statistic is made again per replicate, percentiles are taken.
+ * radiative3d_amd/bands/r3d_envelope_bands.h has the arithmetic:
+ *     COUNTS: for replicate r < R and draw d < B, word (d & 3) of Philox4x32-10 with counter {r, d >> 2, 0, 0x626F6F74} and
+ *       key {seed low, seed high} draws batch j = ((uint64)word * B) >> 32; c[r][j] counts the draws on j (sum_j = B).  The
+ *       same counts for every receiver and bin: one resample reweights whole batches.
+ *     ROWS over a receiver's window, e_j as r3d_envelope_shape takes it: t*_r[k] = acc after acc = +0.0; acc = acc +
+ *       (double)c[r][j] * e_j for j = 0 .. B-1 (product and add each rounded, in that order); then `smooth` passes and the
+ *       six numbers exactly as r3d_envelope_shape makes them of a row.  Energy rows only.
+ *     POINT ESTIMATE: the envelope and six numbers of the total row, the bits r3d_envelope_shape writes.
+ *     ORDER STATISTICS of each window bin's R values and each number's R values, tail T (0 <= 2 T < R): D values are not
+ *       NaN, s_0 <= .. <= s_{D-1} they sorted, T_d = ((uint64)T * D) / R, lo = s_{T_d}, hi = s_{D-1-T_d}; D == 0: both NaN;
+ *       defined = D.  Bins outside the window, and a window that is not b0 <= b1 <= n_bins (never read through, counted in
+ *       bad): +0.0 in the envelope and both bands.
+ *     The values are bit-defined (host, device, every launch geometry).  The interval's statistical coverage is
+ *       approximate, slightly narrow for small B; no rounding bound is claimed for a lo / hi of tp or tq.
+ *
+ * r3d_bootstrap_counts: host only; counts [R][B] bytes WRITTEN.  Refused: null counts, B outside 2 .. 64, R outside 1 ..
+ * R3D_BANDS_MAX_REPLICATES.  r3d_bootstrap_counts_device: the same counts made by the kernel the bands use, into d_counts
+ * [R][B] on `device`, asynchronous on `stream`; the same refusals.
+ *
+ * r3d_envelope_bands: device level, like r3d_envelope_shape -- B batch-major blocks d_batch_energy [B][n_seis][n_bins][5] on
+ * `device`, only read; spec->d_bins [A][2] on the device.  WRITTEN, every entry by one work-item: d_envelope, d_envelope_lo,
+ * d_envelope_hi [A][n_bins]; d_shape, d_shape_lo, d_shape_hi [A][6]; d_defined [A][6] (u32); d_bad (one uint64).  EVERY
+ * output may be NULL and is then untouched.  The rows pass through scratch taken from and returned to the stream's memory
+ * pool: 2 (R + 1) n_bins + 6 R doubles per workgroup, the workgroups cut so that a launch stays under 2^29 doubles.
+ * Asynchronous on `stream`.  REFUSED (non-zero, r3d_last_error with the entry's name in front, nothing enqueued, no buffer
+ * touched; all checked before any HIP call): null blocks or spec, a size mismatch, n_bins == 0, last < first, last >=
+ * n_seismometers, a weight that is negative or not finite, B outside 2 .. 64, R outside 1 .. R3D_BANDS_MAX_REPLICATES,
+ * 2 tail >= R, smooth > R3D_ENVELOPE_MAX_SMOOTH, null bins, one receiver's scratch above the cap.
+ *
+ * r3d_run_batched_envelope_bands: r3d_run_batched (same arguments, refusals, out / energy_se / counts_se) that keeps its
+ * batch blocks on the device, makes the bands there and reads back only the arrays of *res, all WRITTEN (each may be NULL).
+ * For THIS call spec->d_bins is a HOST array, checked here as r3d_run_batched_envelope_shape checks its own; a spec whose
+ * n_seismometers / n_bins are not the model's, a null res or one of another size are refused.  A refusal touches nothing.
+ * Out of scope: amplitude envelopes, bands of the misfit, slant-stack or contrast numbers, combining this call in one run
+ * with another batched product, a job sharded over several devices.                                                      */
+#define R3D_BANDS_MAX_REPLICATES 4096
+typedef struct r3d_bands_spec {
+  uint32_t size;                    /* sizeof(r3d_bands_spec): a mismatch is refused           */
+  uint32_t n_seismometers, n_bins;
+  uint32_t first, last;             /* the array: seismometers first .. last                   */
+  uint32_t smooth;                  /* three-point passes, 0 .. R3D_ENVELOPE_MAX_SMOOTH        */
+  uint32_t n_replicates;            /* R, 1 .. R3D_BANDS_MAX_REPLICATES                        */
+  uint32_t tail;                    /* T, 2 T < R: lo = s_{T_d}, hi = s_{D-1-T_d}              */
+  const uint32_t* d_bins;           /* [A][2] b0, b1; device (the run: host)                   */
+  uint64_t seed;                    /* of the resampling counts                                */
+  double   weight[R3D_N_ENERGY];
+} r3d_bands_spec;
+typedef struct r3d_bands_result {
+  uint32_t size;                    /* sizeof(r3d_bands_result)                                */
+  uint32_t pad_;
+  double*   envelope;               /* [A][n_bins]  each may be NULL                           */
+  double*   envelope_lo;
+  double*   envelope_hi;
+  double*   shape;                  /* [A][6]                                                  */
+  double*   shape_lo;
+  double*   shape_hi;
+  uint32_t* defined;                /* [A][6]                                                  */
+} r3d_bands_result;
+int r3d_bootstrap_counts(uint64_t seed, uint32_t n_batches, uint32_t n_replicates, uint8_t* counts);
+int r3d_bootstrap_counts_device(int device, uint64_t seed, uint32_t n_batches, uint32_t n_replicates, uint8_t* d_counts,
+                                void* stream);
+int r3d_envelope_bands(int device, uint32_t n_batches, const double* d_batch_energy, const r3d_bands_spec* spec,
+                       double* d_envelope, double* d_envelope_lo, double* d_envelope_hi, double* d_shape, double* d_shape_lo,
+                       double* d_shape_hi, uint32_t* d_defined, uint64_t* d_bad, void* stream);
+int r3d_run_batched_envelope_bands(r3d_engine* e, uint64_t n, uint64_t first_id, uint64_t seed, uint32_t n_batches,
+                                   r3d_result* out, double* energy_se, double* counts_se, const r3d_bands_spec* spec,
+                                   r3d_bands_result* res);
+
 /* ---- the envelope misfit against observed data with jackknife errors ---------------------
  * The step the envelope numbers above are for: given an OBSERVED envelope per array receiver, how far the synthetic one is
  * from it -- what vis/seisplot/envcompare.m shows by eye (smoothed, peak-normalised, drawn over each other, a hand-picked

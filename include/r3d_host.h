@@ -235,6 +235,49 @@ int r3dh_envshape_request(const r3dh_model* m, r3dh_envshape_opts* rq);
 int r3dh_envshape_plan(const r3dh_model* m, const r3dh_envshape_opts* rq, double* distances, uint32_t* bins, int32_t* clipped);
 int r3dh_write_envshape(const r3dh_model* m, const r3dh_envshape_opts* rq, const r3dh_envshape_result* res, const char* path);
 
+/* --envelope-bands=R,LEVEL[,V,T0,O,E[,SMOOTH]] [--bands-array=FIRST,LAST] [--bands-axes=X,Y,Z] [--bands-seed=S] in the model's
+ * arguments (the last three refused without the first; the first without --error-batches and with --job-error-batches, every
+ * earlier batched product or --reports): per receiver of an array the bootstrap percentile bands of its smoothed envelope
+ * and of the six shape numbers (r3d.h r3d_run_batched_envelope_bands): the batches resampled R times, tail = floor((0.5 (1 -
+ * LEVEL)) R) replicates left outside either band.  The window, its defaults and SMOOTH are --envelope-shape's.
+ * r3dh_envbands_request: returns 1 and fills *rq when the bands were asked for, 0 otherwise; -1 (r3dh_last_error) if
+ * --bands-array's LAST is not a seismometer of the model.
+ * r3dh_envbands_plan: r3dh_envshape_plan's distances [A], bins [A][2] and clipped [A] for the request's array and window.
+ * r3dh_write_envbands: envbands.octv-style GNU/Octave text at 17 digits to `path`, rows the array's receivers in order:
+ * BandsSeismometers [A], BandsBatches, BandsReplicates, BandsTail, BandsLevel (the achieved 1 - 2 tail / R), BandsSeed,
+ * BandsDistances [A], BandsPhaseEdge [2], BandsWindow [2], BandsAxes [3], BandsSmooth, BandsNumBins, BandsBins [A][2],
+ * BandsClipped [A]; the six numbers in envshape.octv's units, each [A] with _lo, _hi and _defined (the replicates whose
+ * number is not NaN): BandsEnergy, BandsPeak, BandsPeakTime, BandsHalfTime, BandsCentroid, BandsWidth; and BandsEnvelope,
+ * BandsEnvelope_lo, BandsEnvelope_hi [A][n_bins] (+0.0 outside the window).  Returns 0 ok.                              */
+typedef struct r3dh_envbands_opts {
+  uint32_t size;                 /* sizeof(r3dh_envbands_opts)                                   */
+  uint32_t first, last;          /* the array: seismometers first .. last                        */
+  uint32_t smooth;               /* three-point passes, 0 .. 64                                  */
+  uint32_t n_replicates, tail;   /* R and floor((0.5 (1 - level)) R)                             */
+  uint64_t seed;                 /* of the resampling counts                                     */
+  double   level;                /* LEVEL as given                                               */
+  double   phase_edge[2];        /* v, t0                                                         */
+  double   window[2];            /* o, e: seconds behind the edge; e = NaN: to the trace's end   */
+  double   axes[3];              /* weights of the trace's X, Y, Z                               */
+} r3dh_envbands_opts;
+typedef struct r3dh_envbands_result {
+  uint32_t size;                 /* sizeof(r3dh_envbands_result)                                 */
+  uint32_t n_batches;
+  const double*   distances;     /* [A]     r3dh_envbands_plan's                                 */
+  const uint32_t* bins;          /* [A][2]                                                       */
+  const int32_t*  clipped;       /* [A]                                                          */
+  const double*   envelope;      /* [A][n_bins]  as r3d_run_batched_envelope_bands gives them    */
+  const double*   envelope_lo;   /* [A][n_bins]                                                  */
+  const double*   envelope_hi;   /* [A][n_bins]                                                  */
+  const double*   shape;         /* [A][6]  in bins                                              */
+  const double*   shape_lo;      /* [A][6]                                                       */
+  const double*   shape_hi;      /* [A][6]                                                       */
+  const uint32_t* defined;       /* [A][6]                                                       */
+} r3dh_envbands_result;
+int r3dh_envbands_request(const r3dh_model* m, r3dh_envbands_opts* rq);
+int r3dh_envbands_plan(const r3dh_model* m, const r3dh_envbands_opts* rq, double* distances, uint32_t* bins, int32_t* clipped);
+int r3dh_write_envbands(const r3dh_model* m, const r3dh_envbands_opts* rq, const r3dh_envbands_result* res, const char* path);
+
 /* --envelope-fit=FILE[,V,T0,O,E[,SMOOTH[,OBSSMOOTH[,MAXLAG_SECONDS]]]] [--envelope-fit-array=FIRST,LAST]
  * [--envelope-fit-axes=X,Y,Z] [--envelope-fit-energy] in the model's arguments (the last three refused without the first; the
  * first without --error-batches and with --job-error-batches, --lapse-windows, --ttimage, --target-error, --envelope-shape or

@@ -152,6 +152,23 @@ class EnvelopeResult(C.Structure):
                 ("lit", C.c_void_p)]
 
 
+R3D_BANDS_MAX_REPLICATES = 4096
+
+
+class BandsSpec(C.Structure):
+    """include/r3d.h r3d_bands_spec"""
+    _fields_ = [("size", C.c_uint32), ("n_seismometers", C.c_uint32), ("n_bins", C.c_uint32), ("first", C.c_uint32),
+                ("last", C.c_uint32), ("smooth", C.c_uint32), ("n_replicates", C.c_uint32), ("tail", C.c_uint32),
+                ("d_bins", C.c_void_p), ("seed", C.c_uint64), ("weight", C.c_double * R3D_N_ENERGY)]
+
+
+class BandsResult(C.Structure):
+    """include/r3d.h r3d_bands_result"""
+    _fields_ = [("size", C.c_uint32), ("pad_", C.c_uint32), ("envelope", C.c_void_p), ("envelope_lo", C.c_void_p),
+                ("envelope_hi", C.c_void_p), ("shape", C.c_void_p), ("shape_lo", C.c_void_p), ("shape_hi", C.c_void_p),
+                ("defined", C.c_void_p)]
+
+
 R3D_MISFIT_N, R3D_MISFIT_MAX_LAG = 6, 64
 
 
@@ -254,6 +271,20 @@ class LapseResult(C.Structure):
     _fields_ = [("size", C.c_uint32), ("n_batches", C.c_uint32), ("distances", C.c_void_p), ("bins", C.c_void_p),
                 ("clipped", C.c_void_p), ("window_energy", C.c_void_p), ("window_se", C.c_void_p),
                 ("window_counts", C.c_void_p), ("batch_window_energy", C.c_void_p)]
+
+
+class EnvBandsOpts(C.Structure):
+    """include/r3d_host.h r3dh_envbands_opts"""
+    _fields_ = [("size", C.c_uint32), ("first", C.c_uint32), ("last", C.c_uint32), ("smooth", C.c_uint32),
+                ("n_replicates", C.c_uint32), ("tail", C.c_uint32), ("seed", C.c_uint64), ("level", C.c_double),
+                ("phase_edge", C.c_double * 2), ("window", C.c_double * 2), ("axes", C.c_double * 3)]
+
+
+class EnvBandsResult(C.Structure):
+    """include/r3d_host.h r3dh_envbands_result"""
+    _fields_ = [("size", C.c_uint32), ("n_batches", C.c_uint32), ("distances", C.c_void_p), ("bins", C.c_void_p),
+                ("clipped", C.c_void_p), ("envelope", C.c_void_p), ("envelope_lo", C.c_void_p), ("envelope_hi", C.c_void_p),
+                ("shape", C.c_void_p), ("shape_lo", C.c_void_p), ("shape_hi", C.c_void_p), ("defined", C.c_void_p)]
 
 
 class EnvShapeOpts(C.Structure):
@@ -423,6 +454,12 @@ def host_lib():
         L.r3dh_envshape_plan.argtypes = [C.c_void_p, C.POINTER(EnvShapeOpts), _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
         L.r3dh_write_envshape.restype = C.c_int
         L.r3dh_write_envshape.argtypes = [C.c_void_p, C.POINTER(EnvShapeOpts), C.POINTER(EnvShapeResult), C.c_char_p]
+        L.r3dh_envbands_request.restype = C.c_int
+        L.r3dh_envbands_request.argtypes = [C.c_void_p, C.POINTER(EnvBandsOpts)]
+        L.r3dh_envbands_plan.restype = C.c_int
+        L.r3dh_envbands_plan.argtypes = [C.c_void_p, C.POINTER(EnvBandsOpts), _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+        L.r3dh_write_envbands.restype = C.c_int
+        L.r3dh_write_envbands.argtypes = [C.c_void_p, C.POINTER(EnvBandsOpts), C.POINTER(EnvBandsResult), C.c_char_p]
         L.r3dh_slant_request.restype = C.c_int
         L.r3dh_slant_request.argtypes = [C.c_void_p, C.POINTER(SlantOpts)]
         L.r3dh_slant_plan.restype = C.c_int
@@ -647,6 +684,16 @@ def hip_lib(reproducible=False, path=None):
         L.r3d_run_batched_envelope_shape.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                                      C.POINTER(Result), _dp, _dp, C.POINTER(EnvelopeSpec),
                                                      C.POINTER(EnvelopeResult)]
+        L.r3d_bootstrap_counts.restype = C.c_int
+        L.r3d_bootstrap_counts.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.r3d_bootstrap_counts_device.restype = C.c_int
+        L.r3d_bootstrap_counts_device.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.r3d_envelope_bands.restype = C.c_int
+        L.r3d_envelope_bands.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.POINTER(BandsSpec)] + [C.c_void_p] * 9
+        L.r3d_run_batched_envelope_bands.restype = C.c_int
+        L.r3d_run_batched_envelope_bands.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                     C.POINTER(Result), _dp, _dp, C.POINTER(BandsSpec),
+                                                     C.POINTER(BandsResult)]
         L.r3d_envelope_misfit.restype = C.c_int
         L.r3d_envelope_misfit.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.POINTER(MisfitSpec)] + [C.c_void_p] * 9
         L.r3d_run_batched_envelope_misfit.restype = C.c_int

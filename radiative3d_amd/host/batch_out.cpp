@@ -368,6 +368,49 @@ struct ContrastJob : BatchJob {
   }
 };
 
+// --envelope-bands: the bootstrap percentile bands of every array receiver's smoothed envelope and of its six numbers, made
+// on the device (include/r3d.h r3d_run_batched_envelope_bands).
+struct BandsJob : BatchJob {
+  r3dh_envbands_opts opts{};
+  std::vector<double> distances;   // the plan, [A] receivers (include/r3d_host.h r3dh_envbands_plan)
+  std::vector<uint32_t> bins;
+  std::vector<int32_t> clipped;
+  std::vector<double> envelope, envelope_lo, envelope_hi, shape, shape_lo, shape_hi;
+  std::vector<uint32_t> defined;
+
+  BandsJob(const MissionParams& mission, const Model& model) {
+    EnvBandsRequest(model, mission, &opts);
+    const size_t A = (size_t)opts.last - opts.first + 1;
+    distances.assign(A, 0.0), bins.assign(2 * A, 0), clipped.assign(A, 0);
+    EnvBandsPlan(model, opts, distances.data(), bins.data(), clipped.data());
+  }
+  void run(const r3d_model_desc& d, r3d_node* node, uint64_t n, uint64_t seed, r3d_result& total) override {
+    const size_t A = (size_t)opts.last - opts.first + 1, px = A * d.params.n_bins, six = A * R3D_ENVELOPE_N_SHAPE;
+    r3d_bands_spec spec{};
+    spec.size = sizeof spec, spec.n_seismometers = (uint32_t)d.n_seismometers, spec.n_bins = d.params.n_bins;
+    spec.first = opts.first, spec.last = opts.last, spec.smooth = opts.smooth;
+    spec.n_replicates = opts.n_replicates, spec.tail = opts.tail, spec.seed = opts.seed;
+    spec.d_bins = bins.data();   // (for this call: on the host)
+    for (int k = 0; k < 3; k++) spec.weight[k] = opts.axes[k];
+    envelope.assign(px, 0.0), envelope_lo.assign(px, 0.0), envelope_hi.assign(px, 0.0);
+    shape.assign(six, 0.0), shape_lo.assign(six, 0.0), shape_hi.assign(six, 0.0), defined.assign(six, 0);
+    r3d_bands_result res{};
+    res.size = sizeof res, res.envelope = envelope.data(), res.envelope_lo = envelope_lo.data(), res.envelope_hi = envelope_hi.data();
+    res.shape = shape.data(), res.shape_lo = shape_lo.data(), res.shape_hi = shape_hi.data(), res.defined = defined.data();
+    if (r3d_run_batched_envelope_bands(r3d_node_engine(node, 0), n, 0, seed, batches, &total, energy_se.data(), counts_se.data(), &spec,
+                                       &res))
+      throw Runtime(r3d_last_error());
+  }
+  void write(const Model& model, std::ostream& f) const override {
+    r3dh_envbands_result res{};
+    res.size = sizeof res, res.n_batches = batches;
+    res.distances = distances.data(), res.bins = bins.data(), res.clipped = clipped.data();
+    res.envelope = envelope.data(), res.envelope_lo = envelope_lo.data(), res.envelope_hi = envelope_hi.data();
+    res.shape = shape.data(), res.shape_lo = shape_lo.data(), res.shape_hi = shape_hi.data(), res.defined = defined.data();
+    OutputEnvBands(model, opts, res, f);
+  }
+};
+
 // The record of batch_products.hpp that the job's kind has (null: a plain kind).
 const BatchProduct* product_of(BatchKind kind) {
   for (const BatchProduct& p : kBatchProducts)
@@ -405,6 +448,7 @@ std::unique_ptr<BatchJob> make_batch_job(const MissionParams& mission, const Mod
     case BatchKind::FIT: job = std::make_unique<FitJob>(mission, model); break;
     case BatchKind::SLANT: job = std::make_unique<SlantJob>(mission, model); break;
     case BatchKind::CONTRAST: job = std::make_unique<ContrastJob>(mission, model, par); break;
+    case BatchKind::BANDS: job = std::make_unique<BandsJob>(mission, model); break;
     default: job = std::make_unique<BatchJob>(); break;
   }
   job->kind = kind, job->dir = mission.OutputDir;

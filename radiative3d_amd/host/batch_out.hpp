@@ -1,7 +1,7 @@
 // batch_out.hpp -- the batched-run stage of ./main: what --error-batches, --job-error-batches and the batched products of
 // batch_products.hpp (--lapse-windows, --ttimage, --target-error, --envelope-shape, --envelope-fit, --slant-stack,
 // --array-contrast) run in place of the plain run, and what they write after it (seis_NNN_err.octv, then the product's file:
-// lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv, slantstack.octv, contrast.octv).
+// lapse.octv, ttimage.octv, precision.octv, envshape.octv, envfit.octv, slantstack.octv, contrast.octv, envbands.octv).
 // Compiled into ./main beside main.cpp (it calls r3d_run_batched* and r3d_node_run_batched of the engine's library, so
 // it is no part of libr3d_host.so); its row arithmetic is batch_plan.hpp.
 #ifndef R3DH_BATCH_OUT_HPP_

@@ -11,7 +11,7 @@
 
 // What a batched run is.  ERRORS: --error-batches alone; JOB_ERRORS: --job-error-batches; the others: --error-batches with the
 // product of that record below.
-enum class BatchKind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION, SHAPE, FIT, SLANT, CONTRAST };
+enum class BatchKind { NONE, ERRORS, LAPSE, IMAGE, JOB_ERRORS, PRECISION, SHAPE, FIT, SLANT, CONTRAST, BANDS };
 
 struct BatchProduct {
   const char* option;
@@ -60,6 +60,9 @@ inline const BatchProduct kBatchProducts[] = {
      "how that contrast is made", "the contrast is made where ONE device's batch blocks of both runs lie", "r3d_run_batched_contrast",
      "contrast", "the standard errors of the contrast are two-sample jackknives over the B batches of either run.",
      "the contrast needs both runs' batch blocks", true, "both runs' batch blocks must lie on the same device"},
+    {"--envelope-bands", &MissionParams::bBands, &MissionParams::BandsCompanion, BatchKind::BANDS, "envbands.octv",
+     "how those bands are made", "the bands are made where ONE device's batch blocks lie", "r3d_run_batched_envelope_bands", "bands",
+     "the bands are percentiles over resamples of the B batches.", "the bands need one run's batch blocks", true, nullptr},
 };
 
 #endif

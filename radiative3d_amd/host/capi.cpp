@@ -234,6 +234,25 @@ int r3dh_write_envshape(const r3dh_model* m, const r3dh_envshape_opts* rq, const
   return write_file(path, [&](std::ostream& f) { OutputEnvShape(*m->model, *rq, *res, f); });
 }
 
+int r3dh_envbands_request(const r3dh_model* m, r3dh_envbands_opts* rq) {
+  if (!m || !m->mission.bBands) return 0;
+  if (!rq) return 1;
+  return guarded(1, -1, [&] { EnvBandsRequest(*m->model, m->mission, rq); });
+}
+
+int r3dh_envbands_plan(const r3dh_model* m, const r3dh_envbands_opts* rq, double* distances, uint32_t* bins, int32_t* clipped) {
+  if (!m || !rq || !distances || !bins || !clipped) return g_error = "r3dh_envbands_plan: null argument", 1;
+  return guarded(0, 1, [&] { EnvBandsPlan(*m->model, *rq, distances, bins, clipped); });
+}
+
+int r3dh_write_envbands(const r3dh_model* m, const r3dh_envbands_opts* rq, const r3dh_envbands_result* res, const char* path) {
+  if (!m || !rq || !res || !path) return g_error = "r3dh_write_envbands: null argument", 1;
+  if (!res->distances || !res->bins || !res->clipped || !res->envelope || !res->envelope_lo || !res->envelope_hi || !res->shape ||
+      !res->shape_lo || !res->shape_hi || !res->defined)
+    return g_error = "r3dh_write_envbands: null array in the result", 1;
+  return write_file(path, [&](std::ostream& f) { OutputEnvBands(*m->model, *rq, *res, f); });
+}
+
 int r3dh_slant_request(const r3dh_model* m, r3dh_slant_opts* rq) {
   if (!m || !m->mission.bSlant) return 0;
   if (!rq) return 1;

@@ -28,7 +28,8 @@ enum OptID {
   OPTX_ENVFIT, OPTX_ENVFIT_ARRAY, OPTX_ENVFIT_AXES, OPTX_ENVFIT_ENERGY,
   OPTX_SLANT, OPTX_SLANT_ARRAY, OPTX_SLANT_AXES, OPTX_SLANT_ENERGY, OPTX_SLANT_RANGEPOWER, OPTX_SLANT_WINDOWS,
   OPTX_CONTRAST, OPTX_CONTRAST_ARGS, OPTX_CONTRAST_ARRAY, OPTX_CONTRAST_AXES, OPTX_CONTRAST_WINDOWS, OPTX_CONTRAST_REGIONS,
-  OPTX_CONTRAST_RANGEPOWER, OPTX_CONTRAST_SEED, OPTX_CONTRAST_NUMBER
+  OPTX_CONTRAST_RANGEPOWER, OPTX_CONTRAST_SEED, OPTX_CONTRAST_NUMBER,
+  OPTX_BANDS, OPTX_BANDS_ARRAY, OPTX_BANDS_AXES, OPTX_BANDS_SEED
 };
 
 const std::map<std::string, OptID>& option_table() {
@@ -76,7 +77,9 @@ const std::map<std::string, OptID>& option_table() {
       {"--array-contrast", OPTX_CONTRAST}, {"--contrast-model-args", OPTX_CONTRAST_ARGS}, {"--contrast-array", OPTX_CONTRAST_ARRAY},
       {"--contrast-axes", OPTX_CONTRAST_AXES}, {"--contrast-windows", OPTX_CONTRAST_WINDOWS},
       {"--contrast-regions", OPTX_CONTRAST_REGIONS}, {"--contrast-range-power", OPTX_CONTRAST_RANGEPOWER},
-      {"--contrast-seed", OPTX_CONTRAST_SEED}, {"--contrast-num-phonons", OPTX_CONTRAST_NUMBER}};
+      {"--contrast-seed", OPTX_CONTRAST_SEED}, {"--contrast-num-phonons", OPTX_CONTRAST_NUMBER},
+      {"--envelope-bands", OPTX_BANDS}, {"--bands-array", OPTX_BANDS_ARRAY}, {"--bands-axes", OPTX_BANDS_AXES},
+      {"--bands-seed", OPTX_BANDS_SEED}};
   return t;
 }
 
@@ -666,6 +669,54 @@ void ParseCommandLine(const std::vector<std::string>& tokens, ModelParams& par,
         mission.ContrastNumPhonons = o.integer();
         if (mission.ContrastNumPhonons < 0) throw Runtime("--contrast-num-phonons=N: the test run's histories cannot be negative.");
         mission.ContrastCompanion = "--contrast-num-phonons";
+        break;
+      case OPTX_BANDS: {
+        static const char* const form = "--envelope-bands=R,LEVEL[,V,T0,O,E[,SMOOTH]]: ";
+        const long replicates = o.integer();
+        mission.BandsLevel = o.real();
+        long smooth = (long)mission.BandsSmooth;
+        if (o.has()) {
+          for (int k = 0; k < 2; k++) mission.BandsEdge[k] = o.real();
+          for (int k = 0; k < 2; k++) mission.BandsWindow[k] = o.real();
+          if (o.has()) smooth = o.integer();
+        }
+        if (replicates < 1 || replicates > 4096)
+          throw Runtime(std::string(form) + "R, the resamples of the batches, must be 1 .. 4096 (got " + std::to_string(replicates) + ").");
+        if (!(mission.BandsLevel > 0 && mission.BandsLevel < 1))
+          throw Runtime(std::string(form) + "LEVEL, the share of the replicates between the bands, must lie in (0, 1).");
+        const double tail = std::floor((0.5 * (1.0 - mission.BandsLevel)) * (double)replicates);
+        if (2 * tail >= (double)replicates)
+          throw Runtime(std::string(form) + "the tail floor((0.5 (1 - LEVEL)) R) = " + std::to_string((long)tail) +
+                        " leaves nothing between the bands of " + std::to_string(replicates) + " replicates.");
+        const double* w = mission.BandsWindow;
+        if (!(mission.BandsEdge[0] > 0) || !std::isfinite(mission.BandsEdge[0]) || !std::isfinite(mission.BandsEdge[1]) ||
+            !std::isfinite(w[0]) || (!std::isnan(w[1]) && (!std::isfinite(w[1]) || !(w[1] >= w[0]))))
+          throw Runtime(std::string(form) + "the phase velocity V must be positive, the window's end E not before its start O, and "
+                        "every number finite.");
+        if (smooth < 0 || smooth > 64)
+          throw Runtime(std::string(form) + "SMOOTH, the three-point smoothing passes, must be 0 .. 64 (got " + std::to_string(smooth) +
+                        ").");
+        mission.BandsReplicates = (unsigned)replicates, mission.BandsTail = (unsigned)tail, mission.BandsSmooth = (unsigned)smooth;
+        mission.bBands = true;
+        break;
+      }
+      case OPTX_BANDS_ARRAY:
+        mission.BandsArray[0] = o.integer();
+        mission.BandsArray[1] = o.integer();
+        if (mission.BandsArray[0] < 0 || mission.BandsArray[1] < mission.BandsArray[0])
+          throw Runtime("--bands-array=FIRST,LAST: seismometer indices with 0 <= FIRST <= LAST.");
+        mission.BandsCompanion = "--bands-array";
+        break;
+      case OPTX_BANDS_AXES:
+        for (int k = 0; k < 3; k++) mission.BandsAxes[k] = o.real();
+        for (int k = 0; k < 3; k++)
+          if (!std::isfinite(mission.BandsAxes[k]) || mission.BandsAxes[k] < 0)
+            throw Runtime("--bands-axes=X,Y,Z: the weights must be finite and not negative (the envelope's energies must not be).");
+        mission.BandsCompanion = "--bands-axes";
+        break;
+      case OPTX_BANDS_SEED:
+        mission.BandsSeed = (unsigned long)std::strtoull(o.text().c_str(), nullptr, 0);
+        mission.BandsCompanion = "--bands-seed";
         break;
       case OPTX_DEVTABLES: par.DeviceTables = true; break;
       case OPTX_HOSTTABLES: par.HostTables = true, par.DeviceTables = false; break;

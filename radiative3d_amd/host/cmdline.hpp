@@ -149,6 +149,17 @@ struct MissionParams {
   std::vector<double> ContrastRegions;    // R0, R1 pairs
   unsigned long ContrastSeed = 0;
   long ContrastNumPhonons = -1;           // < 0: the base run's
+  // --envelope-bands=R,LEVEL[,V,T0,O,E[,SMOOTH]]: per receiver of an array the bootstrap percentile bands of its smoothed
+  // envelope and of the six shape numbers -- the batches of --error-batches resampled R times (1 .. 4096), the tail
+  // floor((0.5 (1 - LEVEL)) R) of the replicates left outside either band (include/r3d.h r3d_run_batched_envelope_bands) --
+  // as envbands.octv.  The window and SMOOTH as --envelope-shape's.  --bands-array=FIRST,LAST the receivers (default all),
+  // --bands-axes=X,Y,Z the weights of the three trace axes, --bands-seed=S the seed of the resampling counts.
+  bool bBands = false;
+  const char* BandsCompanion = nullptr;   // one of the three that was given (they are refused without --envelope-bands)
+  unsigned BandsReplicates = 0, BandsTail = 0, BandsSmooth = 8;
+  double BandsLevel = 0.0, BandsEdge[2] = {3.6, 0.0}, BandsWindow[2] = {0.0, std::nan("")}, BandsAxes[3] = {1.0, 1.0, 1.0};
+  long BandsArray[2] = {0, -1};           // LAST < 0: through the last receiver
+  unsigned long BandsSeed = 0xB007;
   Text ScatterGridFile = "scattergrid";   // <name>.octv (header) + <name>.u32 (counters), under --output-dir
 };
 

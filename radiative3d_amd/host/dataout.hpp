@@ -67,6 +67,13 @@ void EnvShapeRequest(const Model& model, const MissionParams& mission, r3dh_envs
 void EnvShapePlan(const Model& model, const r3dh_envshape_opts& rq, double* distances, uint32_t* bins, int32_t* clipped);
 void OutputEnvShape(const Model& model, const r3dh_envshape_opts& rq, const r3dh_envshape_result& res, std::ostream& out);
 
+// The bootstrap bands of --envelope-bands (include/r3d_host.h has the request, the plan, the file's items): EnvBandsRequest
+// fills *rq from the mission (throws if --bands-array names a receiver the model does not have), EnvBandsPlan is the envelope
+// shape's plan for the request's array and window, OutputEnvBands writes the file's text.
+void EnvBandsRequest(const Model& model, const MissionParams& mission, r3dh_envbands_opts* rq);
+void EnvBandsPlan(const Model& model, const r3dh_envbands_opts& rq, double* distances, uint32_t* bins, int32_t* clipped);
+void OutputEnvBands(const Model& model, const r3dh_envbands_opts& rq, const r3dh_envbands_result& res, std::ostream& out);
+
 // The envelope misfit of --envelope-fit (include/r3d_host.h has the request, the plan, the file's items and the two plain
 // pieces).  ObservedToBins: r3dh_observed_to_bins' arithmetic (false, nothing written, for what it has no answer for).
 // OctaveItem / ReadOctaveText: the reader of the writer's own `scalar` and `matrix` blocks; throws, naming the variable, for

@@ -5,7 +5,7 @@
 // files.  The N-phonon loop itself (Model::RunSimulation, model.cpp:602-633)
 // is one call into the engine's C-ABI.  What a run with --scatter-grid writes afterwards (the grid, its views, its maps)
 // is the output stage of scatter_out.cpp; what --error-batches, --job-error-batches and the batched products of
-// batch_products.hpp (--lapse-windows ... --array-contrast) run and write (the batched runs, seis_NNN_err.octv and each
+// batch_products.hpp (--lapse-windows ... --envelope-bands) run and write (the batched runs, seis_NNN_err.octv and each
 // product's file) is the stage of batch_out.cpp.  This file
 // makes both jobs, has them checked before the node is built, and calls each once to run and once to write.
 //
@@ -14,7 +14,7 @@
 // (ttimage.octv), `--target-error` (a run that stops when its error bars are good enough; precision.octv) and
 // `--envelope-shape` (envshape.octv), `--envelope-fit` (the misfit against observed envelopes; envfit.octv) and `--slant-stack`
 // (the vespagram of a receiver array; slantstack.octv) and `--array-contrast` (a second model's run compared with this one's
-// along a receiver array; contrast.octv) are accepted
+// along a receiver array; contrast.octv) and `--envelope-bands` (bootstrap percentile bands of the envelopes; envbands.octv) are accepted
 // (the reference seeds from the clock, is single-process, has no event histogram and no error bars, and takes its phonon
 // count from a hand-tuned table); the `--reports` stream is written
 // after the run, grouped by history, where the reference writes its lines as they happen (the engine appends binary
@@ -291,7 +291,13 @@ int main(int argc, char* argv[]) {
               << "distance ranges in km, at most eight (with --contrast-windows)  --contrast-range-power=Q: receiver i times\n"
               << "(r_i / r_ref)^Q in a region's sums (default 0)  --contrast-seed=S (default --seed + 1)  --contrast-num-phonons=N\n"
               << "(default: the base's; the test side is scaled by N_base / N).  seis_NNN.octv and seis_NNN_err.octv are the base run's;\n"
-              << "the test run's traces are not written.  Not in one run with another batched product or --reports\n\n";
+              << "the test run's traces are not written.  Not in one run with another batched product or --reports\n"
+              << "--envelope-bands=R,LEVEL[,V,T0,O,E[,SMOOTH]] (with --error-batches; window and SMOOTH as --envelope-shape): per\n"
+              << "receiver of an array the bootstrap percentile bands of its smoothed envelope and of the six shape numbers -- the\n"
+              << "batches resampled R times (1 .. 4096) on the GPU, floor((0.5 (1 - LEVEL)) R) replicates left outside either band:\n"
+              << "a lower and an upper curve that stay non-negative, and intervals that hold for the peak and half times --, as\n"
+              << "envbands.octv;  --bands-array=FIRST,LAST (default all)  --bands-axes=X,Y,Z (default 1,1,1)  --bands-seed=S: the seed\n"
+              << "of the resampling counts.  Not in one run with another batched product, --job-error-batches or --reports\n\n";
     return 0;
   }
   // A simulation run makes its tables where it uses them (seconds of host work and GBs of upload

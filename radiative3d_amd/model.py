@@ -491,6 +491,64 @@ class Model:
             raise RuntimeError("write_envshape failed: " + self._lib.r3dh_last_error().decode())
 
     @property
+    def envbands_request(self):
+        """What --envelope-bands=R,LEVEL[,V,T0,O,E[,SMOOTH]] and its companions (--bands-array, --bands-axes, --bands-seed) asked
+        for: None, or dict(first, last, smooth, n_replicates, tail, level, seed, phase_edge, window, axes) -- tail is
+        floor((0.5 (1 - level)) n_replicates), the window as envshape_request's (include/r3d_host.h r3dh_envbands_opts)."""
+        rq = _ffi.EnvBandsOpts()
+        rc = self._lib.r3dh_envbands_request(self._h, C.byref(rq))
+        if rc < 0:
+            raise RuntimeError("envbands_request failed: " + self._lib.r3dh_last_error().decode())
+        if rc == 0:
+            return None
+        return dict(first=int(rq.first), last=int(rq.last), smooth=int(rq.smooth), n_replicates=int(rq.n_replicates),
+                    tail=int(rq.tail), level=float(rq.level), seed=int(rq.seed), phase_edge=tuple(rq.phase_edge),
+                    window=tuple(rq.window), axes=tuple(rq.axes))
+
+    @staticmethod
+    def _envbands_opts(request):
+        edge, window = request.get("phase_edge", (3.6, 0.0)), request.get("window", (0.0, math.nan))
+        R, level = int(request.get("n_replicates", 1000)), float(request.get("level", 0.9))
+        return _ffi.EnvBandsOpts(size=C.sizeof(_ffi.EnvBandsOpts), first=int(request["first"]), last=int(request["last"]),
+                                 smooth=int(request.get("smooth", 8)), n_replicates=R, tail=int(request.get("tail", bands_tail(R, level))),
+                                 seed=int(request.get("seed", 0xB007)), level=level,
+                                 phase_edge=(C.c_double * 2)(*[float(v) for v in edge]),
+                                 window=(C.c_double * 2)(*[float(v) for v in window]),
+                                 axes=(C.c_double * 3)(*[float(v) for v in request.get("axes", (1, 1, 1))]))
+
+    def envbands_plan(self, request=None):
+        """(distances [A], bins [A, 2], clipped [A]) of the bands' array (`request`: a dict as envbands_request gives; None: the
+        model's own): envshape_plan's rule for the request's array and window (include/r3d_host.h r3dh_envbands_plan)."""
+        request = request if request is not None else self.envbands_request
+        if request is None:
+            raise RuntimeError("the model's arguments hold no --envelope-bands")
+        rq = self._envbands_opts(request)
+        A = int(rq.last) - int(rq.first) + 1
+        if A < 1:
+            raise ValueError("envbands request: first > last")
+        dist, bins, clipped = np.zeros(A), np.zeros((A, 2), dtype=np.uint32), np.zeros(A, dtype=np.int32)
+        if self._lib.r3dh_envbands_plan(self._h, C.byref(rq), dist.ctypes.data_as(_ffi._dp),
+                                        bins.ctypes.data_as(C.POINTER(C.c_uint32)), clipped.ctypes.data_as(C.POINTER(C.c_int32))):
+            raise RuntimeError("envbands_plan failed: " + self._lib.r3dh_last_error().decode())
+        return dist, bins, clipped
+
+    def write_envbands(self, path, plan, bands, n_batches, request=None):
+        """Write envbands.octv (include/r3d_host.h r3dh_write_envbands) to `path`: plan = envbands_plan(request), bands the dict
+        Engine.run_batched_envelope_bands returned for the request's array."""
+        request = request if request is not None else self.envbands_request
+        if request is None:
+            raise RuntimeError("the model's arguments hold no --envelope-bands")
+        rq = self._envbands_opts(request)
+        keep = [np.ascontiguousarray(plan[0], dtype=np.float64), np.ascontiguousarray(plan[1], dtype=np.uint32),
+                np.ascontiguousarray(plan[2], dtype=np.int32)]
+        for name in ("envelope", "envelope_lo", "envelope_hi", "shape", "shape_lo", "shape_hi"):
+            keep.append(np.ascontiguousarray(bands[name], dtype=np.float64))
+        keep.append(np.ascontiguousarray(bands["defined"], dtype=np.uint32))
+        res = _ffi.EnvBandsResult(C.sizeof(_ffi.EnvBandsResult), int(n_batches), *[a.ctypes.data for a in keep])
+        if self._lib.r3dh_write_envbands(self._h, C.byref(rq), C.byref(res), str(path).encode()):
+            raise RuntimeError("write_envbands failed: " + self._lib.r3dh_last_error().decode())
+
+    @property
     def envfit_request(self):
         """What --envelope-fit=FILE[,V,T0,O,E[,SMOOTH[,OBSSMOOTH[,MAXLAG_SECONDS]]]] and its companions (--envelope-fit-array,
         --envelope-fit-axes, --envelope-fit-energy) asked for: None, or dict(file, first, last, smooth_syn, smooth_obs,
@@ -819,6 +877,72 @@ def envelope_shape(batch_energy, bins, first, last, weights, smooth=8, with_se=N
                                 stream)
     if rc:
         raise RuntimeError("r3d_envelope_shape failed: " + lib.r3d_last_error().decode())
+    return out
+
+
+def bands_spec(n_seismometers, n_bins, first, last, weights, smooth, n_replicates, tail, seed, bins_ptr):
+    """An r3d_bands_spec (include/r3d.h): an envelope_spec's fields with the replicates R, the tail T (2 T < R) and the seed of
+    the resampling counts."""
+    w = [float(v) for v in weights]
+    if len(w) != _ffi.R3D_N_ENERGY:
+        raise ValueError("five component weights (X, Y, Z, P, S) are needed")
+    return _ffi.BandsSpec(size=C.sizeof(_ffi.BandsSpec), n_seismometers=int(n_seismometers), n_bins=int(n_bins),
+                          first=int(first), last=int(last), smooth=int(smooth), n_replicates=int(n_replicates), tail=int(tail),
+                          d_bins=bins_ptr, seed=int(seed) & (2 ** 64 - 1), weight=(C.c_double * _ffi.R3D_N_ENERGY)(*w))
+
+
+def bands_tail(n_replicates, level):
+    """The tail T that ./main --envelope-bands=R,LEVEL takes: floor((0.5 (1 - LEVEL)) R); the achieved level is 1 - 2 T / R."""
+    return int(math.floor((0.5 * (1.0 - float(level))) * float(n_replicates)))
+
+
+def bootstrap_counts(seed, n_batches, n_replicates):
+    """r3d_bootstrap_counts (host): the resampling counts [R, B] uint8 of the seed, every row summing to B."""
+    lib = _ffi.hip_lib()
+    counts = np.zeros((max(int(n_replicates), 0), max(int(n_batches), 0)), dtype=np.uint8)
+    if lib.r3d_bootstrap_counts(int(seed) & (2 ** 64 - 1), int(n_batches), int(n_replicates), counts.ctypes.data):
+        raise RuntimeError("r3d_bootstrap_counts failed: " + lib.r3d_last_error().decode())
+    return counts
+
+
+def envelope_bands(batch_energy, bins, first, last, weights, smooth=8, n_replicates=1000, tail=50, seed=0xB007, with_envelope=True,
+                   stream=None):
+    """r3d_envelope_bands on torch tensors of one device: batch_energy [B, S, n_bins, 5] float64 are B >= 2 batch blocks, the
+    array the receivers first .. last (A of them), bins [A, 2] int32 each receiver's window of bins b0, b1, weights the five
+    component weights (>= 0), smooth the three-point passes; the batches are resampled n_replicates times by the counts of
+    `seed`, and tail values are left outside either band (2 tail < n_replicates).  Returns a dict of tensors, all WRITTEN:
+    envelope, envelope_lo, envelope_hi [A, n_bins] (with_envelope), shape, shape_lo, shape_hi [A, 6], defined [A, 6] (int32: the
+    replicates whose number is not NaN), bad [1] (int64).  include/r3d.h has the arithmetic.  Asynchronous on `stream` (a raw
+    hipStream_t; None: torch's current one)."""
+    import torch
+    lib = _ffi.hip_lib()
+    if batch_energy.dim() != 4 or batch_energy.shape[3] != _ffi.R3D_N_ENERGY or batch_energy.dtype != torch.float64:
+        raise ValueError("batch_energy must be float64 [B, S, n_bins, 5]")
+    if not batch_energy.is_cuda or not batch_energy.is_contiguous():
+        raise ValueError("the blocks must be a contiguous tensor on a GPU")
+    B, S, n_bins = (int(v) for v in batch_energy.shape[:3])
+    dev = batch_energy.device
+    A = int(last) - int(first) + 1
+    if A < 1 or last >= S:
+        raise ValueError("the array first .. last must lie within the blocks' seismometers")
+    if tuple(bins.shape) != (A, 2) or bins.element_size() != 4 or bins.dtype.is_floating_point or bins.device != dev \
+            or not bins.is_contiguous():
+        raise ValueError("bins must be a contiguous 32-bit integer tensor [A, 2] on the blocks' GPU")
+
+    def f64(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=dev)
+    names = ("envelope", "envelope_lo", "envelope_hi", "shape", "shape_lo", "shape_hi", "defined", "bad")
+    out = {k: (f64(A, n_bins) if with_envelope else None) for k in names[:3]}
+    out.update({k: f64(A, _ffi.R3D_ENVELOPE_N_SHAPE) for k in names[3:6]})
+    out["defined"] = torch.empty((A, _ffi.R3D_ENVELOPE_N_SHAPE), dtype=torch.int32, device=dev)
+    out["bad"] = torch.zeros(1, dtype=torch.int64, device=dev)
+    spec = bands_spec(S, n_bins, first, last, weights, smooth, n_replicates, tail, seed, bins.data_ptr())
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.r3d_envelope_bands(dev.index or 0, B, batch_energy.data_ptr(), C.byref(spec),
+                                *[out[k].data_ptr() if out[k] is not None else None for k in names], stream)
+    if rc:
+        raise RuntimeError("r3d_envelope_bands failed: " + lib.r3d_last_error().decode())
     return out
 
 
@@ -1645,6 +1769,31 @@ class Engine:
         res, ese, cse = _run_batched_to_host(self._lib, "r3d_run_batched_envelope_shape", self._e, m, n, first_id, seed,
                                              n_batches, None, C.byref(spec), C.byref(out))
         return res, ese, cse, shp
+
+    def run_batched_envelope_bands(self, n, n_batches, bins, first, last, weights, smooth=8, n_replicates=1000, tail=50,
+                                   bands_seed=0xB007, first_id=0, seed=0x5EED):
+        """run_batched that also makes the bootstrap percentile bands of the receivers first .. last where the batch blocks
+        lie (include/r3d.h r3d_run_batched_envelope_bands): bins [A, 2] each receiver's window b0, b1 (host;
+        Model.envbands_plan or Model.envshape_plan makes them), weights the five component weights, smooth the three-point
+        passes, n_replicates resamples by the counts of bands_seed, tail values outside either band.  Returns (Result,
+        energy_se, counts_se, bands): a dict of envelope, envelope_lo, envelope_hi [A, n_bins], shape, shape_lo, shape_hi [A,
+        6] and defined [A, 6] (uint32)."""
+        m = self.model
+        A = int(last) - int(first) + 1
+        if A < 1:
+            raise ValueError("the array needs first <= last")
+        b = np.ascontiguousarray(bins, dtype=np.uint32)
+        if b.shape != (A, 2):
+            raise ValueError("bins must be [A, 2]")
+        spec = bands_spec(m.n_seismometers, m.n_bins, first, last, weights, smooth, n_replicates, tail, bands_seed, b.ctypes.data)
+        six = _ffi.R3D_ENVELOPE_N_SHAPE
+        bands = dict(envelope=np.zeros((A, m.n_bins)), envelope_lo=np.zeros((A, m.n_bins)), envelope_hi=np.zeros((A, m.n_bins)),
+                     shape=np.zeros((A, six)), shape_lo=np.zeros((A, six)), shape_hi=np.zeros((A, six)),
+                     defined=np.zeros((A, six), dtype=np.uint32))
+        out = _ffi.BandsResult(size=C.sizeof(_ffi.BandsResult), **{k: v.ctypes.data for k, v in bands.items()})
+        res, ese, cse = _run_batched_to_host(self._lib, "r3d_run_batched_envelope_bands", self._e, m, n, first_id, seed,
+                                             n_batches, None, C.byref(spec), C.byref(out))
+        return res, ese, cse, bands
 
     def run_batched_envelope_misfit(self, n, n_batches, bins, observed, first, last, weights, smooth_syn=8, smooth_obs=0,
                                     max_lag=0, amplitude=1, first_id=0, seed=0x5EED):
