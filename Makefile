@@ -6,7 +6,7 @@
 #   make repro      radiative3d_amd/lib/libr3d_hip_repro.so  (the same engine, bit-defined per history)
 #   make oracle     oracle/libr3d_oracle.so, oracle/libr3d_tables_oracle.so  (g++; test infrastructure)
 #   make cli        ./main                               (g++; the reference's command-line surface)
-#   make devtest    tests/emul/libr3d_{physics,tables}_device{,_repro}.so  (hipcc, gfx950; test infrastructure)
+#   make devtest    tests/emul/libr3d_{physics,tables,collect}_device{,_repro}.so  (hipcc, gfx950; test infrastructure)
 #   make emul       tests/emul/libr3d_emul.so            (g++; the kernels' per-lane code on the host, test infrastructure)
 #   make stepfinals radiative3d_amd/lib/variant_STEPFINALS.so  (make variant NAME=STEPFINALS ...; test infrastructure)
 #   make variant NAME=X DEFS=... [DEFS_CYL= DEFS_TET= DEFS_SPH=]   a developer build of the engine (at the end of this file)
@@ -162,7 +162,9 @@ oracle/libr3d_tables_oracle.so: oracle/r3d_tables_oracle.cpp
 # named BEFORE the source on the command line: hipcc reads whatever follows a .hip file as HIP text.)
 # The table builders entry by entry (tests/test_tables_build_device.py): thin test-only entries linked with the table
 # OBJECTS of the two engine builds -- the code libr3d_hip.so and libr3d_hip_repro.so carry, not a sibling compilation.
-DEVTESTS    := physics tables
+# The receiver collection arrival by arrival (tests/test_collect_device.py): a sibling compilation again, of r3d_pool.h's
+# pool_collect_pairs, r3d_wave.h and r3d_step.h's collect.
+DEVTESTS    := physics tables collect
 HDR_physics := tests/emul/physics_cases.h
 device_test_lib = tests/emul/libr3d_$(1)_device$(call build_suffix,$(2)).so
 # device_test(name, build): tests/emul/<name>_device.hip under the build's flags, with the build's table object
